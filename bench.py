@@ -11,9 +11,12 @@ ITERATION of the reference loop (train_lora_xl.py:162-356): k partial-denoise UN
 loss, backward into the adapters, (all-reduce,) AdamW.  The metric counts UNet denoise steps
 (= predict_noise calls = UNet forwards on a CFG pair): value = sum_i (k_i + 4) * N / wall.
 Weights are seeded random-init with the real SDXL shapes and text embeddings are seeded randn (no checkpoints
-exist offline) - throughput does not depend on the values.
+exist offline) - throughput does not depend on the values.  The same arguments give the same inputs in every run:
+--dump-outputs DIR writes what the last timed step computed (bench.dump_outputs) so that two builds can be compared.
 
-"extra_configs" (N=1 default run only): the same loop on BASELINE configs[1] (SD-1.x 512x512 text slider) and configs[4] (SDXL
+A plain run sets up, warms up, times --steps iterations and prints the result line.  Everything below is measured only with --full.
+
+"extra_configs" (N=1 run of the contract configuration only): the same loop on BASELINE configs[1] (SD-1.x 512x512 text slider) and configs[4] (SDXL
 image slider, 512x512 pairs, VAE encode on the GPU, with "vae_roofline" for the fp32 VAE GEMM in both arithmetic modes), timed by
 this process after the contract line.
 
@@ -56,7 +59,16 @@ def parse():
                     help="image workload: the VAE's fp32 operands as bf16 hi+lo halves (narrower than the reference's fp32 VAE; "
                          "the default is the exact-fp32 MFMA)")
     ap.add_argument("--seed", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the same loop with the frozen predictions run as three CFG pairs, "
+                         "the roofline replay, the CPU baselines, the extra_configs and, under torch.distributed.run, the replica check "
+                         "and all-reduce timing (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def gemm_flops(d):
@@ -477,6 +489,19 @@ def cpu_baseline(model, hw):
                       f"UNet{note}"}
 
 
+def dump_outputs(out_dir, tr, store, workload):
+    """What the last timed step computed, as a caller of the training iteration receives it: its loss (both losses of the image
+    slider) and the adapter state it left - the updated parameters, that step's gradient buffer and AdamW's first moment - each whole,
+    as float32 (3 x 4.32 M elements for the SDXL slider: 52 MB).  Two runs of one build agree to rounding, not bit for bit: the
+    gradient buffer differs in its last bits from run to run (SDXL: up to 7e-12 against values up to 2e-4), the parameters by one bf16
+    step where that moves a rounding; the loss is equal."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    losses = {"loss_high": tr.loss_high, "loss_low": tr.loss_low} if workload == "image" else {"loss": tr.loss}
+    for name, t in dict(losses, lora_params=store.params, lora_grads=store.grads, lora_exp_avg=store.exp_avg).items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def params_hash64(store) -> int:
     """64-bit digest of the replicated adapter state (flat parameters, both moments and - train.precision float32 - the fp32 master the
     bf16 parameters are rounded from): sum and xor-fold of the raw 16-bit words, computed on the device, exact in int64.  Equal state ->
@@ -551,7 +576,7 @@ def main():
     dev = torch.device("cuda", local if torch.distributed.is_initialized() else 0)
     torch.cuda.set_device(dev)
     res = run_config(a, dev, world, rank, main_line=True)
-    if rank == 0 and world == 1 and not a.no_extra and a.workload == "text" and a.model == "sdxl" and a.res == 1024:
+    if a.full and rank == 0 and world == 1 and not a.no_extra and a.workload == "text" and a.model == "sdxl" and a.res == 1024:
         # the other single-GPU configurations of BASELINE.json, timed by the same process right after the contract line
         # (untimed for the contract): configs[1] and configs[4]
         extra = []
@@ -651,7 +676,7 @@ def run_config(a, dev, world, rank, main_line):
     for i in range(a.warmup):
         one_step(i)
     barrier()
-    tr.time_allreduce = dist_on          # event pair around every gradient all-reduce (on the stream it is ordered on)
+    tr.time_allreduce = dist_on and a.full          # event pair around every gradient all-reduce (on the stream it is ordered on)
     t0 = time.time()
     unet_steps = 0
     for i in range(a.steps):
@@ -663,9 +688,11 @@ def run_config(a, dev, world, rank, main_line):
         torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tdt.item())
     loss = float(tr.loss_low.item() if a.workload == "image" else tr.loss.item())
-    dp_check = dp_self_check(tr, store, dev, rank, world) if dist_on else None
+    if a.dump_outputs and rank == 0 and main_line:
+        dump_outputs(a.dump_outputs, tr, store, a.workload)
+    dp_check = dp_self_check(tr, store, dev, rank, world) if dist_on and a.full else None
     value_no_dedup = None
-    if a.workload == "text" and rank == 0 and world == 1 and main_line:
+    if a.full and a.workload == "text" and rank == 0 and world == 1 and main_line:
         # the headline counts the de-duplicated B=3 frozen pass as the 3 predictions the reference executes; the same loop
         # with the three CFG-pair passes actually run, for comparison (not the contract value)
         tr.dedup_frozen = False
@@ -707,7 +734,7 @@ def run_config(a, dev, world, rank, main_line):
         res["data_parallel"] = dp_check
     if rank == 0:
         print("[bench] timed region done: " + json.dumps({k: res[k] for k in ("value", "ms_per_step")}), file=sys.stderr, flush=True)
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         eng.set_lora(True, 1.0)
         # counter passes exist for the LoRA-on no-grad pass of each configuration (scripts/measure_round.sh); the image slider's
         # training-pass roofline gets none
@@ -715,7 +742,7 @@ def run_config(a, dev, world, rank, main_line):
         res["roofline"] = measure_roofline(eng, eng.plan(2, hw, hw, "on" if a.workload == "text" else "train"), pmc_tag=tag)
         if a.workload == "image":
             res["vae_roofline"] = measure_vae_roofline(vae, vae_sd, imgs[0], a.res)
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         if not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.model, hw)
             try:

@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
 cd /tmp
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- python $R/bench.py --no-cpu-baseline --no-extra > $O/${RTAG}_prof_bench.log 2>&1
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- python $R/bench.py --full --no-cpu-baseline --no-extra > $O/${RTAG}_prof_bench.log 2>&1
 find /tmp/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/${RTAG}_bench_sdxl1024_kernel_stats.csv \;
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_fwd -o fwd -- python $R/scripts/bench_forward.py --lora --warm 1 --iters 3 > $O/${RTAG}_prof_fwd.log 2>&1
 find /tmp/prof_fwd -name "*kernel_stats.csv" -exec cp {} $O/${RTAG}_fwd_lora_on_kernel_stats.csv \;
@@ -34,7 +34,7 @@ pmc_set ""
 pmc_set _sd1_64 --model sd1 --hw 64
 pmc_set _sdxl_64 --model sdxl --hw 64
 cd $R
-timeout 600 python bench.py > $O/${RTAG}_bench_line.json 2> $O/${RTAG}_bench_line.err
+timeout 600 python bench.py --full > $O/${RTAG}_bench_line.json 2> $O/${RTAG}_bench_line.err
 timeout 300 python scripts/time_train_iter.py --breakdown > $O/${RTAG}_iteration_pieces.txt 2>&1
 timeout 200 python scripts/probe_gn.py > $O/${RTAG}_probe_gn.txt 2>&1
 timeout 200 python scripts/probe_attn.py > $O/${RTAG}_probe_attn.txt 2>&1

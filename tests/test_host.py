@@ -862,6 +862,33 @@ def test_bench_gpus_flag_relaunches_or_refuses():
         assert r.returncode != 0 and "n_gpus" not in r.stdout and "--gpus 2" in r.stderr
 
 
+def test_bench_dump_outputs_are_float32_and_fit_64mb(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the loss and the adapter state the last timed step left, one float32 .npy each, exactly the
+    values of the device buffers, within 64 MB at the benchmarked SDXL size."""
+    import sys
+    import types
+
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    st = LoraStore(CONFIGS["sdxl"](), rank=4, alpha=1.0, train_method="noxattn", device="cpu")
+    g = torch.Generator().manual_seed(0)
+    for t in (st.params, st.grads, st.exp_avg):
+        t.copy_(torch.randn(t.shape, generator=g))
+    bench.dump_outputs(str(tmp_path), types.SimpleNamespace(loss=torch.tensor([0.125])), st, "text")
+    files = {p.name: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(files) == ["lora_exp_avg.npy", "lora_grads.npy", "lora_params.npy", "loss.npy"]
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert files["loss.npy"].tolist() == [0.125]
+    assert np.array_equal(files["lora_params.npy"], st.params.float().numpy())
+    assert np.array_equal(files["lora_grads.npy"], st.grads.numpy())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2 ** 20
+    # a plain command line measures the headline only
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+
+
 def test_gemm_kernel_name_comes_from_the_library():
     """slh_gemm_kernel_name: the kernel a descriptor runs on, named by the dispatch code itself (no device needed) - bench.py and the
     PMC pairing use it instead of rebuilding template arguments from tile codes."""

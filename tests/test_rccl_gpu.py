@@ -84,7 +84,7 @@ def test_bench_under_torchrun_one_rank(dev):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_FORCE_PROCESS_GROUP="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--model", "sd1", "--res", "256", "--no-cpu-baseline", "--no-roofline", "--no-extra"]
+           "--model", "sd1", "--res", "256", "--full", "--no-cpu-baseline", "--no-roofline", "--no-extra"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
