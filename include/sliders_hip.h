@@ -156,9 +156,6 @@ typedef struct slh_gemm_desc {
     const void* pf_ptr; int64_t pf_bytes;
 } slh_gemm_desc;
 int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream);
-/* (WM<<12)|(MI<<8)|(NI<<4)|mode of the kernel instantiation gemm_kernel<MI,NI,mode,..,WM> slh_gemm would launch for d
- * (used by bench.py to attribute measured time and algorithmic FLOPs to one profiled kernel name). */
-int slh_gemm_variant(const slh_gemm_desc* d);
 /* Name of the kernel instantiation slh_gemm would launch for d, as rocprofv3 --kernel-trace prints it without namespace and parameter
  * list (e.g. "gemm8pb_kernel<1, 5, 0, false>", "gemm5_kernel<false, 4>"), written to buf (cap >= 16 bytes, NUL-terminated).  All of
  * slh_gemm's checks and its dispatch run; the launch is replaced by a record of the selected template, so the name is exact for
@@ -168,8 +165,7 @@ int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap);
 /* The 64 x 160 tile (tile code bits 12-15 = 5, e.g. 0x5425; csrc/gemm5.hip): 4 waves of 32 x 80 on the 16 x 16 x 32 MFMA, 4-slot LDS
  * ring - the M = 2048, N = 1280 products as 256 workgroups = one full round of the chip.  Dense single-source products with packed
  * weights (w_layout = 1), M % 64 == 0, N % 160 == 0; epilogue: bias, residual, ln_out - whose chunks are then 80 COLUMNS wide:
- * ln_out [N/80][M][2], and the consumer's ln_in_chunks = K / 80.  slh_gemm5_ok(d) = 1 where it can run the descriptor. */
-int slh_gemm5_ok(const slh_gemm_desc* d);
+ * ln_out [N/80][M][2], and the consumer's ln_in_chunks = K / 80. */
 /* The tiles of csrc/gemm7.hip (tile code bits 12-15 = 7: 0x7<S><XB><WB>): 128 x 256 (0x7648) and 128 x 160 (0x7645) - four loader waves
  * that issue the ring's LDS-DMA + four compute waves, one per SIMD, each a 64 x (16 WB) register tile of 16 x 16 x 32 MFMAs - and 256 x 320
  * (0x748a) on eight compute waves that stage the ring themselves (GEGLU.proj as one round of 256 workgroups); ring of S half K tiles (32
@@ -177,8 +173,16 @@ int slh_gemm5_ok(const slh_gemm_desc* d);
  * K % 64 == 0, K >= 32 S.  Epilogue: bias, residual, ln_in, geglu = 3 on all three; on the 128-row tiles also ln_out (64-column chunks;
  * 80-column chunks on 0x7645), ln_mr_out, vt_out / vt_also_c (vt_col0 % (16 WB) == 0, vt_tokens % 128 == 0) and - 0x7648 only - one fused
  * adapter of 1-3 column groups (forward form, every tile inside one group; with ln_in also its own fold: ln_lora_s / ln_lora_c) and
- * lora_t_out.  No split-K, row bias, external T, geglu 1 / 2, cross-attention.  slh_gemm7_ok(d) = 1 where d->tile can run d. */
-int slh_gemm7_ok(const slh_gemm_desc* d);
+ * lora_t_out.  No split-K, row bias, external T, geglu 1 / 2, cross-attention. */
+/* 1 where the tile named by d->tile (0: the one slh_gemm's own heuristic picks) can run d's shape and features: every check of
+ * slh_gemm except what a caller provisions once the tile is chosen - the split-K slab / ticket workspace and its slab count, and
+ * ln_lora_s / ln_lora_c.  slh_gemm runs this check first and returns its status, so a query and a launch cannot disagree.  Needs
+ * no device. */
+int slh_gemm_tile_ok(const slh_gemm_desc* d);
+/* Width of the LayerNorm chunks (ln_out) d's tile writes: 80 columns on the 64 x 160 tile and on 0x7645, 64 on the other tiles
+ * that take ln_out (128-column ring tiles, 0x8042, 0x7648) - the producer's ln_out is [N / width][M][2] and its consumers'
+ * ln_in_chunks = K / width.  0 when d carries no ln_out or slh_gemm_tile_ok(d) is 0. */
+int slh_gemm_ln_chunk_cols(const slh_gemm_desc* d);
 
 /* ------------------------------------------------------------------------------------------------
  * slh_skinny: T[M][R] = A[M][K] . Wd[R][K]^T (+bias), R <= 16, same A addressing as slh_gemm.

@@ -477,6 +477,8 @@ int launch_gemm(const GemmArgs& a, int mode, int stages, hipStream_t s) {
 
 int slh_gemm5_launch(const slh_gemm_desc* d, slh_stream_t stream);      // gemm5.hip
 int slh_gemm7_launch(const slh_gemm_desc* d, slh_stream_t stream);      // gemm7.hip
+bool gemm5_tile_ok(const slh_gemm_desc* d);                             // gemm5.hip: the 64 x 160 tile's own rule
+bool gemm7_tile_ok(const slh_gemm_desc* d);                             // gemm7.hip: the four-wave tiles' own rule
 
 static int slh_ncu() {
     static const int ncu = [] {
@@ -549,14 +551,19 @@ extern "C" int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap) 
     return rc;
 }
 
-// (MI<<8)|(NI<<4)|mode of the kernel instantiation slh_gemm would launch: gemm_kernel<MI, NI, mode>
-extern "C" int slh_gemm_variant(const slh_gemm_desc* d) {
-    int MI, NI, WM;
-    pick_tile(d, MI, NI, WM);
-    return (WM << 12) | (MI << 8) | (NI << 4) | (d->mode & 15);
+// K slices a launch of d runs (1: no split-K): the factor S of tile bits 16-19, cut so that every slice is non-empty - each publishes
+// its whole partial tile, the last one to arrive reads them all; per = K tiles per slice
+static int gemm_splitk(const slh_gemm_desc* d, int& per) {
+    const int nk = d->K / 64, s = (d->tile >> 16) & 15;
+    per = nk;
+    if (s <= 1) return 1;
+    per = (nk + s - 1) / s;
+    return (nk + per - 1) / per;
 }
 
-extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
+// Every check of slh_gemm except what the caller provisions once the tile is chosen (the split-K slab / ticket workspace and its slab
+// count, ln_lora_s / ln_lora_c): 0, or the status slh_gemm returns for d with slh_last_error saying why
+static int gemm_check(const slh_gemm_desc* d) {
     SLH_CHECK(d && d->a0 && d->w && d->c, "slh_gemm: null pointer");
     SLH_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "slh_gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
     SLH_CHECK((d->tile >> 20) == 0, "slh_gemm: tile 0x%x uses reserved bits (20 and up must be zero)", d->tile);
@@ -612,8 +619,21 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
                   "slh_gemm: geglu = 3 (16 | 16 weight blocks) needs N %% 32 == 0 and excludes adapters, residual, row bias, geglu_pre, vt_out, ln_out");
     SLH_CHECK(d->geglu >= 0 && d->geglu <= 3, "slh_gemm: geglu is 0, 1 / 3 (forward epilogue, 32 | 32 or 16 | 16 weight blocks) or 2 (backward form)");
 
-    if (((d->tile >> 12) & 15) == 7) return slh_gemm7_launch(d, stream);      // the four-wave tiles (gemm7.hip): their own descriptor checks
-    if (((d->tile >> 12) & 15) == 5) return slh_gemm5_launch(d, stream);      // the 64 x 160 tile (gemm5.hip): its own descriptor checks
+    if (((d->tile >> 12) & 15) == 7) {
+        SLH_CHECK(gemm7_tile_ok(d),
+                  "slh_gemm: the tiles of gemm7.hip (0x7<S><XB><WB>: 0x7648 = 128 x 256, 0x7645 = 128 x 160, 0x748a = 256 x 320) run dense "
+                  "single-source products with packed weights, M %% (32 XB) == 0, N %% (32 WB) == 0, K >= 32 S; bias / residual / ln_out / ln_in / "
+                  "fused adapter (128 x 256) / vt_out / geglu = 3 only (256 x 320: bias / residual / ln_in / geglu = 3) (tile 0x%x M=%d N=%d K=%d)",
+                  d->tile, d->M, d->N, d->K);
+        return 0;
+    }
+    if (((d->tile >> 12) & 15) == 5) {
+        SLH_CHECK(gemm5_tile_ok(d),
+                  "slh_gemm: the 64 x 160 tile (0x5xxx) runs dense single-source products with packed weights, M %% 64 == 0, N %% 160 == 0, "
+                  "bias / residual / ln_out / ln_in / one fused rank-4 adapter only (M=%d N=%d K=%d)", d->M, d->N, d->K);
+        SLH_CHECK(((d->tile >> 16) & 15) <= 1, "slh_gemm: the 64 x 160 tile has no split-K");
+        return 0;
+    }
     int MI = 2, NI = 2, WM = 2;
     pick_tile(d, MI, NI, WM);
     if (WM == 8) {
@@ -622,13 +642,92 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
         SLH_CHECK(!d->lora_down || MI == 1, "slh_gemm: the 256 x 256 tile does not take a fused adapter (lora_down)");
         SLH_CHECK(!d->vt_out || (MI == 4 && NI == 2) || (MI == 1 && NI == 4 && d->mode == 0),
                   "slh_gemm: vt_out on the ping-pong tiles needs 256 x 256 (0x8042) or the dense 128 x 256 tile (0x8014)");
+        // (geglu = 1 and ln_out need NI = 2, below)
+        SLH_CHECK(d->geglu != 2 || MI == 4, "slh_gemm: the 128 x 64*NI ping-pong tiles have no GEGLU backward epilogue (geglu = 2)");
     } else {
         SLH_CHECK((MI == 1 || MI == 2) && (NI == 1 || NI == 2), "slh_gemm: bad tile");
         SLH_CHECK(WM == 2 || NI == 2 || MI == 1, "slh_gemm: 8-wave tiles are 128x64, 128x128 or 256x128");
     }
     SLH_CHECK(d->w_layout == 0 || d->w_layout == 1, "slh_gemm: bad w_layout");
     if (d->geglu == 1) SLH_CHECK(NI == 2, "slh_gemm: geglu needs NI=2");
+    if (d->vt_out) {
+        SLH_CHECK(d->vt_D > 0 && d->vt_D % 64 == 0 && d->vt_col0 % 128 == 0 && d->vt_col0 < d->N && d->vt_heads > 0 &&
+                      (d->N - d->vt_col0) == d->vt_heads * d->vt_D && d->vt_tokens % 8 == 0 && d->M % d->vt_tokens == 0 &&
+                      d->vt_ld % 8 == 0 && d->vt_ld >= d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
+                  "slh_gemm: vt_out constraints");
+    }
+    if (d->ln_out) {
+        SLH_CHECK(NI == 2 && d->N % 64 == 0 && !d->geglu && !d->vt_out,
+                  "slh_gemm: ln_out needs a 128-column tile (NI = 2), N %% 64 == 0, no GEGLU / vt_out");
+        SLH_CHECK(((uintptr_t)d->ln_out & 7) == 0, "slh_gemm: ln_out alignment");
+    }
+    if (d->ln_in) {
+        SLH_CHECK(d->mode == 0 && !d->a1 && d->ln_s && d->ln_b && !d->bias && !d->lora_t,
+                  "slh_gemm: ln_in needs a dense single-source product, ln_s / ln_b, no bias (folded into ln_b), no external T");
+        if (d->lora_down)
+            SLH_CHECK(WM == 8 && MI == 1 && NI <= 4 && !d->lora_up_rmajor && !d->lora_t_out && !d->ln_mr_out && ((d->tile >> 16) & 15) <= 1,
+                      "slh_gemm: ln_in with a fused adapter runs on the ping-pong 128 x 192 / 128 x 256 tiles (0x8013, 0x8014); forward form, "
+                      "no split-K");
+        SLH_CHECK(d->ln_in_chunks >= 1 && d->ln_in_chunks <= 20 && d->K % d->ln_in_chunks == 0 &&
+                      (d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks),
+                  "slh_gemm: ln_in_chunks must be K / 64 (producer on a 64 / 128-column tile) or K / 80 (producer on the 64 x 160 tile), <= 20");
+        SLH_CHECK(((uintptr_t)d->ln_in & 7) == 0 && ((uintptr_t)d->ln_s & 15) == 0 && ((uintptr_t)d->ln_b & 15) == 0,
+                  "slh_gemm: ln_in / ln_s / ln_b alignment");
+    }
+    SLH_CHECK(!d->vt_also_c || d->vt_out, "slh_gemm: vt_also_c without vt_out");
+    SLH_CHECK(!d->ln_mr_out || d->ln_in, "slh_gemm: ln_mr_out without ln_in");
+    SLH_CHECK(!d->geglu_pre || (d->geglu && d->ld_pre >= (d->geglu == 2 ? 2 * d->N : d->N) && d->ld_pre % 4 == 0 &&
+                                ((uintptr_t)d->geglu_pre & 7) == 0),
+              "slh_gemm: geglu_pre needs the GEGLU epilogue, ld_pre >= N (2N in the backward form), 8-byte alignment");
+    if (d->geglu == 2)
+        SLH_CHECK(d->geglu_pre && d->N % 32 == 0 && d->ldc >= 2 * d->N && d->ldc % 4 == 0 && !d->bias && !d->rowbias && !d->residual &&
+                      !d->lora_t && !d->lora_down && !d->vt_out && !d->ln_in && !d->ln_out,
+                  "slh_gemm: geglu = 2 (backward form) needs geglu_pre, N %% 32 == 0, ldc >= 2N and a bare product");
+    int per;
+    const int splitk = gemm_splitk(d, per);
+    if (splitk > 1) {
+        SLH_CHECK((long)splitk * ((d->M + 255) / 256 * 256L) * ((d->N + 255) / 256 * 256L) * 4 < (1L << 31),
+                  "slh_gemm: split-K slabs beyond 2 GB");
+        if (WM == 8) {
+            // the slab workspace is sized by contract (include/sliders_hip.h: roundup(M, 256) x roundup(N, 128) floats per slice)
+            const int bm = MI == 1 ? 128 : 256, bn = 64 * NI * (MI == 4 ? 2 : 1);
+            SLH_CHECK((long)((d->M + bm - 1) / bm) * bm * ((d->N + bn - 1) / bn) * bn <= ((d->M + 255) / 256 * 256L) * ((d->N + 127) / 128 * 128L),
+                      "slh_gemm: split-K slabs of %d x %d tiles exceed the workspace contract for M=%d N=%d", bm, bn, d->M, d->N);
+        }
+    }
+    if (d->xa_k) {
+        SLH_CHECK(WM == 4 && MI == 1 && NI == 2 && ((d->tile >> 8) & 15) == 4 && splitk == 1,
+                  "slh_gemm: the fused cross-attention runs on the 128 x 128 8-wave ring tile (0x4412), no split-K");
+        SLH_CHECK(d->mode == 0 && !d->lora_down && !d->lora_t && !d->residual && !d->rowbias && !d->geglu && !d->ln_out && !d->vt_out,
+                  "slh_gemm: xa_k excludes adapters, residual, row bias, GEGLU, ln_out, vt_out");
+        SLH_CHECK(d->xa_vt && d->N % 64 == 0 && d->xa_tk >= 1 && d->xa_tk <= 96 && d->xa_tq > 0 && d->xa_tq % 128 == 0 &&
+                      d->M % d->xa_tq == 0 && d->xa_ldvt >= 128 && d->xa_ldvt % 8 == 0 && d->xa_ldk % 8 == 0 &&
+                      d->xa_vt_heads >= d->N / 64 && ((uintptr_t)d->xa_k & 15) == 0 && ((uintptr_t)d->xa_vt & 15) == 0,
+                  "slh_gemm: xa_* need head dim 64 (N %% 64 == 0), 1 <= xa_tk <= 96, xa_tq %% 128 == 0, M %% xa_tq == 0, "
+                  "xa_ldvt >= 128 (two 64-key tiles are staged), 16-byte aligned keys / values");
+    }
+    return 0;
+}
 
+extern "C" int slh_gemm_tile_ok(const slh_gemm_desc* d) { return gemm_check(d) == 0; }
+
+extern "C" int slh_gemm_ln_chunk_cols(const slh_gemm_desc* d) {
+    if (!d || !d->ln_out || gemm_check(d) != 0) return 0;
+    const int fam = (d->tile >> 12) & 15;
+    if (fam == 5) return 80;                                    // a wave of the 64 x 160 tile owns 80 columns
+    if (fam == 7) return (d->tile & 15) == 5 ? 80 : 64;         // four-wave tiles: 0x7645's waves own 80 columns, 0x7648's 128
+    return 64;                                                  // the 128-column tiles of gemm.hip / gemm8p.hip
+}
+
+extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
+    const int rc = gemm_check(d);
+    if (rc) return rc;
+    SLH_CHECK(!(d->ln_in && d->lora_down) || (d->ln_lora_s && d->ln_lora_c),
+              "slh_gemm: ln_in with a fused adapter needs ln_lora_s / ln_lora_c (lora_down = A . gamma)");
+    if (((d->tile >> 12) & 15) == 7) return slh_gemm7_launch(d, stream);      // the four-wave tiles (gemm7.hip)
+    if (((d->tile >> 12) & 15) == 5) return slh_gemm5_launch(d, stream);      // the 64 x 160 tile (gemm5.hip)
+    int MI = 2, NI = 2, WM = 2;
+    pick_tile(d, MI, NI, WM);
     GemmArgs a;
     a.a0 = (const __bf16*)d->a0; a.a1 = (const __bf16*)d->a1; a.w = (const __bf16*)d->w;
     a.bias = (const __bf16*)d->bias; a.rowbias = (const __bf16*)d->rowbias; a.lora_t = d->lora_t;
@@ -645,49 +744,14 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
     a.w_packed = d->w_layout;
     a.vt = (__bf16*)d->vt_out; a.vt_col0 = d->vt_col0; a.vt_D = d->vt_D; a.vt_heads = d->vt_heads;
     a.vt_tokens = d->vt_tokens; a.vt_ld = d->vt_ld;
-    if (d->vt_out) {
-        SLH_CHECK(d->vt_D > 0 && d->vt_D % 64 == 0 && d->vt_col0 % 128 == 0 && d->vt_col0 < d->N && d->vt_heads > 0 &&
-                      (d->N - d->vt_col0) == d->vt_heads * d->vt_D && d->vt_tokens % 8 == 0 && d->M % d->vt_tokens == 0 &&
-                      d->vt_ld % 8 == 0 && d->vt_ld >= d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
-                  "slh_gemm: vt_out constraints");
-    }
     a.ln_out = d->ln_out; a.ln_in = d->ln_in; a.ln_s = d->ln_s; a.ln_b = d->ln_b;
     a.ln_in_chunks = d->ln_in_chunks; a.ln_eps = d->ln_eps;
-    if (d->ln_out) {
-        SLH_CHECK(NI == 2 && d->N % 64 == 0 && !d->geglu && !d->vt_out,
-                  "slh_gemm: ln_out needs a 128-column tile (NI = 2), N %% 64 == 0, no GEGLU / vt_out");
-        SLH_CHECK(((uintptr_t)d->ln_out & 7) == 0, "slh_gemm: ln_out alignment");
-    }
-    if (d->ln_in) {
-        SLH_CHECK(d->mode == 0 && !d->a1 && d->ln_s && d->ln_b && !d->bias && !d->lora_t,
-                  "slh_gemm: ln_in needs a dense single-source product, ln_s / ln_b, no bias (folded into ln_b), no external T");
-        if (d->lora_down)
-            SLH_CHECK(WM == 8 && MI == 1 && NI <= 4 && d->ln_lora_s && d->ln_lora_c && !d->lora_up_rmajor && !d->lora_t_out && !d->ln_mr_out &&
-                          ((d->tile >> 16) & 15) <= 1,
-                      "slh_gemm: ln_in with a fused adapter runs on the ping-pong 128 x 192 / 128 x 256 tiles (0x8013, 0x8014) and needs "
-                      "ln_lora_s / ln_lora_c (lora_down = A . gamma); forward form, no split-K");
-        SLH_CHECK(d->ln_in_chunks >= 1 && d->ln_in_chunks <= 20 && d->K % d->ln_in_chunks == 0 &&
-                      (d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks),
-                  "slh_gemm: ln_in_chunks must be K / 64 (producer on a 64 / 128-column tile) or K / 80 (producer on the 64 x 160 tile), <= 20");
-        SLH_CHECK(((uintptr_t)d->ln_in & 7) == 0 && ((uintptr_t)d->ln_s & 15) == 0 && ((uintptr_t)d->ln_b & 15) == 0,
-                  "slh_gemm: ln_in / ln_s / ln_b alignment");
-    }
-    a.splitk = (d->tile >> 16) & 15;
     a.c32 = d->splitk_c32;
     a.t32 = d->splitk_t32;
     a.ticket = (unsigned long long*)d->splitk_ticket;
     a.ln_mr_out = d->ln_mr_out;
     a.geglu_pre = (__bf16*)d->geglu_pre; a.ld_pre = d->ld_pre;
     a.vt_also_c = d->vt_also_c;
-    SLH_CHECK(!d->vt_also_c || d->vt_out, "slh_gemm: vt_also_c without vt_out");
-    SLH_CHECK(!d->ln_mr_out || d->ln_in, "slh_gemm: ln_mr_out without ln_in");
-    SLH_CHECK(!d->geglu_pre || (d->geglu && d->ld_pre >= (d->geglu == 2 ? 2 * d->N : d->N) && d->ld_pre % 4 == 0 &&
-                                ((uintptr_t)d->geglu_pre & 7) == 0),
-              "slh_gemm: geglu_pre needs the GEGLU epilogue, ld_pre >= N (2N in the backward form), 8-byte alignment");
-    if (d->geglu == 2)
-        SLH_CHECK(d->geglu_pre && d->N % 32 == 0 && d->ldc >= 2 * d->N && d->ldc % 4 == 0 && !d->bias && !d->rowbias && !d->residual &&
-                      !d->lora_t && !d->lora_down && !d->vt_out && !d->ln_in && !d->ln_out,
-                  "slh_gemm: geglu = 2 (backward form) needs geglu_pre, N %% 32 == 0, ldc >= 2N and a bare product");
     // same-XCD slab reads (gemm_common.h, split-K epilogue): gfx950 only, SLIDERS_SPLITK_LOCAL=0 turns them off
     static const int splitk_local_ok = [] {
         const char* e = getenv("SLIDERS_SPLITK_LOCAL");
@@ -698,54 +762,26 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
         return strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 0;
     }();
     a.splitk_local = splitk_local_ok;
-    a.kper = d->K / 64;
-    if (a.splitk > 1) {
-        // every slice must be non-empty: each publishes its whole partial tile, the last one to arrive reads them all
-        const int nk = d->K / 64;
-        const int per = (nk + a.splitk - 1) / a.splitk;
-        a.splitk = (nk + per - 1) / per;
-        a.kper = per;
-        SLH_CHECK((a.splitk - 1) * per < nk, "slh_gemm: internal: empty K slice (%d slices of %d over %d K tiles)", a.splitk, per, nk);
-    }
+    a.splitk = gemm_splitk(d, a.kper);
     if (a.splitk > 1) {
         SLH_CHECK(d->splitk_c32, "slh_gemm: split-K needs the fp32 slab workspace splitk_c32");
         SLH_CHECK(d->splitk_slabs >= a.splitk, "slh_gemm: split-K into %d slices but the workspace holds %d slabs", a.splitk,
                   d->splitk_slabs);
         SLH_CHECK(d->splitk_ticket, "slh_gemm: split-K needs the arrival tickets splitk_ticket (zeroed once)");
-        SLH_CHECK((long)a.splitk * ((d->M + 255) / 256 * 256L) * ((d->N + 255) / 256 * 256L) * 4 < (1L << 31),
-                  "slh_gemm: split-K slabs beyond 2 GB");
         SLH_CHECK(((uintptr_t)d->splitk_ticket & 7) == 0 && d->N % 4 == 0, "slh_gemm: split-K needs N %% 4 == 0 and 8-byte aligned tickets");
         SLH_CHECK(!d->lora_down || a.t32, "slh_gemm: split-K with a fused adapter needs the slab workspace splitk_t32");
         SLH_CHECK(((uintptr_t)d->splitk_c32 & 15) == 0 && ((uintptr_t)d->splitk_t32 & 15) == 0, "slh_gemm: slab alignment");
-    } else {
-        a.splitk = 1;
     }
     a.store16 = (d->ldc % 8 == 0) && (((uintptr_t)d->c & 15) == 0);
     a.ln_lora_s = d->ln_lora_s; a.ln_lora_c = d->ln_lora_c;
     a.xa_k = (const __bf16*)d->xa_k; a.xa_vt = (const __bf16*)d->xa_vt;
     a.xa_tk = d->xa_tk; a.xa_tq = d->xa_tq; a.xa_ldk = d->xa_ldk; a.xa_ldvt = d->xa_ldvt; a.xa_vt_heads = d->xa_vt_heads;
     a.xa_scale = d->xa_scale;
-    if (d->xa_k) {
-        const int st = (d->tile >> 8) & 15;
-        SLH_CHECK(WM == 4 && MI == 1 && NI == 2 && st == 4 && a.splitk == 1,
-                  "slh_gemm: the fused cross-attention runs on the 128 x 128 8-wave ring tile (0x4412), no split-K");
-        SLH_CHECK(d->mode == 0 && !d->lora_down && !d->lora_t && !d->residual && !d->rowbias && !d->geglu && !d->ln_out && !d->vt_out,
-                  "slh_gemm: xa_k excludes adapters, residual, row bias, GEGLU, ln_out, vt_out");
-        SLH_CHECK(d->xa_vt && d->N % 64 == 0 && d->xa_tk >= 1 && d->xa_tk <= 96 && d->xa_tq > 0 && d->xa_tq % 128 == 0 &&
-                      d->M % d->xa_tq == 0 && d->xa_ldvt >= 128 && d->xa_ldvt % 8 == 0 && d->xa_ldk % 8 == 0 &&
-                      d->xa_vt_heads >= d->N / 64 && ((uintptr_t)d->xa_k & 15) == 0 && ((uintptr_t)d->xa_vt & 15) == 0,
-                  "slh_gemm: xa_* need head dim 64 (N %% 64 == 0), 1 <= xa_tk <= 96, xa_tq %% 128 == 0, M %% xa_tq == 0, "
-                  "xa_ldvt >= 128 (two 64-key tiles are staged), 16-byte aligned keys / values");
-    }
     a.pf_ptr = nullptr; a.pf_bytes = 0; a.pf_blocks = 0;
     if (WM == 8) {
         const int bm = MI == 1 ? 128 : 256, bn = 64 * NI * (MI == 4 ? 2 : 1);
         a.tiles_m = (d->M + bm - 1) / bm;
         a.tiles_n = (d->N + bn - 1) / bn;
-        // the slab workspace is sized by contract (include/sliders_hip.h: roundup(M, 256) x roundup(N, 128) floats per slice)
-        if (a.splitk > 1)
-            SLH_CHECK((long)a.tiles_m * bm * a.tiles_n * bn <= ((d->M + 255) / 256 * 256L) * ((d->N + 127) / 128 * 128L),
-                      "slh_gemm: split-K slabs of %d x %d tiles exceed the workspace contract for M=%d N=%d", bm, bn, d->M, d->N);
         a.group_m = pick_group_m(d, a.tiles_m);
         return launch_gemm8p(a, d->mode, MI == 4 ? 0 : NI, (hipStream_t)stream);
     }

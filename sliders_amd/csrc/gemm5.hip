@@ -364,9 +364,8 @@ static int g5_group_m(int tiles_m, int tiles_n) {
     return best;
 }
 
-// called by slh_gemm (gemm.hip) for tile codes whose bits 12-15 are 5; 1 where slh_gemm5 can run the descriptor (the planner asks)
-extern "C" int slh_gemm5_ok(const slh_gemm_desc* d) {
-    if (!d || !d->a0 || !d->w || !d->c) return 0;
+// the 64 x 160 tile's part of slh_gemm_tile_ok (gemm.hip: tile codes whose bits 12-15 are 5; split-K is refused there)
+bool gemm5_tile_ok(const slh_gemm_desc* d) {
     if (d->mode != 0 || d->a1 || d->ca1 || d->w_layout != 1) return 0;
     if (d->M <= 0 || d->M % 64 || d->N <= 0 || d->N % 160 || d->K < 64 || d->K % 64 || d->ca0 != d->K) return 0;
     if (d->lora_t || d->rowbias || d->geglu || d->vt_out || d->xa_k || d->geglu_pre) return 0;
@@ -391,11 +390,8 @@ extern "C" int slh_gemm5_ok(const slh_gemm_desc* d) {
     return 1;
 }
 
+// slh_gemm (gemm.hip) has checked d with slh_gemm_tile_ok
 int slh_gemm5_launch(const slh_gemm_desc* d, slh_stream_t stream) {
-    SLH_CHECK(slh_gemm5_ok(d),
-              "slh_gemm: the 64 x 160 tile (0x5xxx) runs dense single-source products with packed weights, M %% 64 == 0, N %% 160 == 0, "
-              "bias / residual / ln_out / ln_in / one fused rank-4 adapter only (M=%d N=%d K=%d)", d ? d->M : 0, d ? d->N : 0, d ? d->K : 0);
-    SLH_CHECK(((d->tile >> 16) & 15) <= 1, "slh_gemm: the 64 x 160 tile has no split-K");
     G5Args a;
     a.a = (const __bf16*)d->a0; a.w = (const __bf16*)d->w; a.bias = (const __bf16*)d->bias; a.residual = (const __bf16*)d->residual;
     a.c = (__bf16*)d->c; a.ln_out = d->ln_out;

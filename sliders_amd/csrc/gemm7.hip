@@ -829,9 +829,8 @@ static bool g7_shape(int tile, int& xb, int& wb, int& s) {
            (xb == 8 && wb == 10 && s == 4);      // 0x748a: 256 x 320 on eight compute waves
 }
 
-// called by slh_gemm (gemm.hip) for tile codes whose bits 12-15 are 7; 1 where the tile named by d->tile can run the descriptor
-extern "C" int slh_gemm7_ok(const slh_gemm_desc* d) {
-    if (!d || !d->a0 || !d->w || !d->c) return 0;
+// the four-wave tiles' part of slh_gemm_tile_ok (gemm.hip: tile codes whose bits 12-15 are 7): 1 where the tile named by d->tile can run d
+bool gemm7_tile_ok(const slh_gemm_desc* d) {
     int xb, wb, s;
     if (((d->tile >> 12) & 15) != 7 || (d->tile >> 16) || !g7_shape(d->tile, xb, wb, s)) return 0;
     const int bm = 32 * xb, bn = 32 * wb;
@@ -871,15 +870,8 @@ extern "C" int slh_gemm7_ok(const slh_gemm_desc* d) {
     return 1;
 }
 
+// slh_gemm (gemm.hip) has checked d with slh_gemm_tile_ok
 int slh_gemm7_launch(const slh_gemm_desc* d, slh_stream_t stream) {
-    SLH_CHECK(slh_gemm7_ok(d),
-              "slh_gemm: the tiles of gemm7.hip (0x7<S><XB><WB>: 0x7648 = 128 x 256, 0x7645 = 128 x 160, 0x748a = 256 x 320) run dense "
-              "single-source products with packed weights, M %% (32 XB) == 0, N %% (32 WB) == 0, K >= 32 S; bias / residual / ln_out / ln_in / "
-              "fused adapter (128 x 256) / vt_out / geglu = 3 only (256 x 320: bias / residual / ln_in / geglu = 3) (tile 0x%x M=%d N=%d K=%d)", d ? d->tile : 0, d ? d->M : 0, d ? d->N : 0,
-              d ? d->K : 0);
-    // (not part of slh_gemm7_ok: the planner asks that before it has built the adapter's fold)
-    SLH_CHECK(!(d->ln_in && d->lora_down) || (d->ln_lora_s && d->ln_lora_c),
-              "slh_gemm: ln_in with a fused adapter needs ln_lora_s / ln_lora_c (lora_down = A . gamma)");
     int xb, wb, s;
     g7_shape(d->tile, xb, wb, s);
     G7Args a;

@@ -141,7 +141,7 @@ _ENTRY = {
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
-           "slh_graph_destroy", "slh_gemm_variant", "slh_gemm_kernel_name", "slh_gemm5_ok", "slh_gemm7_ok", "slh_attn_fwd_carries_touch", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
+           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
            "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok"] + [v[0] for v in _ENTRY.values()]
 
 
@@ -212,14 +212,38 @@ def gn_workspace(channels: int, hw: int, groups: int):
 
 
 TILE_64x160 = 0x5425      # the 64 x 160 tile of csrc/gemm5.hip (bits 12-15 = 5: family; 4 ring slots; 2 x 5 blocks of 16 x 16 per wave)
+TILE_128x256 = 0x7648     # four-wave tiles of csrc/gemm7.hip (bits 12-15 = 7; ring slots | X blocks | W blocks of 16 rows per wave)
+TILE_128x160 = 0x7645
+TILE_256x320 = 0x748A     # eight compute waves (gemm7w_kernel): GEGLU.proj as one round of 256 workgroups
+
+
+def gemm_tile_ok(desc) -> bool:
+    """slh_gemm_tile_ok: the tile named by desc.tile (0: the library's heuristic) can run this descriptor - every check of slh_gemm
+    but the split-K workspace and ln_lora_s / ln_lora_c, which a caller provisions after choosing the tile"""
+    lib = load()
+    lib.slh_gemm_tile_ok.argtypes = [C.POINTER(GemmDesc)]
+    lib.slh_gemm_tile_ok.restype = c_i32
+    return bool(lib.slh_gemm_tile_ok(C.byref(desc)))
 
 
 def gemm5_ok(desc) -> bool:
-    """slh_gemm5_ok: the 64 x 160 tile can run this descriptor (dense, packed weights, M % 64 == 0, N % 160 == 0, bias / residual / ln_out)"""
+    """The 64 x 160 tile can run this descriptor: slh_gemm_tile_ok for desc.tile, or for TILE_64x160 where desc.tile is of another family"""
+    d = GemmDesc.from_buffer_copy(desc)
+    d.tile = desc.tile if (desc.tile >> 12) & 15 == 5 else TILE_64x160
+    return gemm_tile_ok(d)
+
+
+def gemm7_ok(desc) -> bool:
+    """The tile of csrc/gemm7.hip named by desc.tile (0x7648 / 0x7645 / 0x748a) can run this descriptor (slh_gemm_tile_ok)"""
+    return (desc.tile >> 12) & 15 == 7 and gemm_tile_ok(desc)
+
+
+def gemm_ln_chunk_cols(desc) -> int:
+    """slh_gemm_ln_chunk_cols: width of the LayerNorm chunks desc's tile writes to desc.ln_out (80 or 64), 0 where it cannot"""
     lib = load()
-    lib.slh_gemm5_ok.argtypes = [C.POINTER(GemmDesc)]
-    lib.slh_gemm5_ok.restype = c_i32
-    return bool(lib.slh_gemm5_ok(C.byref(desc)))
+    lib.slh_gemm_ln_chunk_cols.argtypes = [C.POINTER(GemmDesc)]
+    lib.slh_gemm_ln_chunk_cols.restype = c_i32
+    return lib.slh_gemm_ln_chunk_cols(C.byref(desc))
 
 
 def gn_fused_ok(channels: int, hw: int, groups: int) -> int:
@@ -274,19 +298,6 @@ def wgrad_single_blocks(desc) -> int:
     return nb
 
 
-TILE_128x256 = 0x7648     # four-wave tiles of csrc/gemm7.hip (bits 12-15 = 7; ring slots | X blocks | W blocks of 16 rows per wave)
-TILE_128x160 = 0x7645
-TILE_256x320 = 0x748A     # eight compute waves (gemm7w_kernel): GEGLU.proj as one round of 256 workgroups
-
-
-def gemm7_ok(desc) -> bool:
-    """slh_gemm7_ok: the tile of csrc/gemm7.hip named by desc.tile (0x7648 / 0x7645 / 0x748a) can run this descriptor"""
-    lib = load()
-    lib.slh_gemm7_ok.argtypes = [C.POINTER(GemmDesc)]
-    lib.slh_gemm7_ok.restype = c_i32
-    return bool(lib.slh_gemm7_ok(C.byref(desc)))
-
-
 def attn_carries_touch(desc) -> bool:
     """slh_attn_fwd_carries_touch: this attention launch runs the key-split form, whose idle workgroup slots can stream weights for a
     later product (slh_attn_desc.pf_*)"""
@@ -294,14 +305,6 @@ def attn_carries_touch(desc) -> bool:
     lib.slh_attn_fwd_carries_touch.argtypes = [C.POINTER(AttnDesc)]
     lib.slh_attn_fwd_carries_touch.restype = c_i32
     return bool(lib.slh_attn_fwd_carries_touch(C.byref(desc)))
-
-
-def gemm_variant(desc) -> int:
-    """(MI<<8)|(NI<<4)|mode of the gemm_kernel<MI,NI,mode> instantiation slh_gemm launches for desc."""
-    lib = load()
-    lib.slh_gemm_variant.argtypes = [C.POINTER(GemmDesc)]
-    lib.slh_gemm_variant.restype = c_i32
-    return lib.slh_gemm_variant(C.byref(desc))
 
 
 def gemm_kernel_name(desc) -> str:

@@ -24,7 +24,7 @@ from . import lib
 from .arena import Arena, Buf
 from .config import UNetConfig
 from .lora_store import LoraEntry, LoraStore
-from .tuning import settle_tile, tuned_tile
+from .tuning import TILE_RING, choose_tile, splitk_slabs, splitk_tuning, tile_fields
 from .weights import WeightStore
 
 
@@ -65,40 +65,6 @@ class Act:
 
 Src = Union[Act, Tuple[Act, Act]]
 
-SPLITK_MAX_MN = 6 << 20          # output elements up to which split-K is considered (one 24 MB fp32 slab per slice at most)
-SPLITK_MIN_K = int(os.environ.get("SLIDERS_SPLITK_MIN_K", "2048"))
-
-
-def splitk_candidate(d) -> bool:
-    """Few output tiles and a long reduction (the 1280-channel convolutions at 8x8 / 16x16 of SD-1.x and of SDXL at
-    512x512: 10-40 tiles for 256 CUs, 29 MB of weights each): such a product gets a zeroed fp32 workspace so that
-    slh_gemm may cut K into slices (tile bits 16-19, chosen by the tuner or by default_splitk below)."""
-    return d.M * d.N <= SPLITK_MAX_MN and d.K >= SPLITK_MIN_K and not d.geglu and d.N % 4 == 0
-
-
-def splitk_wanted(d) -> bool:
-    """Provision the workspace when the tile that will run splits K: the tuned tile says so, or there is no tuned tile and
-    the default would; in tuning mode (SLIDERS_NO_TUNING: scripts/tune_insitu.py tries split-K tiles on every candidate)
-    for every candidate."""
-    if not splitk_candidate(d):
-        return False
-    if os.environ.get("SLIDERS_NO_TUNING") or os.environ.get("SLIDERS_SPLITK_ALL"):
-        return True
-    return ((d.tile >> 16) & 15) > 1 if d.tile else bool(default_splitk(d))
-
-
-def default_splitk(d) -> int:
-    """Untuned shape: slices so that tiles x slices is about one workgroup per CU, at least 8 K tiles per slice."""
-    tiles = ((d.M + 127) // 128) * ((d.N + 63) // 64)
-    if tiles >= 128 or d.K < 4096:
-        return 0
-    s = min(8, max(1, 256 // tiles), d.K // 512)
-    return 0 if s < 2 else (s << 16) | 0x412
-
-
-SPLITK_TUNING_SLABS = 8          # slabs provisioned per candidate when the in-situ tuner may try any split factor
-
-
 SPLITK_TICKETS = 4096            # 64-bit arrival tickets per plan (one per output tile of the largest split-K product)
 
 
@@ -112,17 +78,12 @@ def _plan_tickets(plan, n: int) -> int:
 
 
 def provision_splitk(plan, d, name: str):
-    """Give a product that will (or, in tuning mode, may) run split-K its slab workspace: one fp32 slab (M, N rounded up to whole
+    """Give a product whose tile splits K (or, in tuning mode, may) its slab workspace: one fp32 slab (M, N rounded up to whole
     tiles) per K slice
     (each slice writes its own, the last slice of a tile to arrive adds them in slice order inside the launch - bit-reproducible) and, with a
-    fused adapter, two [M][ld_t] slabs per slice for T.  Fixes d.tile for untuned shapes."""
-    if not splitk_wanted(d):
-        return
-    if not d.tile and d.M * d.N <= (1 << 20):      # the untuned default only for the small products it was measured on
-        d.tile = default_splitk(d)
-    tuning = os.environ.get("SLIDERS_NO_TUNING") or os.environ.get("SLIDERS_SPLITK_ALL")
-    slabs = max(SPLITK_TUNING_SLABS if tuning else 0, (d.tile >> 16) & 15)
-    if slabs < 2:
+    fused adapter, two [M][ld_t] slabs per slice for T."""
+    slabs = splitk_slabs(d)
+    if not slabs:
         return
     d.splitk_slabs = slabs
     d.splitk_c32 = plan.arena.alloc((slabs, (d.M + 255) // 256 * 256, (d.N + 127) // 128 * 128), torch.float32, name + ".splitk").ptr
@@ -130,7 +91,7 @@ def provision_splitk(plan, d, name: str):
     if d.lora_down:
         # one pair of T slabs per slice and per COLUMN TILE (each column tile's last slice reduces its own copy); sized for
         # the narrowest tile (64 columns) unless the tile is fixed
-        ni = (d.tile & 15) if (d.tile and not tuning) else 1
+        ni = tile_fields(d.tile)[4] if (d.tile and not splitk_tuning()) else 1
         tiles_n = (d.N + 64 * ni - 1) // (64 * ni)
         d.splitk_t32 = plan.arena.alloc((tiles_n * 2 * slabs, d.M, d.ld_t), torch.float32, name + ".splitk_T").ptr
 
@@ -155,7 +116,7 @@ def attach_weight_touch(prog: "lib.Program") -> "lib.Program":
     def carrier(o, d):
         if o == lib.OP_ATTN_FWD:          # round 6: the key-split self-attention of the 32 x 32 level (its workgroups leave a slot per CU)
             return os.environ.get("SLIDERS_NO_ATTN_TOUCH") is None and lib.attn_carries_touch(d)
-        if o != lib.OP_GEMM or d.mode != 0 or (d.tile & 0xFFFFFF) != 0x4412:
+        if o != lib.OP_GEMM or d.mode != 0 or d.tile != TILE_RING:
             return False
         return ((d.M + 127) // 128) * ((d.N + 127) // 128) <= 192
     used = set()
@@ -362,77 +323,53 @@ class UNetPlan:
                          w_layout=1 if (w_ptr is None and self.w.packed) else 0)
         if conv is not None:
             self._conv_fields(d, x0, conv, Ho, Wo)
-        # the tuned table keys the two sides of a folded LayerNorm apart (",ni" consumer, ",no" producer: the producer needs a
-        # 128-column tile): the descriptor carries the fold BEFORE the lookup (the producer's pointer is a placeholder until the
-        # tile that will run is known to support it)
-        train_fold = self.train and os.environ.get("SLIDERS_TRAIN_NO_LN_FOLD") is None
-        want_ln_out = bool(ln_stats and (not self.train or train_fold) and not geglu and N % 64 == 0)
         if ln_fold is not None:
+            if grp is not None and (not fused or ln_norm is None):
+                return None                       # (the adapter's fold needs the fused adapter and the LayerNorm's parameters)
             d.w, d.bias = self.w.ptr(wname + ".lnw" + sfx), 0
             d.ln_in, d.ln_in_chunks, d.ln_eps = ln_fold.ln[0].ptr, ln_fold.ln[1], 1e-5
             d.ln_s, d.ln_b = self.w.ptr(wname + ".lns" + sfx), self.w.ptr(wname + ".lnb" + sfx)
-        if want_ln_out:
-            d.ln_out = 8
-        d.tile = tuned_tile(d)
-        d.ln_out = 0
-        if not d.tile and M <= 192 and N >= 4096:
-            d.tile = 0x12        # few rows, very wide: 64-row tiles waste the least of the short M
-        if xattn is not None and (d.tile == 0x4412 or os.environ.get("SLIDERS_XATTN_ALL")):
-            # (where the table prefers another tile for the query projection - the 640-channel level - the two launches stay)
-            d.tile = 0x4412
-            k = xattn["k"]
-            d.xa_k, d.xa_vt, d.xa_tk, d.xa_tq = k.ptr, xattn["vt_ptr"], xattn["Tk"], xattn["Tq"]
-            d.xa_ldk, d.xa_ldvt, d.xa_vt_heads, d.xa_scale = k.ld, xattn["ldvt"], xattn["vt_heads"], xattn["scale"]
-            self.xattn_done = True
-        if ln_fold is not None:
-            if ((d.tile >> 16) & 15) > 1 or (not d.tile and splitk_wanted(d)):
-                return None
-            if grp is not None:
-                fam = (d.tile >> 12) & 15
-                fits = (fam == 8 and (d.tile >> 4) & 15 == 1 and (d.tile & 15) <= 4) or (fam == 7 and (d.tile & 15) == 8)
-                if not fused or ln_norm is None or not fits:
-                    return None                   # (the 128-register tiles of gemm.hip have no room for the second fold)
-                R = 4 * len(grp)
-                a2 = self.arena.alloc((R, K), torch.bfloat16, name + ".lnA")
-                sc = self.f32((2, 16), name + ".lnA_sc")
-                d.lora_down, d.ln_lora_s, d.ln_lora_c = a2.ptr, sc.ptr, sc.ptr + 64
-                self.lnfold_items.append((self.lora.down_ptr(grp[0]), self.w.ptr(ln_norm + ".g"), self.w.ptr(ln_norm + ".b"),
-                                          a2.ptr, sc.ptr, sc.ptr + 64, R | (K << 32)))
             if ln_mr is not None:
                 d.ln_mr_out = ln_mr.ptr
-        else:
-            provision_splitk(self, d, name)
         if geglu_pre is not None:
             assert geglu and geglu_pre.C == N
             d.geglu_pre, d.ld_pre = geglu_pre.ptr, geglu_pre.ld
-        if want_ln_out and (d.tile >> 12) & 15 == 5:
-            st = self.f32((N // 80, M, 2), name + ".ln_chunks")      # the 64 x 160 tile leaves 80-column chunks (a wave's columns)
-            d.ln_out = st.ptr
-            out.ln = (st, N // 80)
-        elif want_ln_out and (d.tile >> 12) & 15 == 7:
-            cw = 80 if (d.tile & 15) % 5 == 0 else 64                # the four-wave tiles: 80-column chunks where a wave owns 80 / 160 columns
-            st = self.f32((N // cw, M, 2), name + ".ln_chunks")
-            d.ln_out = st.ptr
-            out.ln = (st, N // cw)
-        elif want_ln_out and not d.splitk_c32 and (lib.gemm_variant(d) >> 4) & 15 == 2 and \
-                ((d.tile >> 12) & 15 != 8 or (d.tile >> 4) & 15 == 4):
-            st = self.f32((N // 64, M, 2), name + ".ln_chunks")
-            d.ln_out = st.ptr
-            out.ln = (st, N // 64)
-        self.last_vt = None
+        train_fold = self.train and os.environ.get("SLIDERS_TRAIN_NO_LN_FOLD") is None
+        want_ln_out = bool(ln_stats and (not self.train or train_fold) and not geglu and N % 64 == 0)
+        vt = None
         if vt_heads and not geglu and conv is None and os.environ.get("SLIDERS_NO_FUSED_VT") is None and \
                 (not self.train or os.environ.get("SLIDERS_TRAIN_NO_FUSED_VT") is None):
             Cq = N // 3
             Dh, Tk = Cq // vt_heads, Ho * Wo
-            pp_ok = (d.tile >> 12) & 15 != 8 or (d.tile & 0xFF) in (0x42, 0x14)     # ping-pong tiles: 256 x 256 and 128 x 256 only
-            if (d.tile >> 12) & 15 == 7:                                            # four-wave tiles: whole tiles per sample, V block on a wave boundary
-                pp_ok = Tk % 128 == 0 and (2 * Cq) % (16 * (d.tile & 15)) == 0
-            if Dh % 64 == 0 and (2 * Cq) % 128 == 0 and Tk % 64 == 0 and not (d.tile >> 16) & 15 and pp_ok:
-                vt = self.arena.alloc((B, vt_heads, Dh, Tk), torch.bfloat16, name + ".vt")
-                d.vt_out, d.vt_col0, d.vt_D, d.vt_heads, d.vt_tokens, d.vt_ld = vt.ptr, 2 * Cq, Dh, vt_heads, Tk, Tk
-                d.vt_also_c = 1 if self.train else 0      # the backward reads V row-major
-                self.last_vt = (vt.ptr, 0)
-        settle_tile(d)
+            if Dh % 64 == 0 and (2 * Cq) % 128 == 0 and Tk % 64 == 0:
+                # (training passes keep V row-major too: the backward reads it so)
+                vt = dict(vt_col0=2 * Cq, vt_D=Dh, vt_heads=vt_heads, vt_tokens=Tk, vt_ld=Tk, vt_also_c=1 if self.train else 0)
+        xa = None
+        if xattn is not None:
+            k = xattn["k"]
+            xa = dict(xa_k=k.ptr, xa_vt=xattn["vt_ptr"], xa_tk=xattn["Tk"], xa_tq=xattn["Tq"], xa_ldk=k.ld, xa_ldvt=xattn["ldvt"],
+                      xa_vt_heads=xattn["vt_heads"], xa_scale=xattn["scale"])
+        ln_cols = choose_tile(d, ln_out=want_ln_out, vt=vt, xa=xa)
+        if ln_cols is None:
+            return None
+        self.xattn_done = bool(d.xa_k)
+        if ln_fold is not None and grp is not None:
+            R = 4 * len(grp)
+            a2 = self.arena.alloc((R, K), torch.bfloat16, name + ".lnA")
+            sc = self.f32((2, 16), name + ".lnA_sc")
+            d.lora_down, d.ln_lora_s, d.ln_lora_c = a2.ptr, sc.ptr, sc.ptr + 64
+            self.lnfold_items.append((self.lora.down_ptr(grp[0]), self.w.ptr(ln_norm + ".g"), self.w.ptr(ln_norm + ".b"),
+                                      a2.ptr, sc.ptr, sc.ptr + 64, R | (K << 32)))
+        provision_splitk(self, d, name)
+        if ln_cols:
+            st = self.f32((N // ln_cols, M, 2), name + ".ln_chunks")
+            d.ln_out = st.ptr
+            out.ln = (st, N // ln_cols)
+        self.last_vt = None
+        if d.vt_out:
+            vtb = self.arena.alloc((B, vt_heads, d.vt_D, d.vt_tokens), torch.bfloat16, name + ".vt")
+            d.vt_out = vtb.ptr
+            self.last_vt = (vtb.ptr, 0)
         self.prog.add(lib.OP_GEMM, d, name)
         if self.train:
             self.tape.append(dict(op="gemm", x=tape_x if tape_x is not None else x,
@@ -1016,8 +953,8 @@ class BackwardPlan:
             d.qt, d.dot, d.ldqt, d.dk, d.dv, d.lddk, d.lddv = qt.ptr, dot.ptr, ldqt, gk.ptr, gv.ptr, gk.ld, gv.ld
         self.prog.add(lib.OP_ATTN_BWD, d, "bwd." + rec["name"])
 
-    def _splitk(self, d, name):
-        d.tile = tuned_tile(d)
+    def _tile(self, d, name, vt=None):
+        choose_tile(d, vt=vt, backward=True)
         provision_splitk(self, d, name)
 
     def _wgrad(self, d, name: str, defer: bool):
@@ -1125,10 +1062,9 @@ class BackwardPlan:
                 assert not pacc
                 ps = self._sl(pre)
                 d = lib.GemmDesc(a0=gy.ptr, w=wT, c=gp.ptr, lda0=gy.ld, ca0=N, mode=0, stride=1, ldw=N, M=Ms, N=cin, K=N,
-                                 ldc=gp.ld, rows_per_sample=Ho * Wo, w_layout=1 if self.w.packed else 0)
-                self._splitk(d, name)
-                d.geglu, d.geglu_pre, d.ld_pre = 2, ps.ptr, ps.ld
-                settle_tile(d)
+                                 ldc=gp.ld, rows_per_sample=Ho * Wo, geglu=2, geglu_pre=ps.ptr, ld_pre=ps.ld,
+                                 w_layout=1 if self.w.packed else 0)
+                self._tile(d, name)
                 self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
                 return
             if x1 is None:
@@ -1149,17 +1085,18 @@ class BackwardPlan:
                     d.lora_down, d.lora_t_out = base + 2 * up_t_off, U.ptr
                 else:
                     d.lora_t = U.ptr
-            self._splitk(d, name)
             want = self._wants_dot.get(x0.buf.ptr) if (x1 is None and not tacc and tgt.ptr == gx.ptr) else None
+            vt = None
             if want is not None:
                 heads, Tq = want
                 Dh = cin // heads
                 if Dh % 64 == 0 and Tq % 64 == 0 and Ms == self.nb * Tq and cin == x0.C and tgt.ld % 8 == 0:
-                    dot = self.arena.alloc((self.nb, heads, Dh, Tq), torch.bfloat16, name + ".dot")
-                    d.vt_out, d.vt_col0, d.vt_D, d.vt_heads, d.vt_tokens, d.vt_ld = dot.ptr, 0, Dh, heads, Tq, Tq
-                    d.vt_also_c = 1
-                    self._dot_made[x0.buf.ptr] = (dot, Tq)
-            settle_tile(d)
+                    vt = dict(vt_col0=0, vt_D=Dh, vt_heads=heads, vt_tokens=Tq, vt_ld=Tq, vt_also_c=1)
+            self._tile(d, name, vt)
+            if d.vt_out:
+                dot = self.arena.alloc((self.nb, heads, Dh, Tq), torch.bfloat16, name + ".dot")
+                d.vt_out = dot.ptr
+                self._dot_made[x0.buf.ptr] = (dot, Tq)
             self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
             for dA, nm in dA_after:
                 self._wgrad(dA, nm, defer=True)
@@ -1182,8 +1119,7 @@ class BackwardPlan:
                              batch=self.nb, hs=Ho, ws=Wo, src_xform=2 if stride == 2 else 0, stride=1, ho=HL, wo=WL,
                              ldw=9 * N, M=self.nb * HL * WL, N=cin, K=9 * N, ld_res=tgt.ld, ldc=tgt.ld,
                              rows_per_sample=HL * WL, w_layout=1 if self.w.packed else 0)
-            self._splitk(d, name)
-            settle_tile(d)
+            self._tile(d, name)
             self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
             if grp is not None:
                 d2 = lib.LoraCdgradDesc(u=U.ptr, a_down=self.lora.down_ptr(grp[0]), scale=self.scale_ptr, gx=tgt.ptr,

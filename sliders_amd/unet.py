@@ -93,11 +93,13 @@ class UNetEngine:
     def _virtual_size(self, B, H, W, mode) -> int:
         va = Arena(1 << 50, None, "virtual")
         vz = Arena(1 << 40, None, "virtualz")
+        # (placeholder pointers where the real plan has some: slh_gemm_tile_ok refuses an adapter without its scale, and the dry run
+        # must choose the tiles - and split-K workspaces - the real plan will)
         p = UNetPlan(self.cfg, _VirtualWeights(self.weights), va, vz, B, H, W, self.ctx_len,
-                     _VirtualLora(self.lora) if mode != "off" else None, mode, 0)
+                     _VirtualLora(self.lora) if mode != "off" else None, mode, 0x4000)
         if mode == "train":
             b0, nb = self._grad_samples(B)
-            BackwardPlan(p, b0, nb, 0)
+            BackwardPlan(p, b0, nb, 0x4000)
         return va.high_water
 
     def _grad_samples(self, B: int):

@@ -46,7 +46,7 @@ def test_prompt_pair_loss_formula():
     assert torch.allclose(got, ((t - (n - 2.0 * (p - u))) ** 2).mean())
 
 
-def test_c_abi_exports_every_declared_symbol():
+def test_c_abi_exports_exactly_the_declared_symbols():
     """libsliders_hip.so loads without a GPU and exports exactly the entry points include/sliders_hip.h declares."""
     hdr = open(os.path.join(ROOT, "include", "sliders_hip.h")).read()
     declared = set(re.findall(r"^(?:int|const char\*)\s+(slh_\w+)\s*\(", hdr, flags=re.M))
@@ -54,7 +54,7 @@ def test_c_abi_exports_every_declared_symbol():
     l = lib.load()
     for sym in sorted(declared):
         assert hasattr(l, sym), f"{sym} declared in sliders_hip.h but not exported"
-    assert declared == set(lib.EXPORTS) | {"slh_gemm_variant"}
+    assert declared == set(lib.EXPORTS)
     assert l.slh_version() >= 1
     # descriptor sizes were cross-checked inside lib.load(); a bad descriptor is rejected with a message
     d = lib.GemmDesc()
@@ -177,9 +177,9 @@ def test_tile_64x160_entries_and_fallback():
 @pytest.mark.parametrize("nb", [1, 2])
 def test_every_recorded_tile_can_run_its_launch(train_method, nb):
     """Every GEMM a plan records - no-grad, training forward AND backward, every train_method of lora.py:126-147, one or two samples
-    carrying a gradient (prompt batch_size 1 / 2) - names a tile the library accepts for that launch.  The table lookup happens before
-    the planner attaches V^T / dO^T stores and the GEGLU backward, so a 64 x 160 entry could land on a launch that tile has no epilogue
-    for (xattn at nb = 2 recorded 70 attn1.out dgrads on 0x5425 with vt_out; slh_gemm5_launch refuses them)."""
+    carrying a gradient (prompt batch_size 1 / 2) - names a tile the library accepts for that launch, as recorded: slh_gemm's whole
+    check, workspaces included (a table entry for the 64 x 160 tile once landed on 70 attn1.out dgrads at nb = 2 that
+    carried a dO^T store, which that tile has no epilogue for)."""
     from sliders_amd.tuning import tile_ok
     cfg = CONFIGS["sdxl"]()
     store = LoraStore(cfg, train_method=train_method, init="none")
@@ -200,7 +200,45 @@ def test_every_recorded_tile_can_run_its_launch(train_method, nb):
                     n5 += 1
                     assert lib.gemm5_ok(d), f"{nm}: tile {d.tile:#x} cannot run this launch"
                 assert not d.tile or tile_ok(d, d.tile), f"{nm}: tile {d.tile:#x}"
+                try:            # slh_gemm's whole check, workspaces included, on every tile family
+                    lib.gemm_kernel_name(d)
+                except lib.SlidersHipError as e:
+                    raise AssertionError(f"{nm}: tile {d.tile:#x} cannot run this launch") from e
     assert n5 > 0
+
+
+def test_geglu_backward_is_refused_on_the_narrow_ping_pong_tiles():
+    """geglu = 2 (the GEGLU backward in the epilogue) is compiled out of the 128 x 64*NI ping-pong tiles: the library refuses the launch
+    instead of running it without the epilogue - the query and the dispatch alike."""
+    d = lib.GemmDesc(a0=0x1000, w=0x2000, c=0x3000, lda0=1280, ca0=1280, mode=0, stride=1, ldw=0, M=1024, N=5120, K=1280, ldc=10240,
+                     rows_per_sample=1024, w_layout=1, geglu=2, geglu_pre=0x4000, ld_pre=10240)
+    for tile in (0x4412, 0x4011, 0x8042):
+        d.tile = tile
+        assert lib.gemm_tile_ok(d) and lib.gemm_kernel_name(d), hex(tile)
+    for tile in (0x8013, 0x8014, 0x8015):
+        d.tile = tile
+        assert not lib.gemm_tile_ok(d), hex(tile)
+        with pytest.raises(lib.SlidersHipError, match="geglu = 2"):
+            lib.gemm_kernel_name(d)
+
+
+def test_tile_and_its_extras_are_chosen_together(monkeypatch):
+    """A table entry for the 64 x 160 tile on a product that wants both LayerNorm chunk statistics (ln_stats) and the V^T store
+    (vt_heads): the tile is settled before anything is sized from it, so the recorded launch is one the library runs and its chunk
+    buffer has the chunk count of the tile that runs."""
+    from sliders_amd import tuning
+    cfg = CONFIGS["tiny_sdxl"]()
+    p = UNetPlan(cfg, _FakeWeights(cfg), Arena(1 << 50, None), Arena(1 << 40, None), 1, 16, 16, 77, None, "off", 0x10)
+    N, K = 1920, 640
+    x = p.act(1, 32, 32, K, "x")
+    monkeypatch.setitem(tuning.table(), f"{x.M},{N},{K},m0,s1,x0,g0,l0,no", 0x5425)
+    out = p.gemm(x, "probe", N, "probe", bias=False, vt_heads=10, ln_stats=True)
+    o, d = p.prog.ops[-1]
+    assert o == lib.OP_GEMM and d.tile == 0x5425
+    lib.gemm_kernel_name(d)
+    assert out.ln is not None and d.ln_out == out.ln[0].ptr
+    assert out.ln[1] == N // lib.gemm_ln_chunk_cols(d) == N // 80
+    assert out.ln[0].shape == (N // 80, x.M, 2)
 
 
 @pytest.mark.parametrize("name,hw", [("sdxl", 128), ("sd2", 64), ("sd1", 64)])
