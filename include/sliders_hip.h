@@ -56,7 +56,10 @@ typedef struct slh_gemm_desc {
     const void* residual;    /* [M][ld_res] bf16 or NULL (may alias c) */
     void* c;                 /* [M][ldc] bf16 (N/2 columns when geglu) */
     const void* lora_down;   /* [rank][K] bf16 or NULL: FUSED down-projection, T = A.lora_down^T is computed inside
-                                the same kernel (rank = 4*lora_groups <= 12); excludes lora_t */
+                                the same kernel (rank = 4*lora_groups <= 12); excludes lora_t.  In the forward form (lora_up [N][4])
+                                lora_scale * T is ROUNDED TO bf16 ahead of the up-projection, which runs as one more MFMA (the
+                                reference's lora_down output is a bf16 tensor too); lora_t_out receives the unrounded fp32 T.  The
+                                backward-data form (lora_up_rmajor) and an external lora_t keep T in fp32 */
     float* lora_t_out;       /* optional [M][ld_t] fp32: the fused T, kept for the backward pass */
     int32_t lda0, lda1, ca0, ca1;
     int32_t mode;            /* 0 dense, 1 conv3x3 */
@@ -74,7 +77,11 @@ typedef struct slh_gemm_desc {
                                 [M][N] leaves as d(proj) [M][2N] in proj's blocked column order, computed with the forward's
                                 pre-activation geglu_pre (slh_elementwise GEGLU_BWD fused; bare product only).
                                 3: as 1 with W rows pre-permuted in 32-row blocks [16 a | 16 g] (any tile; no geglu_pre) */
-    int32_t tile;            /* 0 auto; else (S<<16)|(WM<<12)|(stages<<8)|(MI<<4)|NI, MI,NI in {1,2}, WM in {0|2, 4}: WM*2 waves per
+    int32_t tile;            /* bits 0-15 all zero: auto (the heuristic picks one of the ring codes below; S may still be set).  Any other
+                                code must be complete: every nibble of bits 0-15 is read by the dispatch or must be zero, and a code
+                                that names no kernel is refused (unknown WM or stages, MI = 0, stages bits on a WM = 8 code, a
+                                0x5xxx / 0x7xxx code other than those listed below).
+                                Else (S<<16)|(WM<<12)|(stages<<8)|(MI<<4)|NI, MI,NI in {1,2}, WM in {0|2, 4}: WM*2 waves per
                                 workgroup, block tile (32*MI*WM) x (64*NI); stages 0|2: double buffer, 3|4: deep LDS ring;
                                 S: split-K factor (0|1 none), needs splitk_c32.
                                 WM = 8: ping-pong K loops, one 8-wave workgroup per CU (csrc/gemm8p.hip): 0x8042 = 256 x 256
@@ -106,7 +113,9 @@ typedef struct slh_gemm_desc {
                                 vt_out[((b*vt_heads + h)*Dp + d)*vt_ld + t] = C[b*vt_tokens + t][vt_col0 + h*vt_D + d],
                                 Dp = 64*ceil(vt_D/64) - exactly what slh_transpose_heads would produce from c, without
                                 the extra launch and the round trip of V through HBM.  Needs vt_D % 64 == 0 (no padded
-                                rows), vt_col0 % 128 == 0, vt_tokens % 8 == 0, M % 8 == 0; not with geglu */
+                                rows), vt_col0 % 128 == 0, vt_tokens % 8 == 0, M % 8 == 0; not with geglu; vt_ld == vt_tokens
+                                (slh_transpose_heads zero-fills padding columns up to its ldt; this epilogue writes the vt_tokens
+                                columns only, so a padded row is refused rather than left half-initialised) */
     int32_t vt_col0, vt_D, vt_heads, vt_tokens, vt_ld;
     int32_t splitk_slabs;    /* slabs splitk_c32 holds (>= the S of tile) */
     /* LayerNorm folded into the products around it (BasicTransformerBlock.norm1/2/3 of the no-grad passes: no LayerNorm
@@ -162,8 +171,8 @@ int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream);
  * every present and future tile.  Needs no device and launches nothing.  0, or the status slh_gemm would return for d.
  * (bench.py / scripts/make_pmc_traffic.py pair in-situ event times and PMC rows by this name.) */
 int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap);
-/* The 64 x 160 tile (tile code bits 12-15 = 5, e.g. 0x5425; csrc/gemm5.hip): 4 waves of 32 x 80 on the 16 x 16 x 32 MFMA, 4-slot LDS
- * ring - the M = 2048, N = 1280 products as 256 workgroups = one full round of the chip.  Dense single-source products with packed
+/* The 64 x 160 tile (tile codes 0x5425: 4-slot LDS ring, 0x5525: 5 slots - no other 0x5xxx code is accepted; csrc/gemm5.hip): 4 waves
+ * of 32 x 80 on the 16 x 16 x 32 MFMA - the M = 2048, N = 1280 products as 256 workgroups = one full round of the chip.  Dense single-source products with packed
  * weights (w_layout = 1), M % 64 == 0, N % 160 == 0; epilogue: bias, residual, ln_out - whose chunks are then 80 COLUMNS wide:
  * ln_out [N/80][M][2], and the consumer's ln_in_chunks = K / 80. */
 /* The tiles of csrc/gemm7.hip (tile code bits 12-15 = 7: 0x7<S><XB><WB>): 128 x 256 (0x7648) and 128 x 160 (0x7645) - four loader waves
@@ -171,7 +180,7 @@ int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap);
  * (0x748a) on eight compute waves that stage the ring themselves (GEGLU.proj as one round of 256 workgroups); ring of S half K tiles (32
  * deep).  Dense single-source products with packed weights (w_layout = 1, w 128-byte aligned), M % (32 XB) == 0, N % (32 WB) == 0,
  * K % 64 == 0, K >= 32 S.  Epilogue: bias, residual, ln_in, geglu = 3 on all three; on the 128-row tiles also ln_out (64-column chunks;
- * 80-column chunks on 0x7645), ln_mr_out, vt_out / vt_also_c (vt_col0 % (16 WB) == 0, vt_tokens % 128 == 0) and - 0x7648 only - one fused
+ * 80-column chunks on 0x7645), ln_mr_out, vt_out / vt_also_c (vt_col0 % (16 WB) == 0, vt_tokens % 128 == 0, vt_ld == vt_tokens) and - 0x7648 only - one fused
  * adapter of 1-3 column groups (forward form, every tile inside one group; with ln_in also its own fold: ln_lora_s / ln_lora_c) and
  * lora_t_out.  No split-K, row bias, external T, geglu 1 / 2, cross-attention. */
 /* 1 where the tile named by d->tile (0: the one slh_gemm's own heuristic picks) can run d's shape and features: every check of

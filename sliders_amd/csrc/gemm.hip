@@ -619,6 +619,21 @@ static int gemm_check(const slh_gemm_desc* d) {
                   "slh_gemm: geglu = 3 (16 | 16 weight blocks) needs N %% 32 == 0 and excludes adapters, residual, row bias, geglu_pre, vt_out, ln_out");
     SLH_CHECK(d->geglu >= 0 && d->geglu <= 3, "slh_gemm: geglu is 0, 1 / 3 (forward epilogue, 32 | 32 or 16 | 16 weight blocks) or 2 (backward form)");
 
+    {
+        // a tile code names a kernel or is refused: every nibble of bits 0-15 is either read by the dispatch or must be zero
+        const int fam = (d->tile >> 12) & 15, st = (d->tile >> 8) & 15, code = d->tile & 0xffff;
+        SLH_CHECK(fam == 0 || fam == 2 || fam == 4 || fam == 5 || fam == 7 || fam == 8,
+                  "slh_gemm: tile 0x%x: bits 12-15 are 0 | 2 (4 waves), 4 (8 waves), 8 (ping-pong), 5 (64 x 160) or 7 (gemm7.hip)", d->tile);
+        SLH_CHECK(code == 0 || fam == 5 || fam == 7 || ((code >> 4) & 15) != 0,
+                  "slh_gemm: tile 0x%x names no block tile (MI = 0): bits 0-15 are all zero (heuristic) or a complete tile code", d->tile);
+        if (fam == 5)
+            SLH_CHECK((d->tile & 0xfff) == 0x425 || (d->tile & 0xfff) == 0x525,
+                      "slh_gemm: the 64 x 160 tile is 0x5425 (4 ring slots) or 0x5525 (5 ring slots), not 0x%x", code);
+        if ((fam == 0 || fam == 2 || fam == 4) && code)
+            SLH_CHECK(st == 0 || st == 2 || st == 3 || st == 4,
+                      "slh_gemm: tile 0x%x: bits 8-11 (ring slots) are 0 | 2 (double buffer), 3 or 4", d->tile);
+        if (fam == 8) SLH_CHECK(st == 0, "slh_gemm: tile 0x%x: bits 8-11 of a ping-pong tile (0x8042, 0x801<NI>) must be zero", d->tile);
+    }
     if (((d->tile >> 12) & 15) == 7) {
         SLH_CHECK(gemm7_tile_ok(d),
                   "slh_gemm: the tiles of gemm7.hip (0x7<S><XB><WB>: 0x7648 = 128 x 256, 0x7645 = 128 x 160, 0x748a = 256 x 320) run dense "
@@ -653,8 +668,9 @@ static int gemm_check(const slh_gemm_desc* d) {
     if (d->vt_out) {
         SLH_CHECK(d->vt_D > 0 && d->vt_D % 64 == 0 && d->vt_col0 % 128 == 0 && d->vt_col0 < d->N && d->vt_heads > 0 &&
                       (d->N - d->vt_col0) == d->vt_heads * d->vt_D && d->vt_tokens % 8 == 0 && d->M % d->vt_tokens == 0 &&
-                      d->vt_ld % 8 == 0 && d->vt_ld >= d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
-                  "slh_gemm: vt_out constraints");
+                      d->vt_ld % 8 == 0 && d->vt_ld == d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
+                  "slh_gemm: vt_out constraints (vt_D %% 64, vt_col0 %% 128, vt_tokens %% 8, M %% vt_tokens, vt_ld == vt_tokens: the padding columns "
+                  "slh_transpose_heads zero-fills are not written here, so there must be none; 16-byte aligned; no GEGLU)");
     }
     if (d->ln_out) {
         SLH_CHECK(NI == 2 && d->N % 64 == 0 && !d->geglu && !d->vt_out,

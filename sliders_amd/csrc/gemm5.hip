@@ -368,7 +368,7 @@ static int g5_group_m(int tiles_m, int tiles_n) {
 bool gemm5_tile_ok(const slh_gemm_desc* d) {
     if (d->mode != 0 || d->a1 || d->ca1 || d->w_layout != 1) return 0;
     if (d->M <= 0 || d->M % 64 || d->N <= 0 || d->N % 160 || d->K < 64 || d->K % 64 || d->ca0 != d->K) return 0;
-    if (d->lora_t || d->rowbias || d->geglu || d->vt_out || d->xa_k || d->geglu_pre) return 0;
+    if (d->lora_t || d->rowbias || d->geglu || d->vt_out || d->vt_also_c || d->xa_k || d->geglu_pre) return 0;
     if (d->ln_in) {          // consumer side of a folded LayerNorm (as the 128-row tiles: gemm7.hip), without an adapter
         if (!d->ln_s || !d->ln_b || d->bias || d->lora_down || ((uintptr_t)d->ln_in & 7) || ((uintptr_t)d->ln_s & 15) || ((uintptr_t)d->ln_b & 15)) return 0;
         if (d->ln_in_chunks < 1 || d->ln_in_chunks > 20 || !(d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks)) return 0;

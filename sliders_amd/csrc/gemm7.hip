@@ -862,7 +862,7 @@ bool gemm7_tile_ok(const slh_gemm_desc* d) {
     if (d->vt_out) {
         if (d->geglu || d->vt_D <= 0 || d->vt_D % 64 || d->vt_col0 % (16 * wb) || d->vt_col0 >= d->N || d->vt_heads <= 0 ||
             (d->N - d->vt_col0) != d->vt_heads * d->vt_D || d->vt_tokens % bm || d->M % d->vt_tokens || d->vt_ld % 8 ||
-            d->vt_ld < d->vt_tokens || ((uintptr_t)d->vt_out & 15))
+            d->vt_ld != d->vt_tokens || ((uintptr_t)d->vt_out & 15))
             return 0;
     } else if (d->vt_also_c) {
         return 0;

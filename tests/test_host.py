@@ -942,3 +942,200 @@ def test_gemm_kernel_name_comes_from_the_library():
     d.tile, d.K = 0x5425, 100            # a descriptor slh_gemm refuses: the error, not a name
     with pytest.raises(lib.SlidersHipError):
         lib.gemm_kernel_name(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The element-wise GEMM bound of tests/util.py has teeth (and lets a correct kernel through)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _trunc_bf16(x32):
+    """fp32 -> bf16 by dropping the low 16 bits (round towards zero): the mutant the whole-tensor norm cannot see"""
+    return (x32.contiguous().view(torch.int32) & -65536).view(torch.float32).to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 328, 192), (256, 960, 1280), (154, 256, 5760)])
+def test_gemm_elementwise_bound_passes_a_standin_and_fails_four_mutants(M, N, K):
+    """Stand-in kernel: torch's fp32 CPU product + bias + residual, rounded to bf16 (nearest).  It must meet the bound
+    |got - ref| <= 2^-8 |ref| + n 2^-24 S at every element and |b| <= 0.05; each mutant - truncation instead of rounding, the last
+    64 of K missing in one 32 x 64 block, the bias missing in the last 4 columns, a stale last row - must fail at least one of the
+    two checks, and truncation must fail the rounding statistic, at every shape.  (A bound of 2^-9 |ref| + n 2^-23 S fails the
+    stand-in itself, which is why this proof stays in the suite.)"""
+    from tests.util import check_elementwise, elementwise_bound, rounding_statistic, STAT_LIMIT
+    g = torch.Generator().manual_seed(M + N + K)
+    x = torch.randn(M, K, generator=g).bfloat16()
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16()
+    bias = torch.randn(N, generator=g).bfloat16()
+    res = torch.randn(M, N, generator=g).bfloat16()
+    xd, wd, bd, rd = x.double(), w.double(), bias.double(), res.double()
+    ref = xd @ wd.t() + bd + rd
+    sabs = xd.abs() @ wd.abs().t() + bd.abs() + rd.abs()
+    bound = elementwise_bound(ref, sabs, K + 2)
+    acc32 = x.float() @ w.float().t() + bias.float() + res.float()
+    good = acc32.bfloat16()
+    worst, _, b = check_elementwise("stand-in", good, ref, bound)
+    print(f"[parity] stand-in M{M} N{N} K{K}: worst |got - ref| / bound = {worst:.3f}, b = {b:+.4f}")
+    assert worst <= 1.0 and b is not None and abs(b) <= STAT_LIMIT
+
+    def fails(name, got):
+        try:
+            check_elementwise(name, got, ref, bound)
+        except AssertionError as e:
+            print(f"[parity] mutant {name} M{M} N{N} K{K}: caught - {str(e)[:160]}")
+            return True
+        return False
+
+    trunc = _trunc_bf16(acc32)
+    assert fails("truncation", trunc)
+    bt, cnt = rounding_statistic(trunc, ref)
+    assert bt is not None and abs(bt) > STAT_LIMIT, (bt, cnt)          # the statistic alone sees it, at every K
+    m0, n0 = (M - 32) // 32 * 32, 64
+    short = acc32.clone()
+    short[m0:m0 + 32, n0:n0 + 64] -= x.float()[m0:m0 + 32, K - 64:] @ w.float()[n0:n0 + 64, K - 64:].t()
+    assert fails("dropped K tile", short.bfloat16())
+    nobias = acc32.clone()
+    nobias[:, N - 4:] -= bias.float()[N - 4:]
+    assert fails("bias quad", nobias.bfloat16())
+    stale = good.clone()
+    stale[M - 1] = good[M - 2]
+    assert fails("stale last row", stale)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The GEMM test matrix (tests/gemm_matrix.py) against the library's capability rule
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def gemm_matrix_cases():
+    from tests import gemm_matrix as gm
+    return gm, gm.enumerate_cases()
+
+
+def test_gemm_capability_matches_the_recorded_table(gemm_matrix_cases):
+    """slh_gemm_tile_ok's answers over the whole matrix equal tests/data/gemm_capability.json (python -m tests.gemm_matrix --write):
+    a change that widens or narrows the rule shows in the diff of that file."""
+    gm, (acc, _) = gemm_matrix_cases
+    rec = json.load(open(gm.DATA))
+    table = gm.capability_table(acc)
+    assert sorted(table) == sorted(rec["table"]), set(table) ^ set(rec["table"])
+    diff = {k: (table[k], rec["table"][k]) for k in table if table[k] != rec["table"][k]}
+    assert not diff, f"the rule and the recorded table disagree (library, file): {diff}"
+    assert rec["accepted"] == len(acc)
+    assert os.path.getsize(gm.DATA) < 200 * 1024
+
+
+def test_gemm_matrix_is_not_hollow(gemm_matrix_cases):
+    """Every tile code names a kernel and runs the bare recipe at the exact-multiple shape; every recipe is accepted by at least one
+    tile of each family the header (include/sliders_hip.h) says takes it - Recipe.families restates the header's text, so this is
+    the check that header and rule agree; at least 4000 cases are accepted; the matrix covers every tile code the tuning tables
+    and the hand-written kernel tests name."""
+    gm, (acc, ref) = gemm_matrix_cases
+    bare_a = {c.tile & 0xFFFF for c in acc if c.recipe.name == "bare" and c.cls == "a" and (c.tile >> 16) == 0}
+    assert set(gm.TILES) <= bare_a, [hex(t) for t in set(gm.TILES) - bare_a]
+    for c in acc:
+        if c.recipe.name == "bare" and c.cls == "a":
+            off, _ = gm.layout(c)
+            assert lib.gemm_kernel_name(gm.make_desc(c, gm._FAKE_BASE, off))
+    took = {}
+    for c in acc:
+        took.setdefault(c.recipe.name, set()).add(gm.family(c.tile))
+    miss = set()
+    for r in gm.RECIPES:
+        # (tile 0 is no family of the header: the heuristic's pick is one of the explicit tiles, and takes what that tile takes)
+        want = set(r.families) - {"auto"}
+        miss.update({(r.name, f) for f in want - took.get(r.name, set())})
+    assert not miss, f"the header promises these (recipe, family) pairs, the rule accepts no case of them: {sorted(miss)}"
+    assert len(acc) >= 4000, len(acc)
+    # split-K does not drop out where it matters: a tile that takes the bare recipe with split-K at the exact-multiple shape also takes it
+    # at the ragged shape (b) and at K >= 2560 (kbig), with S = 2 and with S = 3 - uneven slices, many K tiles per slice
+    def sk(cls, S):
+        return {c.tile & 0xFFFF for c in acc if c.recipe.name == "bare" and c.cls == cls and (c.tile >> 16) == S}
+    split_a = sk("a", 2) | sk("a", 3)
+    assert {gm.family(t) for t in split_a} == {"auto", "r2", "r4", "pp"}
+    for cls in ("b", "kbig"):
+        for S in (2, 3):
+            assert split_a <= sk(cls, S), (cls, S, sorted(hex(t) for t in split_a - sk(cls, S)))
+    # ... and every split-K case of the matrix really cuts K into at least two slices
+    for c in acc:
+        S = (c.tile >> 16) & 15
+        if S > 1:
+            nk = c.dims["K"] // 64
+            per = -(-nk // S)
+            assert -(-nk // per) >= 2, c.id
+    # tile codes named elsewhere in the repository
+    named = set()
+
+    def walk(x):
+        if isinstance(x, dict):
+            for v in x.values():
+                walk(v)
+        elif isinstance(x, list):
+            for v in x:
+                walk(v)
+        elif isinstance(x, int):
+            named.add(x & 0xFFFF)
+    for fn in os.listdir(os.path.join(ROOT, "sliders_amd", "tuning")):
+        if fn.endswith(".json"):
+            walk(json.load(open(os.path.join(ROOT, "sliders_amd", "tuning", fn))))
+    for fn in ("test_kernels_gpu.py", "test_gemm7_gpu.py"):
+        for line in open(os.path.join(ROOT, "tests", fn)):
+            if "tile" in line and "parametrize" in line:
+                named |= {int(m, 16) & 0xFFFF for m in re.findall(r"0x[0-9a-fA-F]+", line)}
+    named = {t for t in named if t and (t >> 12) in (0, 4, 5, 7, 8)}
+    missing = sorted(hex(t) for t in named - set(gm.TILES))
+    assert not missing, f"tile codes the tuning tables / kernel tests name but the matrix does not sweep: {missing}"
+
+
+def test_gemm_tile_codes_name_a_kernel_or_are_refused():
+    """Every nibble of bits 0-15 of a tile code is read by the dispatch or must be zero: 0x5xxx codes other than 0x5425 / 0x5525, unknown
+    wave codes and ring depths, ring-depth bits on a ping-pong code (0x8142, 0x8f15) and codes without a block tile (MI = 0: 0x0002,
+    0x4000 ...; only an all-zero code, with or without S, asks for the heuristic) are refused with a message; the aliases the header allows (WM 2 = 0, stages 2 = 0) name the same kernel; vt_also_c without vt_out,
+    ln_mr_out without ln_in and geglu_pre without geglu are refused by every family (the 64 x 160 tile used to take the first)."""
+    from tests import gemm_matrix as gm
+
+    def desc(tile, wl, M=256, N=320, K=256, **kw):
+        c = gm.plan_case(gm.RECIPE["bare"], 0x11, 0, wl, "a")
+        off, _ = gm.layout(c)
+        d = gm.make_desc(c, gm._FAKE_BASE, off, tile)
+        d.M, d.N, d.K, d.ca0, d.lda0, d.ldc, d.ldw, d.rows_per_sample = M, N, K, K, K, N, 0 if wl else K, M
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+    for tile, wl in ((0x5425, 1), (0x5525, 1), (0x7645, 1), (0x11, 0), (0x4412, 1), (0x8042, 0), (0x8015, 1), (0, 0), (0x20000, 0)):
+        assert lib.gemm_tile_ok(desc(tile, wl)), hex(tile)
+    for tile, wl in ((0x5000, 1), (0x5999, 1), (0x5426, 1), (0x1011, 0), (0x3011, 0), (0x6011, 0), (0x9011, 0), (0x911, 0), (0x4112, 0),
+                     (0x8142, 0), (0x8942, 0), (0x8f15, 1), (0x8415, 1), (0x0002, 0), (0x4002, 0), (0x8002, 0), (0x4000, 0), (0x2000, 0),
+                     (0x0400, 0), (0x20002, 0)):
+        d = desc(tile, wl)
+        assert not lib.gemm_tile_ok(d), hex(tile)
+        with pytest.raises(lib.SlidersHipError, match="tile"):
+            lib.gemm_kernel_name(d)
+    assert lib.gemm_kernel_name(desc(0x2011, 0)) == lib.gemm_kernel_name(desc(0x11, 0))
+    assert lib.gemm_kernel_name(desc(0x211, 0)) == lib.gemm_kernel_name(desc(0x11, 0))
+    for tile in (0x5425, 0x7645, 0x4412):
+        for kw in (dict(vt_also_c=1), dict(ln_mr_out=gm._FAKE_BASE), dict(geglu_pre=gm._FAKE_BASE, ld_pre=320)):
+            d = desc(tile, 1, **kw)
+            assert not lib.gemm_tile_ok(d), (hex(tile), kw)
+            with pytest.raises(lib.SlidersHipError, match="slh_gemm"):
+                lib.gemm_kernel_name(d)
+
+
+@pytest.mark.parametrize("name,hw,method", [("tiny_sdxl", 16, "noxattn"), ("tiny_sd1", 16, "full"), ("sdxl", 128, "noxattn"), ("sdxl", 64, "noxattn")])
+def test_every_gemm_of_the_dry_run_plans_passes_the_capability_rule(name, hw, method):
+    """Every slh_gemm descriptor of every dry-run plan (adapters off / on / training forward + backward) is one the capability rule
+    accepts, names a kernel, and - where it writes vt_out - has no padding columns: a change that narrows the rule cannot strand a
+    plan without this test saying which product."""
+    cfg = CONFIGS[name]()
+    store = LoraStore(cfg, train_method=method, init="none")
+    store.temb_tcol = torch.zeros(1, dtype=torch.int32)
+    n = 0
+    for mode in ("off", "on", "train"):
+        va, vz = Arena(1 << 50, None), Arena(1 << 40, None)
+        p = UNetPlan(cfg, _FakeWeights(cfg), va, vz, 2, hw, hw, 77, store if mode != "off" else None, mode, 0x10)
+        progs = [p.prog] + ([BackwardPlan(p, 1, 1, 0x20).prog] if mode == "train" else [])
+        for pr in progs:
+            for o, d in pr.ops:
+                if o != lib.OP_GEMM:
+                    continue
+                n += 1
+                assert lib.gemm_tile_ok(d), f"{name} {mode}: M{d.M} N{d.N} K{d.K} tile 0x{d.tile:x}: {lib.last_error()}"
+                assert lib.gemm_kernel_name(d)
+                assert not d.vt_out or d.vt_ld == d.vt_tokens
+    assert n > 100
