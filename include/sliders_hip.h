@@ -488,6 +488,31 @@ typedef struct slh_lora_lnfold_item {
 typedef struct slh_lora_lnfold_desc { const slh_lora_lnfold_item* items; int32_t n; int32_t pad_; } slh_lora_lnfold_desc;
 int slh_lora_ln_fold(const slh_lora_lnfold_desc* d, slh_stream_t stream);
 
+/* Adapters folded into the frozen weights (inference: the adapters are constants of a denoise loop, so any number of sliders of
+ * any rank become W' = W + sum_i s_i (alpha_i / r_i) B_i A_i once, and the adapter-free programs run on W').  For every item
+ *   out[n][k] = bf16( float(base[n][k]) + sum_{r < R} (c[r] * u[n - n0][r]) * d[r][k] ),   n0 <= n < n0 + rows,
+ * on a STORED matrix: base is a pristine copy in the layout of out (w_layout as slh_gemm_desc.w_layout: 1 tile-packed, rows past N
+ * are never written; 0 row-major with row stride ld).  The sum is one fp32 fma chain per element, r ascending from 0.  The host
+ * concatenates all sliders' factors along R and keeps scale * alpha / rank in c: new scales rewrite R floats.  R is any value >= 1.
+ * gamma != NULL: the item writes the LayerNorm-folded copy instead (weights.py fold_layernorm, on the merged matrix):
+ *   out[n][k] = bf16( (base + delta)[n][k] * gamma[k] ),  lns[n] = sum_k float(out[n][k]),
+ *   lnb[n] = bias[n] + sum_k float(bf16((base + delta)[n][k])) * beta[k]      (fp32, fixed order; bias may be NULL)
+ * One workgroup owns 64 rows of an item and walks K: no atomics, bit-reproducible.  items is a DEVICE array, prefix a DEVICE
+ * int32[n + 1] running sum of slh_lora_merge_blocks(item) (which validates a HOST copy of the item: -1 + slh_last_error()),
+ * total = prefix[n]; one launch covers every item.  Items of one launch must not write the same rows of the same tensor. */
+typedef struct slh_lora_merge_item {
+    const void* base; void* out;                              /* bf16 stored matrices (first element of the whole matrix) */
+    const float* u; const float* d; const float* c;           /* fp32 [rows][ldu], [R][ldd], [R] */
+    const void* gamma; const void* beta; const void* bias;    /* bf16 [K], [K], [N]; gamma NULL: plain merge */
+    float* lns; float* lnb;                                   /* fp32 [N], written at rows n0 .. n0 + rows (folded copy only) */
+    int32_t n0, rows, N, K;                                   /* K % 8 == 0 (tile-packed: % 64) */
+    int32_t R, ldu, ldd, ld;                                  /* ldu >= R; ldd >= K, % 4 == 0; ld: row-major only, >= K, % 8 == 0 */
+    int32_t w_layout, pad_;
+} slh_lora_merge_item;
+typedef struct slh_lora_merge_desc { const slh_lora_merge_item* items; const int32_t* prefix; int32_t n, total; } slh_lora_merge_desc;
+int slh_lora_merge_blocks(const slh_lora_merge_item* item);
+int slh_lora_merge(const slh_lora_merge_desc* d, slh_stream_t stream);
+
 /* Backward-data term of a 3x3 LoRA down conv (lora.py:82-87): gx[i][c] (+)= scale * sum_{tap,r} U[o][r] *
  * A[r][tap][c] for the output pixels o with o*stride + tap - 1 = i.  U fp32 [batch*ho*wo][ldu], A = lora_down
  * as stored [4][9*cin], gx bf16 pixel-major image of hl x wl. */
@@ -623,7 +648,8 @@ enum {
     SLH_OP_TEMB_LORA_BWD = 22, SLH_OP_SGEMM = 23, SLH_OP_GN32_STATS = 24, SLH_OP_GN32_APPLY = 25, SLH_OP_SOFTMAX32 = 26,
     SLH_OP_VAE_CONV_IN = 27, SLH_OP_VAE_MOMENTS = 28, SLH_OP_VAE_SAMPLE = 29, SLH_OP_VAE_POST_QUANT = 30, SLH_OP_LION = 31,
     SLH_OP_WGRAD_BATCH = 32, SLH_OP_TRANSPOSE_BATCH = 33, SLH_OP_GATHER16 = 34, SLH_OP_GN_FUSED = 35,
-    SLH_OP_LORA_LN_FOLD = 36      /* 37 was SLH_OP_PREFETCH (side-stream weight touch: measured slower, removed in round 5) */
+    SLH_OP_LORA_LN_FOLD = 36,     /* 37 was SLH_OP_PREFETCH (side-stream weight touch: measured slower, removed in round 5) */
+    SLH_OP_LORA_MERGE = 38
 };
 /* SLH_OP_MEMSET: byte fill by a kernel of this library (not hipMemsetAsync: a captured memset node is a runtime blit whose
  * replays were observed to go wrong on the legacy default stream - see the executor's comment) */

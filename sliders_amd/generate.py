@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model_path", default=None, help="diffusers-format model directory (unet/, vae/, text encoders)")
     p.add_argument("--synthetic", action="store_true", help="random-init weights and embeddings (no model files)")
     p.add_argument("--lora_weight", default=None, help="slider checkpoint (.pt) written by the trainers")
+    p.add_argument("--compose", action="append", default=[], metavar="PATH:SCALE",
+                   help="one more slider (.pt, any rank) held at a fixed scale in every image; repeatable.  With --compose, or when "
+                        "--lora_weight is not rank 4, the sliders are merged into the weights (sliders_amd/merge.py)")
     p.add_argument("--prompt", default="image of a person")
     p.add_argument("--scales", default="-2,-1,0,1,2")
     p.add_argument("--start_noise", type=int, default=750)
@@ -61,6 +64,22 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--from_case", type=int, default=0)
     p.add_argument("--till_case", type=int, default=1000000)
     return p
+
+
+def parse_compose(spec: str) -> Tuple[str, float]:
+    """'PATH:SCALE' -> (path, scale); the scale follows the LAST colon"""
+    path, sep, scale = spec.rpartition(":")
+    if not sep or not path:
+        raise SystemExit(f"--compose {spec!r}: expected PATH:SCALE")
+    try:
+        return path, float(scale)
+    except ValueError:
+        raise SystemExit(f"--compose {spec!r}: {scale!r} is not a number")
+
+
+def slider_rank(sd) -> int:
+    """rank of a slider checkpoint, from its lora_down weights (the file name is only a convention)"""
+    return max(int(v.shape[0]) for k, v in sd.items() if k.endswith(".lora_down.weight"))
 
 
 def scale_folder(scale: float) -> str:
@@ -98,12 +117,20 @@ def main(argv=None):
         else:
             tok, enc = model_util.load_text_encoder(a.model_path, dev, torch.bfloat16)
             ctx, pooled = torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in ("", a.prompt)]), None
-    store = None
-    if a.lora_weight:
+    store = sliders = None
+    swept = torch.load(a.lora_weight, map_location="cpu") if a.lora_weight else None
+    if a.compose or (swept is not None and slider_rank(swept) != 4):
+        # several sliders, or a rank the fused adapter kernels are not built for: merged into the weights.  The swept slider
+        # (scale None) takes each image's --scales value, the composed ones keep theirs
+        from .merge import SliderSet
+        held = [parse_compose(c) for c in a.compose]
+        sliders = SliderSet(eng.cfg, ([(swept, None)] if swept is not None else [])
+                            + [(torch.load(path, map_location="cpu"), s) for path, s in held])
+    elif swept is not None:
         rank, alpha, method = parse_slider_name(a.lora_weight)
         store = LoraStore(eng.cfg, rank=rank, alpha=alpha, train_method=method, device=dev, init="none")
-        store.load_state_dict(torch.load(a.lora_weight, map_location="cpu"), strict=True)
-    smp = SliderSampler(eng, store, dec, scheduler=a.scheduler, scheduler_seed=a.seed)
+        store.load_state_dict(swept, strict=True)
+    smp = SliderSampler(eng, store, dec, scheduler=a.scheduler, scheduler_seed=a.seed, sliders=sliders)
     os.makedirs(a.out, exist_ok=True)
     from PIL import Image
     scales = [float(v) for v in a.scales.split(",")]

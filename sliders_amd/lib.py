@@ -97,6 +97,10 @@ BatchDesc = _struct("BatchDesc", _ptrs("table", "prefix") + _ints("n", "total", 
 Gather16Desc = _struct("Gather16Desc", _ptrs("src", "idx", "out") + [("n", c_i64)])
 LoraLnFoldDesc = _struct("LoraLnFoldDesc", _ptrs("items") + _ints("n", "pad_"))
 LORA_LNFOLD_ITEM_I64 = 7          # slh_lora_lnfold_item as int64 words: a, gamma, beta, a_out, s_out, c_out, rows | K << 32
+LoraMergeDesc = _struct("LoraMergeDesc", _ptrs("items", "prefix") + _ints("n", "total"))
+# slh_lora_merge_item: one row range of one stored matrix (include/sliders_hip.h)
+LoraMergeItem = _struct("LoraMergeItem", _ptrs("base", "out", "u", "d", "c", "gamma", "beta", "bias", "lns", "lnb")
+                        + _ints("n0", "rows", "N", "K", "R", "ldu", "ldd", "ld", "w_layout", "pad_"))
 VaeSampleDesc = _struct("VaeSampleDesc", _ptrs("moments", "post_noise", "noise", "latent_f32", "noisy_f32", "noisy_bf16")
                         + _ints("batch", "hw") + [("scaling", c_f32), ("sqrt_alpha", c_f32), ("sqrt_one_minus_alpha", c_f32)]
                         + _ints("pad_"))
@@ -105,7 +109,7 @@ VaeSampleDesc = _struct("VaeSampleDesc", _ptrs("moments", "post_noise", "noise",
 _SIZE_ORDER = [GemmDesc, SkinnyDesc, GemvDesc, GnDesc, GnBwdDesc, LnDesc, LnBwdDesc, AttnDesc, TransposeDesc,
                AttnBwdDesc, TembedDesc, ConvInDesc, EwDesc, CfgDdimDesc, LossDesc, WgradDesc, AdamwDesc, MemsetDesc,
                LoraCdgradDesc, TembLoraBwdDesc, SgemmDesc, Gn32Desc, Softmax32Desc, VaeConvDesc, VaeSampleDesc, LionDesc,
-               BatchDesc, Gather16Desc, LoraLnFoldDesc]
+               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc]
 
 # opcodes (enum in sliders_hip.h)
 OP_GEMM, OP_SKINNY, OP_GEMV, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTN_FWD, OP_TRANSPOSE_HEADS = range(1, 9)
@@ -116,6 +120,7 @@ OP_SGEMM, OP_GN32_STATS, OP_GN32_APPLY, OP_SOFTMAX32, OP_VAE_CONV_IN, OP_VAE_MOM
 OP_LION = 31
 OP_WGRAD_BATCH, OP_TRANSPOSE_BATCH, OP_GATHER16, OP_GN_FUSED = 32, 33, 34, 35
 OP_LORA_LN_FOLD = 36
+OP_LORA_MERGE = 38
 
 EW_COPY, EW_ADD, EW_GEGLU_FWD, EW_GEGLU_BWD, EW_UPSAMPLE_BWD, EW_COLSUM = range(6)
 
@@ -137,12 +142,12 @@ _ENTRY = {
     OP_VAE_POST_QUANT: ("slh_vae_post_quant", VaeConvDesc), OP_LION: ("slh_lion", LionDesc),
     OP_WGRAD_BATCH: ("slh_lora_wgrad_batch", BatchDesc), OP_TRANSPOSE_BATCH: ("slh_transpose_heads_batch", BatchDesc),
     OP_GATHER16: ("slh_gather16", Gather16Desc), OP_GN_FUSED: ("slh_gn_fused", GnDesc),
-    OP_LORA_LN_FOLD: ("slh_lora_ln_fold", LoraLnFoldDesc),
+    OP_LORA_LN_FOLD: ("slh_lora_ln_fold", LoraLnFoldDesc), OP_LORA_MERGE: ("slh_lora_merge", LoraMergeDesc),
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
            "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
-           "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok"] + [v[0] for v in _ENTRY.values()]
+           "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
 
 
 class SlidersHipError(RuntimeError):
@@ -285,6 +290,24 @@ def batch_table(opcode: int, descs, device, arg: int = 0):
     table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
     pre = torch.tensor(prefix, dtype=torch.int32, device=device)
     return BatchDesc(table=table.data_ptr(), prefix=pre.data_ptr(), n=len(descs), total=prefix[-1], arg=arg), (table, pre)
+
+
+def merge_table(items, device):
+    """slh_lora_merge items -> (LoraMergeDesc, tensors to keep alive).  Every item is validated by the library here
+    (slh_lora_merge_blocks); the device table and the running sum of workgroups are built once and reused by every launch."""
+    import torch
+    l = load()
+    l.slh_lora_merge_blocks.argtypes = [C.POINTER(LoraMergeItem)]
+    l.slh_lora_merge_blocks.restype = c_i32
+    prefix = [0]
+    for it in items:
+        nb = l.slh_lora_merge_blocks(C.byref(it))
+        if nb <= 0:
+            raise SlidersHipError(f"slh_lora_merge_blocks: {last_error()}")
+        prefix.append(prefix[-1] + nb)
+    table = torch.frombuffer(bytearray(b"".join(bytes(it) for it in items)), dtype=torch.uint8).to(device)
+    pre = torch.tensor(prefix, dtype=torch.int32, device=device)
+    return LoraMergeDesc(items=table.data_ptr(), prefix=pre.data_ptr(), n=len(items), total=prefix[-1]), (table, pre)
 
 
 def wgrad_single_blocks(desc) -> int:

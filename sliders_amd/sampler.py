@@ -25,17 +25,25 @@ from . import lib
 from . import schedulers
 from .ddim import DDIMSchedule
 from .lora_store import LoraStore
+from .merge import SliderSet, WeightMerger
 from .unet import UNetEngine
 from .vae import VaeDecoder
 
 
 class SliderSampler:
     def __init__(self, engine: UNetEngine, store: Optional[LoraStore] = None, decoder: Optional[VaeDecoder] = None,
-                 prediction_type: str = "epsilon", scheduler: str = "ddim", scheduler_seed: int = 0):
-        """scheduler: "ddim" (fused HIP step), "lms" (what eval-scripts/generate_images_sd1.py:51 and the SD-1 notebook
+                 prediction_type: str = "epsilon", scheduler: str = "ddim", scheduler_seed: int = 0,
+                 sliders: Optional[SliderSet] = None):
+        """sliders: several sliders of any rank, folded into the frozen weights (sliders_amd/merge.py) instead of the fused rank-4
+        adapter path of `store`: the loop samples on the base weights while t > start_noise, merges once when it crosses
+        start_noise, runs the adapter-free program on the merged weights and restores the original bits when the image is done.
+        scheduler: "ddim" (fused HIP step), "lms" (what eval-scripts/generate_images_sd1.py:51 and the SD-1 notebook
         construct), "euler" (the SDXL checkpoints' scheduler_config: what generate_images_xl.py's pipeline runs), "euler_a",
         "ddpm" - the non-DDIM ones from sliders_amd/schedulers.py."""
         self.eng, self.store, self.decoder = engine, store, decoder
+        if sliders is not None and store is not None:
+            raise ValueError("SliderSampler: give either store= (one rank-4 slider, fused adapters) or sliders= (merged weights)")
+        self.merger = WeightMerger(engine.weights, sliders) if sliders is not None else None
         if store is not None and engine.lora is not store:
             engine.attach_lora(store)
         if scheduler.lower().replace(" ", "_") == "ddim":
@@ -75,17 +83,37 @@ class SliderSampler:
         s = torch.cuda.current_stream().cuda_stream
         chw = eng.cfg.out_channels * h * w
         half = bs * chw * 2
-        for i, t in enumerate(self.sched.make_timesteps(ddim_steps)):
-            if self.store is not None:
-                eng.set_lora(True, 0.0 if t > start_noise else float(scale))
-            io["t"].tensor.fill_(float(t))
-            (p.prog if (i == 0 or p.prog_text_cached is None) else p.prog_text_cached).run(s)
-            d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, out2=smp.ptr + half, nb=bs, chw=chw,
-                                guidance=float(guidance_scale), **self.sched.step_fields(t, ddim_steps))
-            lib.call(lib.OP_CFG_DDIM, d, s)
+        try:
+            for i, t in enumerate(self.sched.make_timesteps(ddim_steps)):
+                if self.store is not None:
+                    eng.set_lora(True, 0.0 if t > start_noise else float(scale))
+                io["t"].tensor.fill_(float(t))
+                self._program(p, i, t, scale, start_noise).run(s)
+                d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, out2=smp.ptr + half, nb=bs, chw=chw,
+                                    guidance=float(guidance_scale), **self.sched.step_fields(t, ddim_steps))
+                lib.call(lib.OP_CFG_DDIM, d, s)
+        finally:
+            self._restore()
         if self.store is not None:
             eng.set_lora(False)
         return smp.tensor[:bs].clone()
+
+    def _program(self, p, i: int, t: float, scale: float, start_noise: float):
+        """The program of step i: the full pass for the first step and for the first step on newly merged weights (the cross-attention
+        K/V that prog_text_cached reuses were projected with the weights of the step before), else the one that skips the text
+        projections.  Merges the sliders when the loop crosses start_noise (all-zero scales: nothing to merge, the weights stay)."""
+        full = i == 0 or p.prog_text_cached is None
+        m = self.merger
+        if m is not None and not m.merged and not float(t) > start_noise:
+            scales = m.sliders.scales(scale)
+            if any(v != 0.0 for v in scales):
+                m.merge(scales)
+                full = True
+        return p.prog if full else p.prog_text_cached
+
+    def _restore(self):
+        if self.merger is not None and self.merger.merged:
+            self.merger.restore()
 
     def _sample_unfused(self, p, noise, scale, start_noise, steps, guidance_scale):
         """generate_images_sd1.py:160-185 with a tensor-op scheduler: scale_model_input -> UNet replay -> guidance combine
@@ -97,18 +125,21 @@ class SliderSampler:
         lat = (noise.to(eng.device, torch.float32) * sch.init_noise_sigma).to(torch.bfloat16)
         eps = torch.empty_like(lat)
         chw = lat[0].numel()
-        for i, t in enumerate(sch.timesteps):
-            if self.store is not None:
-                eng.set_lora(True, 0.0 if float(t) > start_noise else float(scale))
-            x = sch.scale_model_input(lat, t)
-            io["sample"].tensor[:bs].copy_(x)
-            io["sample"].tensor[bs:].copy_(x)
-            io["t"].tensor.fill_(float(t))
-            (p.prog if (i == 0 or p.prog_text_cached is None) else p.prog_text_cached).run(s)
-            d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=0, out=eps.data_ptr(), out2=0, nb=bs, chw=chw,
-                                guidance=float(guidance_scale), do_step=0)
-            lib.call(lib.OP_CFG_DDIM, d, s)
-            lat = sch.step(eps, t, lat, generator=self.sched_generator).prev_sample
+        try:
+            for i, t in enumerate(sch.timesteps):
+                if self.store is not None:
+                    eng.set_lora(True, 0.0 if float(t) > start_noise else float(scale))
+                x = sch.scale_model_input(lat, t)
+                io["sample"].tensor[:bs].copy_(x)
+                io["sample"].tensor[bs:].copy_(x)
+                io["t"].tensor.fill_(float(t))
+                self._program(p, i, float(t), scale, start_noise).run(s)
+                d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=0, out=eps.data_ptr(), out2=0, nb=bs, chw=chw,
+                                    guidance=float(guidance_scale), do_step=0)
+                lib.call(lib.OP_CFG_DDIM, d, s)
+                lat = sch.step(eps, t, lat, generator=self.sched_generator).prev_sample
+        finally:
+            self._restore()
         if self.store is not None:
             eng.set_lora(False)
         return lat

@@ -79,7 +79,15 @@ class UNetEngine:
         return None
 
     # ---- LoRA switch (driven by sliders_amd.lora.LoRANetwork) ------------------------------------
+    @property
+    def w(self) -> WeightStore:
+        return self.weights
+
     def attach_lora(self, store: LoraStore):
+        if store.rank != 4:
+            raise NotImplementedError(
+                f"the fused adapter kernels are built for rank 4, this LoraStore has rank {store.rank}: train at rank 4; sliders of "
+                f"other ranks are sampled through the weight merge (sliders_amd.merge.SliderSet, SliderSampler(engine, sliders=...))")
         self.lora = store
         self._plans = {k: v for k, v in self._plans.items() if k[3] == "off"}
 
