@@ -336,6 +336,10 @@ typedef struct slh_attn_desc {
 } slh_attn_desc;
 int slh_attn_fwd(const slh_attn_desc* d, slh_stream_t stream);
 int slh_attn_fwd_carries_touch(const slh_attn_desc* d);
+/* The kernel instantiation slh_attn_fwd would launch for d, as a profiler prints it ("attn_fwd_kernel<4, 1, true>": workgroup waves,
+ * d-tiles, masked tail tile; "attn_fwd_ks_kernel": the key-split form), written to buf (cap >= 32).  Answered by the dispatch code
+ * itself, environment knobs included; no device needed, nothing launched.  0, or the error slh_attn_fwd would give. */
+int slh_attn_fwd_kernel_name(const slh_attn_desc* d, char* buf, int cap);
 
 /* src [B][T][ld] columns [h*64,(h+1)*64) -> dst [B][H][64][ldt] (columns >= T zero-filled up to ldt) */
 typedef struct slh_transpose_desc {
@@ -353,8 +357,9 @@ typedef struct slh_attn_bwd_desc {
     const void* kt;          /* [B][H][64][ldkt] K transposed (slh_transpose_heads) */
     const void* qt;          /* [B][H][64][ldqt] Q transposed   (need_dkv only) */
     const void* dot;         /* [B][H][64][ldqt] dO transposed  (need_dkv only) */
-    const float* lse;        /* [B][H][Tq] from the forward, padded by 64 floats */
-    float* delta;            /* [B][H][Tq] fp32 workspace, padded by 64 floats */
+    const float* lse;        /* [B][H][Tq] from the forward, padded by 64 floats: the dK/dV kernel reads up to 63 floats past the end. */
+    float* delta;            /* [B][H][Tq] fp32 workspace, padded by 64 floats.  The padding of both may hold ANYTHING (NaN, Inf,
+                                recycled memory): it is read, never used, and never written */
     void* dq; void* dk; void* dv;
     int32_t B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddo, ldkt, ldqt, lddq, lddk, lddv;
     float scale;
@@ -363,6 +368,9 @@ typedef struct slh_attn_bwd_desc {
     int32_t pad_;
 } slh_attn_bwd_desc;
 int slh_attn_bwd(const slh_attn_bwd_desc* d, slh_stream_t stream);
+/* The dq and dkv instantiations slh_attn_bwd would launch for d ("attn_bwd_dq_kernel<2>", "attn_bwd_dkv_kernel<2, 2>": d-tiles, query
+ * tile buffers; dkv = "" with need_dkv = 0), each written to a buffer of cap >= 32 bytes.  No device needed, nothing launched. */
+int slh_attn_bwd_kernel_names(const slh_attn_bwd_desc* d, char* dq, char* dkv, int cap);
 
 /* ------------------------------------------------------------------------------------------------
  * small ops

@@ -470,33 +470,48 @@ static bool attn_ks_form(const slh_attn_desc* d, int DT) {
     return knob_ks && attn_ks_ok(d, DT) && blocks4 < 512 && blocks2 > 128 && blocks2 <= 768;
 }
 
-template <int DT>
-int launch_fwd(const slh_attn_desc* d, hipStream_t s) {
-    const long blocks4 = (long)((d->Tq + 127) / 128) * d->H * d->B;
-    const bool tail = (d->Tk & 63) != 0;
+// The one place that decides which forward kernel runs a descriptor: launch_fwd launches what this returns, slh_attn_fwd_kernel_name
+// names it through the same launch statements (common.h: slh_launch), slh_attn_fwd_carries_touch reads .ks of the default knobs.
+struct attn_fwd_form {
+    bool ks;        // attn_fwd_ks_kernel (D = 64, whole key tiles in two equal halves), else attn_fwd_kernel<nw, DT, tail>
+    int nw;         // 4: 128-query workgroups, 2: 64-query workgroups
+    bool tail;      // Tk is not a multiple of 64
+    long blocks;    // workgroups of the launch's own (the key-split form adds the weight-touch workgroups behind them)
+};
+static attn_fwd_form attn_fwd_choose(const slh_attn_desc* d, int DT) {
     static const int knob_nw2 = getenv("SLH_ATTN_NW2") ? atoi(getenv("SLH_ATTN_NW2")) : 0;     // A/B: 64-query workgroups everywhere
+    static const int knob_ks = getenv("SLH_ATTN_KS") ? atoi(getenv("SLH_ATTN_KS")) : 1;        // A/B: 0 = never, 2 = whenever the shape allows
+    const long blocks4 = (long)((d->Tq + 127) / 128) * d->H * d->B;
+    attn_fwd_form f;
+    f.tail = (d->Tk & 63) != 0;
+    // key-split form (attn_fwd_ks_kernel above): D = 64, whole key tiles in two equal halves, and a 64-query grid that neither
+    // fills every SIMD twice (>= 1024 workgroups) nor is so small that one round of full-length waves is cheaper
+    f.ks = attn_ks_form(d, DT) || (knob_ks == 2 && attn_ks_ok(d, DT));
     // 128-query workgroups once they fill every CU twice; below that the 64-query form (same waves per SIMD at most, finer
     // placement: T = 1024 with 40 heads 31.2 -> 28.9 us, same box).  (Capping the workgroups per CU with unused dynamic LDS so
     // that the dispatcher must spread them was tried: the hardware already places them evenly, the cap only delays backfill.)
-    // key-split form (attn_fwd_ks_kernel above): D = 64, whole key tiles in two equal halves, and a 64-query grid that neither
-    // fills every SIMD twice (>= 1024 workgroups) nor is so small that one round of full-length waves is cheaper
-    static const int knob_ks = getenv("SLH_ATTN_KS") ? atoi(getenv("SLH_ATTN_KS")) : 1;        // A/B: 0 = never
-    const long blocks2 = (long)(d->Tq / 64) * d->H * d->B;
-    if (attn_ks_form(d, DT) || (knob_ks == 2 && attn_ks_ok(d, DT))) {      // 2 = whenever the shape allows (A/B)
+    f.nw = (!f.ks && blocks4 >= 512 && !knob_nw2) ? 4 : 2;
+    f.blocks = f.ks ? (long)(d->Tq / 64) * d->H * d->B : f.nw == 4 ? blocks4 : (long)((d->Tq + 63) / 64) * d->H * d->B;
+    return f;
+}
+
+template <int DT>
+int launch_fwd(const slh_attn_desc* d, hipStream_t s) {
+    const attn_fwd_form f = attn_fwd_choose(d, DT);
+    const int grid = (int)f.blocks;
+    if (f.ks) {
         // weight touch (pf_*): up to 64 workgroups behind the launch's own; with three workgroups per CU they are resident beside them
         const int pf_blocks = (d->pf_ptr && d->pf_bytes >= 16) ? 64 : 0;
-        hipLaunchKernelGGL(attn_fwd_ks_kernel, dim3((unsigned)blocks2 + pf_blocks), dim3(256), 0, s, *d);
+        slh_launch<attn_fwd_ks_kernel>(grid + pf_blocks, 256, s, *d, "attn_fwd_ks_kernel");
         SLH_LAUNCH_CHECK("slh_attn_fwd (key split)");
         return 0;
     }
-    if (blocks4 >= 512 && !knob_nw2) {
-        const dim3 grid((unsigned)blocks4);
-        if (tail) hipLaunchKernelGGL((attn_fwd_kernel<4, DT, true>), grid, dim3(256), 0, s, *d);
-        else hipLaunchKernelGGL((attn_fwd_kernel<4, DT, false>), grid, dim3(256), 0, s, *d);
+    if (f.nw == 4) {
+        if (f.tail) slh_launch<attn_fwd_kernel<4, DT, true>>(grid, 256, s, *d, "attn_fwd_kernel<4, %d, true>", DT);
+        else slh_launch<attn_fwd_kernel<4, DT, false>>(grid, 256, s, *d, "attn_fwd_kernel<4, %d, false>", DT);
     } else {
-        const dim3 grid((unsigned)((long)((d->Tq + 63) / 64) * d->H * d->B));
-        if (tail) hipLaunchKernelGGL((attn_fwd_kernel<2, DT, true>), grid, dim3(128), 0, s, *d);
-        else hipLaunchKernelGGL((attn_fwd_kernel<2, DT, false>), grid, dim3(128), 0, s, *d);
+        if (f.tail) slh_launch<attn_fwd_kernel<2, DT, true>>(grid, 128, s, *d, "attn_fwd_kernel<2, %d, true>", DT);
+        else slh_launch<attn_fwd_kernel<2, DT, false>>(grid, 128, s, *d, "attn_fwd_kernel<2, %d, false>", DT);
     }
     SLH_LAUNCH_CHECK("slh_attn_fwd");
     return 0;
@@ -523,6 +538,18 @@ extern "C" int slh_attn_fwd(const slh_attn_desc* d, slh_stream_t stream) {
     if (DT == 1) return launch_fwd<1>(d, s);
     if (DT == 2) return launch_fwd<2>(d, s);
     return launch_fwd<3>(d, s);
+}
+
+// the name of the kernel instantiation slh_attn_fwd would launch for d, as rocprofv3 prints it ("attn_fwd_kernel<4, 1, true>",
+// "attn_fwd_ks_kernel"): the whole of slh_attn_fwd runs - descriptor checks, attn_fwd_choose with the SLH_ATTN_KS / SLH_ATTN_NW2
+// knobs - with the launch replaced by a record of the selected template.  No device needed, nothing launched.
+extern "C" int slh_attn_fwd_kernel_name(const slh_attn_desc* d, char* buf, int cap) {
+    SLH_CHECK(buf && cap >= 32, "slh_attn_fwd_kernel_name: buffer");
+    slh_name_sink_set(buf, cap);
+    const int rc = slh_attn_fwd(d, nullptr);
+    slh_name_sink_set(nullptr, 0);
+    if (rc == 0 && !buf[0]) { slh_set_error("slh_attn_fwd_kernel_name: internal: no launch site recorded a name"); return -3; }
+    return rc;
 }
 
 static int transpose_check(const slh_transpose_desc* d) {

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
             lds_dma_syncthreads();    // tile t landed for all waves
         }
         const int bufo = (NBUF == 2 ? (t & 1) : 0) * DT * 8192;
-        // per-query lse2 / delta straight from global (L1-resident; the arrays are padded by 64 floats)
+        // per-query lse2 / delta straight from global (L1-resident; the arrays are padded by 64 floats whose contents are never used)
         const float* cL = p.lse + ((long)b * p.H + h) * p.Tq + t * 64;
         const float* cD = p.delta + ((long)b * p.H + h) * p.Tq + t * 64;
         bf16x8 pb[2][2], dsb[2][2];
@@ -276,9 +276,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
                 for (int e = 0; e < 8; ++e) {
                     const int r = hf * 8 + e;
                     float pv = __builtin_amdgcn_exp2f(s[r] * c - lv[e]);
-                    if (t * 64 + qb + e >= p.Tq) pv = 0.f;
+                    const bool dead = t * 64 + qb + e >= p.Tq;
+                    if (dead) pv = 0.f;
                     pb[qt][hf][e] = (__bf16)pv;
-                    dsb[qt][hf][e] = (__bf16)(pv * (dp[r] - dl[e]));
+                    // rows >= Tq: dl / lv come from beyond the arrays (the next head's values, or the padding, which may hold anything -
+                    // NaN, Inf): select, never multiply, so that nothing read there reaches the dK MFMA
+                    dsb[qt][hf][e] = dead ? (__bf16)0.f : (__bf16)(pv * (dp[r] - dl[e]));
                 }
             }
         }
@@ -315,9 +318,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
     }
 }
 
-}  // namespace
-
-extern "C" int slh_attn_bwd(const slh_attn_bwd_desc* d, slh_stream_t stream) {
+// the descriptor checks of slh_attn_bwd
+static int attn_bwd_check(const slh_attn_bwd_desc* d) {
     SLH_CHECK(d && d->q && d->k && d->v && d->o && d->d_o && d->lse && d->delta && d->dq && d->kt,
               "slh_attn_bwd: null pointer");
     const int D = d->D > 0 ? d->D : 64;
@@ -326,23 +328,60 @@ extern "C" int slh_attn_bwd(const slh_attn_bwd_desc* d, slh_stream_t stream) {
                   d->lddq % 4 == 0 && d->ldkt % 64 == 0,
               "slh_attn_bwd: alignment");
     SLH_CHECK(d->ldkt >= ((d->Tk + 63) / 64) * 64, "slh_attn_bwd: KT must be padded to a multiple of 64 keys");
-    hipStream_t s = (hipStream_t)stream;
-    const int DT = (D + 63) / 64;
-    const long total = (long)d->B * d->Tq * d->H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *d, D);
-    const dim3 gq((unsigned)((long)((d->Tq + 127) / 128) * d->H * d->B));
-    if (DT == 1) hipLaunchKernelGGL(attn_bwd_dq_kernel<1>, gq, dim3(256), 0, s, *d);
-    else if (DT == 2) hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, gq, dim3(256), 0, s, *d);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<3>, gq, dim3(256), 0, s, *d);
     if (d->need_dkv) {
         SLH_CHECK(d->qt && d->dot && d->dk && d->dv, "slh_attn_bwd: dK/dV need qt, dot, dk, dv");
         SLH_CHECK(d->ldqt % 64 == 0 && d->ldqt >= ((d->Tq + 63) / 64) * 64 && d->lddk % 4 == 0 && d->lddv % 4 == 0,
                   "slh_attn_bwd: QT/dOT padding");
-        const dim3 gk((unsigned)((long)((d->Tk + 127) / 128) * d->H * d->B));
-        if (DT == 1) hipLaunchKernelGGL((attn_bwd_dkv_kernel<1, 2>), gk, dim3(256), 0, s, *d);
-        else if (DT == 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<2, 2>), gk, dim3(256), 0, s, *d);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<3, 1>), gk, dim3(256), 0, s, *d);
     }
+    return 0;
+}
+
+// The one place each that picks the dq / dkv instantiation: slh_attn_bwd launches through them, slh_attn_bwd_kernel_names names
+// through them (common.h: slh_launch records the template instead of launching it while a name sink is set).
+static void launch_bwd_dq(const slh_attn_bwd_desc* d, hipStream_t s) {
+    const int D = d->D > 0 ? d->D : 64, DT = (D + 63) / 64;
+    const int gq = (int)((long)((d->Tq + 127) / 128) * d->H * d->B);
+    if (DT == 1) slh_launch<attn_bwd_dq_kernel<1>>(gq, 256, s, *d, "attn_bwd_dq_kernel<1>");
+    else if (DT == 2) slh_launch<attn_bwd_dq_kernel<2>>(gq, 256, s, *d, "attn_bwd_dq_kernel<2>");
+    else slh_launch<attn_bwd_dq_kernel<3>>(gq, 256, s, *d, "attn_bwd_dq_kernel<3>");
+}
+static void launch_bwd_dkv(const slh_attn_bwd_desc* d, hipStream_t s) {
+    const int D = d->D > 0 ? d->D : 64, DT = (D + 63) / 64;
+    const int gk = (int)((long)((d->Tk + 127) / 128) * d->H * d->B);
+    if (DT == 1) slh_launch<attn_bwd_dkv_kernel<1, 2>>(gk, 256, s, *d, "attn_bwd_dkv_kernel<1, 2>");
+    else if (DT == 2) slh_launch<attn_bwd_dkv_kernel<2, 2>>(gk, 256, s, *d, "attn_bwd_dkv_kernel<2, 2>");
+    else slh_launch<attn_bwd_dkv_kernel<3, 1>>(gk, 256, s, *d, "attn_bwd_dkv_kernel<3, 1>");
+}
+
+}  // namespace
+
+extern "C" int slh_attn_bwd(const slh_attn_bwd_desc* d, slh_stream_t stream) {
+    if (attn_bwd_check(d)) return -1;
+    const int D = d->D > 0 ? d->D : 64;
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)d->B * d->Tq * d->H;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *d, D);
+    launch_bwd_dq(d, s);
+    if (d->need_dkv) launch_bwd_dkv(d, s);
     SLH_LAUNCH_CHECK("slh_attn_bwd");
+    return 0;
+}
+
+// the names of the dq and dkv instantiations slh_attn_bwd would launch for d, as rocprofv3 prints them ("attn_bwd_dq_kernel<2>",
+// "attn_bwd_dkv_kernel<2, 2>"; dkv is the empty string with need_dkv = 0): the descriptor checks and launch_bwd_dq / launch_bwd_dkv run
+// with the launches replaced by a record of the selected template.  No device needed, nothing launched.  (attn_delta_kernel, which
+// every call launches first, has one form.)
+extern "C" int slh_attn_bwd_kernel_names(const slh_attn_bwd_desc* d, char* dq, char* dkv, int cap) {
+    SLH_CHECK(dq && dkv && cap >= 32, "slh_attn_bwd_kernel_names: buffers");
+    dq[0] = dkv[0] = 0;
+    if (attn_bwd_check(d)) return -1;
+    slh_name_sink_set(dq, cap);
+    launch_bwd_dq(d, nullptr);
+    if (d->need_dkv) {
+        slh_name_sink_set(dkv, cap);
+        launch_bwd_dkv(d, nullptr);
+    }
+    slh_name_sink_set(nullptr, 0);
+    if (!dq[0] || (d->need_dkv && !dkv[0])) { slh_set_error("slh_attn_bwd_kernel_names: internal: no launch site recorded a name"); return -3; }
     return 0;
 }

@@ -146,7 +146,7 @@ _ENTRY = {
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
-           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
+           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_attn_fwd_kernel_name", "slh_attn_bwd_kernel_names", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
            "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
 
 
@@ -328,6 +328,32 @@ def attn_carries_touch(desc) -> bool:
     lib.slh_attn_fwd_carries_touch.argtypes = [C.POINTER(AttnDesc)]
     lib.slh_attn_fwd_carries_touch.restype = c_i32
     return bool(lib.slh_attn_fwd_carries_touch(C.byref(desc)))
+
+
+def attn_fwd_kernel_name(desc) -> str:
+    """slh_attn_fwd_kernel_name: the instantiation slh_attn_fwd would launch for this descriptor ('attn_fwd_kernel<4, 1, true>',
+    'attn_fwd_ks_kernel'), named by the dispatch code itself; raises for a descriptor slh_attn_fwd refuses."""
+    lib = load()
+    lib.slh_attn_fwd_kernel_name.argtypes = [C.POINTER(AttnDesc), C.c_char_p, c_i32]
+    lib.slh_attn_fwd_kernel_name.restype = c_i32
+    buf = C.create_string_buffer(96)
+    rc = lib.slh_attn_fwd_kernel_name(C.byref(desc), buf, 96)
+    if rc != 0:
+        raise SlidersHipError(f"slh_attn_fwd_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
+    return buf.value.decode()
+
+
+def attn_bwd_kernel_names(desc):
+    """slh_attn_bwd_kernel_names: (dq, dkv) instantiations slh_attn_bwd would launch ('attn_bwd_dq_kernel<2>',
+    'attn_bwd_dkv_kernel<2, 2>'; dkv is '' with need_dkv = 0); raises for a descriptor slh_attn_bwd refuses."""
+    lib = load()
+    lib.slh_attn_bwd_kernel_names.argtypes = [C.POINTER(AttnBwdDesc), C.c_char_p, C.c_char_p, c_i32]
+    lib.slh_attn_bwd_kernel_names.restype = c_i32
+    a, b = C.create_string_buffer(96), C.create_string_buffer(96)
+    rc = lib.slh_attn_bwd_kernel_names(C.byref(desc), a, b, 96)
+    if rc != 0:
+        raise SlidersHipError(f"slh_attn_bwd_kernel_names failed ({rc}): {lib.slh_last_error().decode()}")
+    return a.value.decode(), b.value.decode()
 
 
 def gemm_kernel_name(desc) -> str:

@@ -1139,3 +1139,281 @@ def test_every_gemm_of_the_dry_run_plans_passes_the_capability_rule(name, hw, me
                 assert lib.gemm_kernel_name(d)
                 assert not d.vt_out or d.vt_ld == d.vt_tokens
     assert n > 100
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The attention test matrix (tests/attention_matrix.py): the library names its kernels, the bounds admit an honest implementation and
+# reject mutants of it, and the matrix reaches every form
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_attention_kernel_names_come_from_the_library():
+    """slh_attn_fwd_kernel_name / slh_attn_bwd_kernel_names: answered by the dispatch code (attn_fwd_choose, launch_bwd_dq / _dkv), no
+    device needed; the SLH_ATTN_NW2 / SLH_ATTN_KS knobs are part of the answer; a refused descriptor gives the error, not a name."""
+    import subprocess
+    import sys
+    from tests import attention_matrix as am
+    F = am.FwdCase
+    for c, want in ((F(4, 16, 1024, 77, 64, "a"), "attn_fwd_kernel<4, 1, true>"), (F(4, 16, 1024, 192, 160, "a"), "attn_fwd_kernel<4, 3, false>"),
+                    (F(1, 3, 192, 192, 80, "a"), "attn_fwd_kernel<2, 2, false>"), (F(2, 10, 1024, 1024, 64, "a"), "attn_fwd_ks_kernel"),
+                    (F(1, 128, 64, 256, 64, "a"), "attn_fwd_kernel<2, 1, false>"), (F(1, 129, 64, 256, 64, "a"), "attn_fwd_ks_kernel"),
+                    (F(6, 64, 128, 256, 64, "a"), "attn_fwd_ks_kernel"), (F(1, 769, 64, 256, 64, "a"), "attn_fwd_kernel<4, 1, false>"),
+                    (F(2, 10, 1024, 1024, 80, "a"), "attn_fwd_kernel<2, 2, false>"), (F(2, 10, 1024, 320, 64, "a"), "attn_fwd_kernel<2, 1, false>")):
+        d = am.fwd_desc(c)
+        assert lib.attn_fwd_kernel_name(d) == want, c.id
+        assert lib.attn_carries_touch(d) == (want == "attn_fwd_ks_kernel"), c.id
+    Bc = am.BwdCase
+    assert am.bwd_names(Bc(2, 2, 100, 100, 40, "a")) == ("attn_bwd_dq_kernel<1>", "attn_bwd_dkv_kernel<1, 2>")
+    assert am.bwd_names(Bc(2, 2, 100, 100, 80, "a")) == ("attn_bwd_dq_kernel<2>", "attn_bwd_dkv_kernel<2, 2>")
+    assert am.bwd_names(Bc(2, 2, 100, 100, 160, "a")) == ("attn_bwd_dq_kernel<3>", "attn_bwd_dkv_kernel<3, 1>")
+    assert am.bwd_names(Bc(2, 2, 100, 77, 160, "a", need_dkv=0)) == ("attn_bwd_dq_kernel<3>", "")
+    d = am.fwd_desc(F(1, 3, 192, 192, 64, "a"))
+    d.D = 44
+    with pytest.raises(lib.SlidersHipError, match="head_dim"):
+        lib.attn_fwd_kernel_name(d)
+    d = am.bwd_desc(Bc(2, 2, 100, 100, 64, "a"))
+    d.qt = 0
+    with pytest.raises(lib.SlidersHipError, match="dK/dV need"):
+        lib.attn_bwd_kernel_names(d)
+    # the knobs are read once per process
+    code = ("from tests import attention_matrix as am; F = am.FwdCase; "
+            "print(am.fwd_name(F(4, 16, 1024, 77, 64, 'a')), '|', am.fwd_name(F(2, 10, 1024, 1024, 64, 'a')), '|', am.fwd_name(F(4, 16, 1024, 256, 64, 'a')))")
+    for env, want in (({"SLH_ATTN_NW2": "1"}, "attn_fwd_kernel<2, 1, true> | attn_fwd_ks_kernel | attn_fwd_kernel<2, 1, false>"),
+                      ({"SLH_ATTN_KS": "0"}, "attn_fwd_kernel<4, 1, true> | attn_fwd_kernel<2, 1, false> | attn_fwd_kernel<4, 1, false>"),
+                      ({"SLH_ATTN_KS": "2"}, "attn_fwd_kernel<4, 1, true> | attn_fwd_ks_kernel | attn_fwd_ks_kernel")):
+        out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env={**os.environ, **env}, capture_output=True, text=True, check=True).stdout
+        assert out.strip() == want, (env, out)
+
+
+def _attn_fwd_check(am, c, key_split=False, mutant=None, seed=1):
+    """stand-in (or a mutant of it) against the forward bounds: {output: (worst ratio, b)} or {output: the AssertionError's text}"""
+    from tests.util import check_elementwise
+    L = am.make_inputs(c, "cpu", seed)
+    q, k, v = (am.heads(L[n]) for n in "qkv")
+    o, bo, l, bl = am.forward_reference(q, k, v, c.D ** -0.5)
+    go, gl = am.standin_forward(q, k, v, c.D ** -0.5, key_split, mutant)
+    res = {}
+    for nm, g, r, b in (("o", go, o, bo), ("lse", gl, l, bl)):
+        try:
+            w, _, bb = check_elementwise(f"{c.id} {mutant or 'stand-in'} [{nm}]", g, r, b, statistic=nm == "o")
+            res[nm] = (w, bb)
+        except AssertionError as e:
+            res[nm] = str(e)
+    return res
+
+
+def _attn_bwd_check(am, c, mutant=None, pad=float("nan"), seed=1):
+    from tests.util import check_elementwise
+    L = am.make_inputs(c, "cpu", seed)
+    q, k, v, do = (am.heads(L[n]) for n in ("q", "k", "v", "do"))
+    sc = c.D ** -0.5
+    o, lse = am.forward_for_backward(q, k, v, sc)
+    ref = am.backward_reference(q, k, v, o, do, lse, sc, bool(c.need_dkv))
+    padding = torch.full((64,), pad)
+    got = am.standin_backward(q, k, v, o, do, torch.cat([lse.reshape(-1), padding]), padding, sc, bool(c.need_dkv), mutant)
+    res = {}
+    for nm, (r, b) in ref.items():
+        try:
+            w, _, bb = check_elementwise(f"{c.id} {mutant or 'stand-in'} [{nm}]", got[nm], r, b, statistic=am.bwd_takes_statistic(c) and nm != "delta")
+            res[nm] = (w, bb)
+        except AssertionError as e:
+            res[nm] = str(e)
+    return res, got
+
+
+_ATTN_FWD_SMALL = [("a", 2, 4, 256, 192, 64), ("ac", 2, 4, 256, 192, 64), ("bc", 2, 4, 256, 77, 64), ("dc", 2, 4, 256, 256, 64), ("ec", 1, 8, 320, 384, 64),
+                   ("fc", 2, 4, 256, 256, 160), ("g", 2, 4, 200, 65, 64), ("gc", 2, 4, 256, 333, 80), ("b", 2, 2, 129, 5, 40), ("a", 2, 2, 33, 1, 64)]
+
+
+@pytest.mark.parametrize("cls,B,H,Tq,Tk,D", _ATTN_FWD_SMALL, ids=[f"{s[0]}-Tq{s[3]}-Tk{s[4]}-D{s[5]}" for s in _ATTN_FWD_SMALL])
+def test_attention_forward_bounds_admit_the_standin(cls, B, H, Tq, Tk, D):
+    """every input class, at small shapes: the stand-in of attn_fwd_kernel - and of the key-split kernel where Tk allows - meets the o and
+    lse bounds at every element, and the rounding statistic wherever it applies (class c with >= 10000 elements above 0.1: it must)"""
+    from tests import attention_matrix as am
+    from tests.util import STAT_LIMIT
+    c = am.FwdCase(B, H, Tq, Tk, D, cls)
+    for ks in ((False, True) if Tk % 128 == 0 and Tk >= 256 else (False,)):
+        res = _attn_fwd_check(am, c, key_split=ks)
+        assert all(isinstance(r, tuple) for r in res.values()), res
+        (w, b), (wl, _) = res["o"], res["lse"]
+        print(f"[parity] attention stand-in {c.id} key_split={ks}: worst |got - ref| / bound = {w:.3f} (o), {wl:.3f} (lse), b = {b}")
+        assert w <= 1.0 and wl <= 1.0
+        if "c" in cls:
+            assert b is not None and abs(b) <= STAT_LIMIT
+    if "g" in cls:       # the class does what it says: the last key leads by more than 30 in the exponent
+        L = am.make_inputs(c, "cpu", 1)
+        s = (am.heads(L["q"]).double() @ am.heads(L["k"]).double().transpose(-1, -2)) * D ** -0.5
+        assert float((s[..., -1] - s[..., :-1].amax(-1)).min()) > 30.0
+    if "e" in cls or "f" in cls:   # the row maximum rises (falls) from tile to tile for nearly every row
+        L = am.make_inputs(c, "cpu", 1)
+        s = (am.heads(L["q"]).double() @ am.heads(L["k"]).double().transpose(-1, -2)) * D ** -0.5
+        tm = torch.stack([s[..., t:t + 64].amax(-1) for t in range(0, Tk, 64)], -1)
+        step = tm[..., 1:] - tm[..., :-1]
+        assert float(((step > 0) if "e" in cls else (step < 0)).double().mean()) > 0.99
+    if Tk == 1:
+        L = am.make_inputs(c, "cpu", 1)
+        go, _ = am.standin_forward(*(am.heads(L[n]) for n in "qkv"), D ** -0.5)
+        assert torch.equal(go, am.heads(L["v"]).expand(B, H, Tq, D))
+
+
+def test_attention_forward_bounds_reject_the_mutants():
+    """Each forward mutant of the stand-in fails a check.  The two truncations are caught by the rounding statistic (class c, >= 10000
+    elements above 0.1 - which is why the matrix pairs class c with every form); the denominator summed from the rounded P is caught by
+    the lse bound, o alone lets it pass; the missing tail mask needs class g (the clamped row Tk - 1 counted again in the denominator)."""
+    from tests import attention_matrix as am
+    from tests.util import STAT_LIMIT, rounding_statistic
+    F = am.FwdCase
+    ac, g, dc = F(2, 4, 256, 192, 64, "ac"), F(2, 4, 200, 65, 64, "g"), F(2, 4, 256, 256, 64, "dc")
+    for c, ks, mutant, where in ((ac, False, "p_trunc", "o"), (ac, False, "o_trunc", "o"), (ac, False, "drop_last_key", "o"), (g, False, "no_tail_mask", "o"),
+                                 (ac, False, "skip_rescale", "o"), (ac, False, "l_from_rounded_p", "lse"), (dc, True, "ks_merge_without_a1", "o"),
+                                 (dc, True, "p_trunc", "o"), (dc, True, "skip_rescale", "o")):
+        good, bad = _attn_fwd_check(am, c, ks), _attn_fwd_check(am, c, ks, mutant)
+        assert all(isinstance(r, tuple) for r in good.values()), good
+        assert isinstance(bad[where], str), f"{mutant} passed the {where} check of {c.id}: {bad}"
+        print(f"[parity] attention mutant {mutant} ({c.id}): caught - {bad[where][:150]}")
+    assert isinstance(_attn_fwd_check(am, ac, False, "l_from_rounded_p")["o"], tuple)          # only the lse bound sees it
+    for mutant in ("p_trunc", "o_trunc"):                                                       # the statistic alone sees truncation
+        L = am.make_inputs(ac, "cpu", 1)
+        q, k, v = (am.heads(L[n]) for n in "qkv")
+        b, cnt = rounding_statistic(am.standin_forward(q, k, v, 0.125, False, mutant)[0], am.forward_reference(q, k, v, 0.125)[0])
+        assert b is not None and abs(b) > STAT_LIMIT and cnt >= 10000, (mutant, b, cnt)
+
+
+_ATTN_BWD_SMALL = [("a", "n", 2, 2, 100, 100, 64, 1), ("b", "n", 2, 4, 256, 256, 64, 1), ("bc", "o", 2, 2, 200, 77, 80, 1), ("d", "n", 1, 2, 256, 256, 160, 1),
+                   ("g", "n", 1, 2, 129, 65, 160, 1), ("e", "o", 1, 2, 320, 448, 64, 1), ("f", "n", 1, 2, 192, 320, 80, 1), ("b", "o", 2, 2, 192, 5, 80, 0)]
+
+
+@pytest.mark.parametrize("cls,do_cls,B,H,Tq,Tk,D,dkv", _ATTN_BWD_SMALL, ids=[f"{s[0]}{s[1]}-Tq{s[4]}-Tk{s[5]}-D{s[6]}" for s in _ATTN_BWD_SMALL])
+def test_attention_backward_bounds_admit_the_standin(cls, do_cls, B, H, Tq, Tk, D, dkv):
+    """every input class, dO with and without an offset: the stand-in of the delta, dq and dkv kernels - handed NaN in the 64 floats behind
+    lse and delta - meets every bound, no non-finite value, and the rounding statistic where bwd_takes_statistic says it applies"""
+    from tests import attention_matrix as am
+    from tests.util import STAT_LIMIT
+    c = am.BwdCase(B, H, Tq, Tk, D, cls, do_cls, need_dkv=dkv)
+    res, _ = _attn_bwd_check(am, c)
+    assert all(isinstance(r, tuple) for r in res.values()), res
+    print(f"[parity] attention backward stand-in {c.id}: " + ", ".join(f"{n} {w:.3f} (b = {b})" for n, (w, b) in res.items()))
+    assert all(w <= 1.0 and (b is None or abs(b) <= STAT_LIMIT) for w, b in res.values())
+    if (cls, do_cls) == ("b", "n"):
+        assert all(res[n][1] is not None for n in ("dq", "dk", "dv")), res
+
+
+def test_attention_backward_bounds_reject_the_mutants():
+    """Each backward mutant fails a check - but for two that compute the same function on every valid input, which is shown instead:
+      * dq_no_kv_mask: the keys past Tk of the last tile are key Tk - 1 again, p is finite there, and K^T is ZERO there (slh_transpose_heads),
+        so the unmasked dS columns meet zeros in the dQ MFMA: bit-identical results.
+      * no_q_tail_zero / ds_multiplied_not_selected with FINITE values behind lse and delta: Q^T and dO^T are zero for the rows past Tq.
+    With NaN behind lse / delta - what recycled arena memory may hold - the last two put 0 x NaN into the dK (and dV) product of the last
+    (sample, head): non-finite dK.  ds_multiplied_not_selected is attn_bwd_dkv_kernel as it was before the rows past Tq were selected."""
+    from tests import attention_matrix as am
+    B_ = am.BwdCase
+    stat, ragged = B_(2, 4, 256, 256, 64, "b", "n"), B_(2, 2, 100, 100, 64, "a", "n")
+    for c, mutant, where in ((stat, "ds_trunc", ("dq", "dk")), (ragged, "no_q_tail_zero", ("dk", "dv")), (ragged, "ds_multiplied_not_selected", ("dk",)),
+                             (stat, "dk_without_scale", ("dk",)), (stat, "delta_of_next_head", ("dq", "dk"))):
+        good, _ = _attn_bwd_check(am, c)
+        assert all(isinstance(r, tuple) for r in good.values()), good
+        bad, got = _attn_bwd_check(am, c, mutant)
+        for nm in where:
+            assert isinstance(bad[nm], str), f"{mutant} passed the {nm} check of {c.id}: {bad}"
+        print(f"[parity] attention mutant {mutant} ({c.id}): caught - {bad[where[0]][:150]}")
+        if mutant == "ds_multiplied_not_selected":
+            assert not bool(torch.isfinite(got["dk"][-1, -1].float()).all()) and bool(torch.isfinite(got["dk"][0, 0].float()).all())
+    eq = lambda a, b: all(torch.equal(a[n].view(torch.int16) if a[n].dtype == torch.bfloat16 else a[n], b[n].view(torch.int16) if b[n].dtype == torch.bfloat16 else b[n]) for n in a)
+    for c in (B_(2, 2, 200, 77, 80, "b", "o"), ragged):
+        _, honest = _attn_bwd_check(am, c, None, pad=0.0)
+        assert eq(honest, _attn_bwd_check(am, c, "dq_no_kv_mask", pad=0.0)[1])
+        assert eq(honest, _attn_bwd_check(am, c, "no_q_tail_zero", pad=3.0)[1])
+        assert eq(honest, _attn_bwd_check(am, c, "ds_multiplied_not_selected", pad=3.0)[1])
+
+
+def test_attention_backward_reference_agrees_with_autograd():
+    """backward_reference is the file header's formula; on the UNROUNDED float64 forward (o, lse2) it is float64 autograd through
+    softmax(scale q k^T) v, and on the bf16 o / fp32 lse2 a backward case is handed it moves by no more than what those roundings put
+    into delta and P: |d delta| <= sum_d |dO| |o_r - o|, |dP| <= P expm1(ln 2 |lse_r - lse|)."""
+    from tests import attention_matrix as am
+    c = am.BwdCase(2, 2, 100, 77, 80, "b", "o")
+    L = am.make_inputs(c, "cpu", 3)
+    q, k, v, do = (am.heads(L[n]) for n in ("q", "k", "v", "do"))
+    sc = am.f32(c.D ** -0.5)
+    qa, ka, va = (t.double().clone().requires_grad_(True) for t in (q, k, v))
+    (torch.softmax(qa @ ka.transpose(-1, -2) * sc, -1) @ va).backward(do.double())
+    o64, _, l64, _ = am.forward_reference(q, k, v, c.D ** -0.5)
+    exact = am.backward_reference(q, k, v, o64, do, l64, c.D ** -0.5)
+    for nm, g in (("dq", qa.grad), ("dk", ka.grad), ("dv", va.grad)):
+        assert float((exact[nm][0] - g).abs().max()) <= 1e-11 * float(g.abs().max()), nm
+    o_r, l_r = am.forward_for_backward(q, k, v, c.D ** -0.5)
+    given = am.backward_reference(q, k, v, o_r, do, l_r, c.D ** -0.5)
+    p = torch.softmax(q.double() @ k.double().transpose(-1, -2) * sc, -1)
+    dpf = torch.expm1(am.LN2 * (l_r.double() - l64).abs())[..., None]                       # relative change of P
+    x = (do.double() @ v.double().transpose(-1, -2) - (do.double() * o64).sum(-1, keepdim=True)).abs()
+    dd = (do.double().abs() * (o_r.double() - o64).abs()).sum(-1, keepdim=True)
+    e_ds = p * (1 + dpf) * dd + p * dpf * x
+    assert bool(((given["dq"][0] - qa.grad).abs() <= sc * (e_ds @ k.double().abs()) * (1 + 1e-9) + 1e-12).all())
+    assert bool(((given["dk"][0] - ka.grad).abs() <= sc * (e_ds.transpose(-1, -2) @ q.double().abs()) * (1 + 1e-9) + 1e-12).all())
+    assert bool(((given["dv"][0] - va.grad).abs() <= ((p * dpf).transpose(-1, -2) @ do.double().abs()) * (1 + 1e-9) + 1e-12).all())
+    assert float((given["dq"][0] - qa.grad).abs().max()) > 0        # the roundings are there, and accounted for
+
+
+def test_attention_matrix_is_not_hollow():
+    """The kernel names the library returns over the matrix are exactly the 13 forward, 3 dq and 3 dkv instantiations; the sources launch
+    no instantiation this list does not name; for every name some case applies the rounding statistic to each bf16 output (asked of the
+    stand-in); every Tq / Tk edge class is present; nothing in the GPU file is skipped or expected to fail."""
+    from tests import attention_matrix as am
+    fwd = {}
+    for c in am.FWD_CASES:
+        fwd.setdefault(am.fwd_name(c), []).append(c)
+    assert sorted(fwd) == sorted(am.FWD_NAMES) and len(am.FWD_NAMES) == 13, set(fwd) ^ set(am.FWD_NAMES)
+    dq, dkv = {}, {}
+    for c in am.BWD_CASES:
+        a, b = am.bwd_names(c)
+        dq.setdefault(a, []).append(c)
+        if c.need_dkv:
+            dkv.setdefault(b, []).append(c)
+        else:
+            assert b == ""
+    assert sorted(dq) == sorted(am.BWD_DQ_NAMES) and sorted(dkv) == sorted(am.BWD_DKV_NAMES)
+    # the sources: every launch site of an attention kernel goes through slh_launch, and names one of the listed instantiations
+    src = open(os.path.join(ROOT, "sliders_amd", "csrc", "attention.hip")).read()
+    dts = set(re.findall(r"launch_fwd<(\d)>\(", src))
+    inst = {m.replace("DT", dt) for m in re.findall(r"slh_launch<(attn_fwd\w*(?:<[^>]*>)?)>", src) for dt in dts}
+    assert inst == set(am.FWD_NAMES), inst ^ set(am.FWD_NAMES)
+    assert not re.search(r"hipLaunchKernelGGL\(\(?attn_fwd", src)
+    srcb = open(os.path.join(ROOT, "sliders_amd", "csrc", "attention_bwd.hip")).read()
+    assert set(re.findall(r"slh_launch<(attn_bwd_\w+<[^>]*>)>", srcb)) == set(am.BWD_DQ_NAMES + am.BWD_DKV_NAMES)
+    assert not re.search(r"hipLaunchKernelGGL\(\(?attn_bwd", srcb)
+    # the statistic is applied, per name
+    for name, cases in sorted(fwd.items()):
+        for c in sorted((c for c in cases if "c" in c.cls and "g" not in c.cls), key=lambda c: c.B * c.H * c.Tq * c.Tk * c.D):
+            r = _attn_fwd_check(am, c, key_split=name == "attn_fwd_ks_kernel")
+            assert all(isinstance(x, tuple) for x in r.values()), r
+            if r["o"][1] is not None:
+                break
+        else:
+            raise AssertionError(f"{name}: no case of the matrix applies the rounding statistic to o")
+    for names, outs in ((dq, ("dq",)), (dkv, ("dk", "dv"))):
+        for name, cases in sorted(names.items()):
+            for c in sorted((c for c in cases if am.bwd_takes_statistic(c) and not c.chained), key=lambda c: c.Tq * c.Tk * c.D):
+                r, _ = _attn_bwd_check(am, c)
+                assert all(isinstance(x, tuple) for x in r.values()), r
+                if all(r[o][1] is not None for o in outs):
+                    break
+            else:
+                raise AssertionError(f"{name}: no case of the matrix applies the rounding statistic to {outs}")
+    # edges
+    for what, pred in am.TQ_EDGES.items():
+        assert any(pred(c.Tq) for c in am.FWD_CASES), f"no forward case with Tq {what}"
+    for nw in ("4", "2"):
+        for t in (33, 100, 129, 200):
+            assert any(c.Tq % 128 == t % 128 and f"<{nw}," in am.fwd_name(c) for c in am.FWD_CASES), (nw, t)
+    assert set(am.TK_EDGES) <= {c.Tk for c in am.FWD_CASES}, set(am.TK_EDGES) - {c.Tk for c in am.FWD_CASES}
+    ks = fwd["attn_fwd_ks_kernel"]
+    assert {256, 384, 1024} <= {c.Tk for c in ks} and {129, 768} <= {c.Tq // 64 * c.H * c.B for c in ks} and any(c.Tq % 128 == 64 for c in ks)
+    assert any(c.pack == "qkv" for c in am.FWD_CASES) and any(c.ldo_pad for c in am.FWD_CASES) and any(c.vt_extra for c in am.FWD_CASES)
+    assert any(c.pf for c in ks) and any("g" in c.cls and c.Tk % 64 for c in am.FWD_CASES)
+    assert {ch for c in am.FWD_CASES for ch in c.cls} == set(am.INPUT_CLASSES)
+    for name in am.BWD_DQ_NAMES:
+        cs = [c for c in dq[name] if not c.chained]
+        assert any(c.B > 1 and c.H > 1 and c.Tq >= 1024 and c.Tk >= 1024 and c.need_dkv for c in cs), name
+        assert any(c.Tq % 64 and c.need_dkv for c in cs) and any(c.Tk % 64 and not c.need_dkv for c in cs), name
+        assert any(c.pack == "qkv" for c in cs) and any(c.chained for c in dq[name]), name
+    assert any(c.Tk % 64 and c.need_dkv for c in am.BWD_CASES) and {"n", "o"} <= {c.do_cls for c in am.BWD_CASES}
+    gpu = open(os.path.join(ROOT, "tests", "test_attention_matrix_gpu.py")).read()
+    assert "skip" not in gpu and "xfail" not in gpu
