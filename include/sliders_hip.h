@@ -429,6 +429,29 @@ typedef struct slh_cfg_ddim_desc {
 } slh_cfg_ddim_desc;
 int slh_cfg_ddim(const slh_cfg_ddim_desc* d, slh_stream_t stream);
 
+/* One step of the residual DDPM noise space that edits a given image (sliders_amd/edit.py, docs/EDIT.md): CFG combine, the DDIM
+ * mean mu of x_{t-1} (the formulas of slh_cfg_ddim, but fp32 throughout on an fp32 master latent, one rounding per operation, no
+ * contraction), then
+ *   mode 0 (invert): resid = target - mu is written;   mode 1 (edit): resid is read;   both: out = mu + resid.
+ * mu is computed ahead of the mode branch, so an edit over the same epsilon and the inversion's residuals reproduces the
+ * inversion's `out` bit for bit.  The bf16 copies are the round-to-nearest-even of out. */
+typedef struct slh_ddpm_edit_desc {
+    const void* eps;         /* bf16 [2*nb][chw], uncond half first */
+    const void* eps_text;    /* optional, as slh_cfg_ddim_desc */
+    const float* x;          /* fp32 [nb][chw] master latent x_t */
+    const float* target;     /* mode 0: x_{t-1} of the constructed path (x0 on the last step); mode 1: unused, may be NULL */
+    float* resid;            /* fp32 [nb][chw]; mode 0: written, mode 1: read */
+    float* out;              /* fp32 x_{t-1}; may alias x */
+    void* out_bf16; void* out2_bf16;   /* optional bf16 copies of out: the two halves of the CFG pair's sample input */
+    int32_t nb, chw;
+    float guidance;
+    float c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev;
+    float c_dir;             /* sqrt(1 - alpha_prev - sigma^2): the noise sigma z of a DDPM step is part of resid */
+    int32_t mode;            /* 0 invert, 1 edit */
+    int32_t v_prediction;    /* as slh_cfg_ddim_desc (c_sqrt_alpha_t is read only then) */
+} slh_ddpm_edit_desc;
+int slh_ddpm_edit_step(const slh_ddpm_edit_desc* d, slh_stream_t stream);
+
 /* guidance loss (prompt_util.py:108-148): loss = mean((target - (neutral +- gs*(positive-uncond)))^2);
  * writes loss (fp32 scalar, atomically accumulated: zero it first) and d(loss)/d(target) (bf16). */
 typedef struct slh_loss_desc {
@@ -657,7 +680,7 @@ enum {
     SLH_OP_VAE_CONV_IN = 27, SLH_OP_VAE_MOMENTS = 28, SLH_OP_VAE_SAMPLE = 29, SLH_OP_VAE_POST_QUANT = 30, SLH_OP_LION = 31,
     SLH_OP_WGRAD_BATCH = 32, SLH_OP_TRANSPOSE_BATCH = 33, SLH_OP_GATHER16 = 34, SLH_OP_GN_FUSED = 35,
     SLH_OP_LORA_LN_FOLD = 36,     /* 37 was SLH_OP_PREFETCH (side-stream weight touch: measured slower, removed in round 5) */
-    SLH_OP_LORA_MERGE = 38
+    SLH_OP_LORA_MERGE = 38, SLH_OP_DDPM_EDIT = 39
 };
 /* SLH_OP_MEMSET: byte fill by a kernel of this library (not hipMemsetAsync: a captured memset node is a runtime blit whose
  * replays were observed to go wrong on the legacy default stream - see the executor's comment) */

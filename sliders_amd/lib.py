@@ -70,6 +70,9 @@ CfgDdimDesc = _struct("CfgDdimDesc", _ptrs("eps", "x", "out", "out2", "eps_text"
                       + [("guidance", c_f32), ("c_sqrt_beta_t", c_f32), ("c_inv_sqrt_alpha_t", c_f32),
                          ("c_sqrt_alpha_prev", c_f32), ("c_dir", c_f32)] + _ints("do_step", "v_prediction")
                       + [("c_sqrt_alpha_t", c_f32)] + _ints("pad_"))
+DdpmEditDesc = _struct("DdpmEditDesc", _ptrs("eps", "eps_text", "x", "target", "resid", "out", "out_bf16", "out2_bf16") + _ints("nb", "chw")
+                       + [(n, c_f32) for n in ("guidance", "c_sqrt_beta_t", "c_inv_sqrt_alpha_t", "c_sqrt_alpha_t", "c_sqrt_alpha_prev", "c_dir")]
+                       + _ints("mode", "v_prediction"))
 LossDesc = _struct("LossDesc", _ptrs("target", "positive", "neutral", "uncond", "loss", "dtarget", "dtarget_pix")
                    + _ints("n") + [("guidance", c_f32)] + _ints("erase", "hw", "nch"))
 WgradDesc = _struct("WgradDesc", _ptrs("z0", "z1", "v", "out", "scale")
@@ -109,7 +112,7 @@ VaeSampleDesc = _struct("VaeSampleDesc", _ptrs("moments", "post_noise", "noise",
 _SIZE_ORDER = [GemmDesc, SkinnyDesc, GemvDesc, GnDesc, GnBwdDesc, LnDesc, LnBwdDesc, AttnDesc, TransposeDesc,
                AttnBwdDesc, TembedDesc, ConvInDesc, EwDesc, CfgDdimDesc, LossDesc, WgradDesc, AdamwDesc, MemsetDesc,
                LoraCdgradDesc, TembLoraBwdDesc, SgemmDesc, Gn32Desc, Softmax32Desc, VaeConvDesc, VaeSampleDesc, LionDesc,
-               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc]
+               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc, DdpmEditDesc]
 
 # opcodes (enum in sliders_hip.h)
 OP_GEMM, OP_SKINNY, OP_GEMV, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTN_FWD, OP_TRANSPOSE_HEADS = range(1, 9)
@@ -121,6 +124,7 @@ OP_LION = 31
 OP_WGRAD_BATCH, OP_TRANSPOSE_BATCH, OP_GATHER16, OP_GN_FUSED = 32, 33, 34, 35
 OP_LORA_LN_FOLD = 36
 OP_LORA_MERGE = 38
+OP_DDPM_EDIT = 39
 
 EW_COPY, EW_ADD, EW_GEGLU_FWD, EW_GEGLU_BWD, EW_UPSAMPLE_BWD, EW_COLSUM = range(6)
 
@@ -143,6 +147,7 @@ _ENTRY = {
     OP_WGRAD_BATCH: ("slh_lora_wgrad_batch", BatchDesc), OP_TRANSPOSE_BATCH: ("slh_transpose_heads_batch", BatchDesc),
     OP_GATHER16: ("slh_gather16", Gather16Desc), OP_GN_FUSED: ("slh_gn_fused", GnDesc),
     OP_LORA_LN_FOLD: ("slh_lora_ln_fold", LoraLnFoldDesc), OP_LORA_MERGE: ("slh_lora_merge", LoraMergeDesc),
+    OP_DDPM_EDIT: ("slh_ddpm_edit_step", DdpmEditDesc),
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
