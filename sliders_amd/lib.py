@@ -415,19 +415,6 @@ class Program:
         except Exception:
             pass
 
-    def mark(self) -> int:
-        """Number of recorded ops; truncate(mark) forgets everything recorded since (planner rollbacks)."""
-        return self.n_ops
-
-    def truncate(self, n: int):
-        if n >= self.n_ops:
-            return
-        del self._chunks[n:], self.op_names[n:], self.ops[n:]
-        self.n_ops = n
-        self._buf = None
-        if self._graphs:
-            self._drop_graphs()
-
     def add(self, opcode: int, desc, name: str = ""):
         raw = bytes(desc)
         pad = (-len(raw)) % 8

@@ -15,7 +15,7 @@ unfused so its pre-activation is available; `build_backward()` then emits the ba
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import Dict, List, Optional, Tuple, Union
 
 import torch
@@ -40,6 +40,8 @@ class Act:
     buf: Optional[Buf] = None
     name: str = ""
     ln: Optional[tuple] = None     # (Buf of per-row 64-column chunk statistics written by the producing GEMM, chunks): folded LayerNorm
+    vt: Optional[tuple] = None     # q|k|v projection whose epilogue also stored V head-transposed: (pointer, 0) as attention()'s vt_pre
+    attended: bool = False         # attn2.to_q whose epilogue ran the cross-attention: this IS the attention output
 
     @property
     def HW(self) -> int:
@@ -65,14 +67,64 @@ class Act:
 
 Src = Union[Act, Tuple[Act, Act]]
 
+PH = 0x1000                      # placeholder for a pointer _emit fills in (aligned like every arena buffer: the tile rule looks)
+
+
+@dataclass
+class Product:
+    """One slh_gemm launch as UNetPlan._decide settled it.  d says the rest: d.vt_out - V^T / dO^T is stored, d.xa_k - the
+    cross-attention rides in the epilogue, d.tile, d.ln_in."""
+    d: "lib.GemmDesc"              # complete but for the pointers of what _emit allocates: output, T, statistics, V^T (placeholders)
+    ln_cols: int                   # chunk width of the row statistics left for a folded LayerNorm (0: none)
+    fused: bool                    # the adapter's down-projection runs inside the launch
+    x: Src
+    geglu_pre: Optional[Act]
+    ln_norm: Optional[str]         # LayerNorm folded into the adapter's down-projection as well
+    rec: dict                      # the tape record, `out` and `T` filled in by _emit; rec["grp"] = the adapter group
+
+
 SPLITK_TICKETS = 4096            # 64-bit arrival tickets per plan (one per output tile of the largest split-K product)
+
+
+def _sw(env: str, parse: str = "set"):
+    return field(default=False, metadata=dict(env=env, parse=parse))
+
+
+@dataclass(frozen=True)
+class Switches:
+    """Every environment switch of the planner: A/B knobs of closed experiments, all off by default.  Read once per forward plan
+    (from_env, at the head of UNetPlan.__init__); the BackwardPlan of a plan uses the same copy.  parse: "set" = the variable exists
+    (any value), "truthy" = it is non-empty, "zero" = it is exactly "0"."""
+    no_weight_touch: bool = _sw("SLIDERS_NO_WEIGHT_TOUCH")   # no weight touch from idle workgroup slots: 24.35 / 24.32 ms a pass against 24.18 / 24.09
+    no_attn_touch: bool = _sw("SLIDERS_NO_ATTN_TOUCH")   # the key-split self-attention carries no touch: 23.34 ms against 23.21 / 23.26
+    touch_farthest: bool = _sw("SLIDERS_TOUCH_FARTHEST", "truthy")   # farthest carrier in the window first: 25.05 ms against 24.95 nearest-first
+    lora_unfused: bool = _sw("SLIDERS_LORA_UNFUSED")   # the adapters' down-projection as a launch of its own ahead of every product
+    train_no_ln_fold: bool = _sw("SLIDERS_TRAIN_NO_LN_FOLD")   # training passes keep every LayerNorm launch
+    no_fused_vt: bool = _sw("SLIDERS_NO_FUSED_VT")   # V^T by a transpose launch instead of the q|k|v epilogue
+    train_no_fused_vt: bool = _sw("SLIDERS_TRAIN_NO_FUSED_VT")   # the same for training passes only
+    gn_split_slab: bool = _sw("SLIDERS_GN_ONE", "zero")   # =0: two launches for a GroupNorm over a cache-resident slab: 24.44 / 24.37 ms against 24.32 / 24.40
+    gn_two_launch: bool = _sw("SLIDERS_GN_TWO_LAUNCH")   # two launches for every GroupNorm
+    no_lora_ln_fold: bool = _sw("SLIDERS_NO_LORA_LN_FOLD")   # adapter-carrying q|k|v keeps its LayerNorm launch
+    no_fused_xattn: bool = _sw("SLIDERS_NO_FUSED_XATTN")   # cross-attention as its own launch behind attn2.to_q
+    train_unfused_geglu: bool = _sw("SLIDERS_TRAIN_UNFUSED_GEGLU")   # training forward: GEGLU as an elementwise launch behind ff.net.0.proj
+    train_kv_per_block: bool = _sw("SLIDERS_TRAIN_KV_PER_BLOCK", "truthy")   # training forward: text K/V projected per block (the form of rounds 1-2)
+    bwd_dot_launch: bool = _sw("SLIDERS_BWD_DOT_LAUNCH")   # dO^T of a self-attention by a transpose launch instead of the dgrad epilogue
+    bwd_unfused_geglu: bool = _sw("SLIDERS_BWD_UNFUSED_GEGLU")   # GEGLU backward as an elementwise launch instead of ff.net.2's dgrad epilogue
+    bwd_unbatched: bool = _sw("SLIDERS_BWD_UNBATCHED")   # one launch per head transpose and weight gradient instead of the batched ones
+    wgrad_atomic: bool = _sw("SLIDERS_WGRAD_ATOMIC")   # weight gradients by fp32 atomics (not bit-reproducible) instead of slabs + tickets
+    bwd_unfused_u: bool = _sw("SLIDERS_BWD_UNFUSED_U")   # U = dY . B as skinny launches instead of inside the dgrad product
+
+    @classmethod
+    def from_env(cls) -> "Switches":
+        read = {"set": lambda v: v is not None, "truthy": bool, "zero": lambda v: v == "0"}
+        return cls(**{f.name: read[f.metadata["parse"]](os.environ.get(f.metadata["env"])) for f in fields(cls)})
 
 
 def _plan_tickets(plan, n: int) -> int:
     """The arrival tickets of a plan's split-K products: ONE array per plan - every launch leaves its tickets zero and the
     launches of a plan are ordered on one stream.  Lives in the zero-init arena (zeroed at the head of the program)."""
     assert n <= SPLITK_TICKETS, f"split-K product with {n} output tiles"
-    if getattr(plan, "_splitk_tickets", None) is None:
+    if plan._splitk_tickets is None:
         plan._splitk_tickets = plan.zarena.alloc((2 * SPLITK_TICKETS,), torch.float32, "splitk.tickets")
     return plan._splitk_tickets.ptr
 
@@ -102,44 +154,44 @@ PREFETCH_MAX_BYTES = 96 << 20
 TOUCH_WINDOW = 6      # ops a weight touch may ride ahead of the product that needs the weights
 
 
-def attach_weight_touch(prog: "lib.Program") -> "lib.Program":
+def attach_weight_touch(ops: List[tuple], sw: Switches):
     """The product path's weight prefetch (slh_gemm_desc.pf_*): every GEMM whose packed weights are 6-96 MB (GEGLU.proj 26 MB,
     ff.net.2 13 MB, q|k|v 10 MB at the 1280-channel level) has those bytes touched by the idle workgroup slots of an EARLIER
     launch that leaves >= 64 CUs free - the 160-tile products on the 128 x 128 ring tile (attention out-projections, attn2.to_q,
     ff.net.2 itself) - or, round 6, of the key-split self-attention launch (slh_attn_desc.pf_*: three workgroups per CU, 640 of 768
     slots taken) - the nearest such carrier within TOUCH_WINDOW ops that does not carry a touch yet.  No extra launch, no
-    second stream.  SLIDERS_NO_WEIGHT_TOUCH=1 returns the program unchanged."""
-    if os.environ.get("SLIDERS_NO_WEIGHT_TOUCH") is not None:
-        return prog
-    ops = list(prog.ops)
+    second stream.  ops = the (opcode, descriptor, name) list of a plan, before it is serialised: the carriers' pf_* are set in place."""
+    if sw.no_weight_touch:
+        return
 
-    def carrier(o, d):
+    def carrier(o, d, _):
         if o == lib.OP_ATTN_FWD:          # round 6: the key-split self-attention of the 32 x 32 level (its workgroups leave a slot per CU)
-            return os.environ.get("SLIDERS_NO_ATTN_TOUCH") is None and lib.attn_carries_touch(d)
+            return not sw.no_attn_touch and lib.attn_carries_touch(d)
         if o != lib.OP_GEMM or d.mode != 0 or d.tile != TILE_RING:
             return False
         return ((d.M + 127) // 128) * ((d.N + 127) // 128) <= 192
     used = set()
-    for i, (o, d) in enumerate(ops):
+    for i, (o, d, _) in enumerate(ops):
         if o != lib.OP_GEMM or d.w_layout != 1:
             continue
         nb = (d.N + 63) // 64 * 64 * d.K * 2
         if not (PREFETCH_MIN_BYTES <= nb <= PREFETCH_MAX_BYTES):
             continue
         cand = reversed(range(max(0, i - TOUCH_WINDOW), i))     # nearest first (measured: 24.95 ms against 25.05 farthest-first, 25.27 without)
-        if os.environ.get("SLIDERS_TOUCH_FARTHEST"):
+        if sw.touch_farthest:
             cand = range(max(0, i - TOUCH_WINDOW), i)
         for j in cand:
             if j not in used and carrier(*ops[j]):
                 ops[j][1].pf_ptr, ops[j][1].pf_bytes = d.w, nb
                 used.add(j)
                 break
-    if not used:
-        return prog
-    out = lib.Program()
-    for (o, d), nm in zip(ops, prog.op_names):
-        out.add(o, d, nm)
-    return out
+
+
+def _program(ops) -> "lib.Program":
+    prog = lib.Program()
+    for o, d, nm in ops:
+        prog.add(o, d, nm)
+    return prog
 
 
 def _src_parts(x: Src):
@@ -160,24 +212,27 @@ class UNetPlan:
         self.mode = mode
         self.train = mode == "train"
         self.lora_scale_ptr = lora_scale_ptr
-        self.prog = lib.Program()
+        self.sw = Switches.from_env()
+        self.ops: List[tuple] = []                # (opcode, descriptor, name) in launch order; serialised once, below
         self.tape: List[dict] = []
         self.lnfold_items: List[tuple] = []       # adapter sides of LayerNorm folds (slh_lora_lnfold_item as int64 words)
+        self._splitk_tickets = None
         self.zmark = zarena.mark()
         self._build_io(io)
         self._forward()
         self.zend = zarena.mark()
         # zero the fp32 accumulators (GroupNorm statistics ...) used by this program first
-        head = lib.Program()
+        head = []
         if self.zend > self.zmark:
             p, n = zarena.region(self.zmark, self.zend)
-            head.memset(p, n, 0, "zero_stats")
+            head.append((lib.OP_MEMSET, lib.MemsetDesc(ptr=p, nbytes=n, value=0, pad=0), "zero_stats"))
         if self.lnfold_items:
             self._lnfold_table = torch.tensor(self.lnfold_items, dtype=torch.int64, device=self.lora.params.device)
-            head.add(lib.OP_LORA_LN_FOLD, lib.LoraLnFoldDesc(items=self._lnfold_table.data_ptr(), n=len(self.lnfold_items)),
-                     "lora_ln_fold")
-        head.extend(self.prog)
-        self.prog = attach_weight_touch(head)
+            head.append((lib.OP_LORA_LN_FOLD, lib.LoraLnFoldDesc(items=self._lnfold_table.data_ptr(), n=len(self.lnfold_items)),
+                         "lora_ln_fold"))
+        self.ops = head + self.ops
+        attach_weight_touch(self.ops, self.sw)
+        self.prog = _program(self.ops)
         # The text K/V of every cross-attention block depend only on the prompt embeddings (and frozen weights): inside a
         # denoise loop (train_util.py:263-294: same embeddings for every timestep) steps 2.. replay the pass without
         # the batched K/V projection and its head transpose.  Valid only while no other plan ran in between (plans
@@ -185,11 +240,10 @@ class UNetPlan:
         self.prog_text_cached = None
         if self.kv_all is not None:
             skip = {"attn2_kv_all", "attn2_vt_all", "lora_ln_fold"}     # (the adapters do not change inside a denoise loop either)
-            pc = lib.Program()
-            for (op, d), nm in zip(self.prog.ops, self.prog.op_names):
-                if nm not in skip:
-                    pc.add(op, d, nm)
-            self.prog_text_cached = pc
+            self.prog_text_cached = _program(op for op in self.ops if op[2] not in skip)
+
+    def add(self, opcode: int, desc, name: str):
+        self.ops.append((opcode, desc, name))
 
     # ------------------------------------------------------------------------------------------------
     # buffers
@@ -250,37 +304,45 @@ class UNetPlan:
             self._conv_fields(d, x0, conv, Ho, Wo)
         else:
             d.stride = 1
-        self.prog.add(lib.OP_SKINNY, d, name)
+        self.add(lib.OP_SKINNY, d, name)
         return out
 
-    def gemm(self, x: Src, wname: str, N: int, name: str, bias: bool = True, conv: Optional[dict] = None,
-             rowbias: Optional[Tuple[int, int]] = None, residual: Optional[Act] = None,
-             lora_paths: Optional[List[str]] = None, geglu: bool = False, out: Optional[Act] = None,
-             w_ptr: Optional[int] = None, bias_ptr: Optional[int] = None, vt_heads: Optional[int] = None,
-             ln_stats: bool = False, ln_fold: Optional[Act] = None, geglu_pre: Optional[Act] = None,
-             ln_mr: Optional[Buf] = None, tape_x: Optional[Act] = None, geglu16: bool = False,
-             xattn: Optional[dict] = None, ln_norm: Optional[str] = None) -> Optional[Act]:
-        """y = x . W^T (+bias)(+rowbias per sample)(+LoRA)(+residual).  conv: {'stride','xform'} for 3x3.
-        vt_heads: the product is a fused q|k|v projection of that many heads; where the kernel supports it (no-grad
-        passes, head_dim % 64 == 0) its V third is written head-transposed for slh_attn_fwd straight from the epilogue
-        and self.last_vt = (pointer, 0) names it - one launch and one HBM round trip of V less per self-attention.
-        ln_stats: also leave per-row statistics of the result for a LayerNorm folded into the NEXT product (out.ln, set only
-        when the tile that will run supports it).  ln_fold = the un-normalised activation x whose producer left such
-        statistics: this product computes Linear(LayerNorm(x)) from x itself with the gamma-scaled copy of the weights
-        (weights.py _put_ln_folded); returns None - nothing emitted - when the tile that would run cannot (split-K).
+    def gemm(self, x: Src, wname: str, N: int, name: str, **kw) -> Act:
+        """y = x . W^T (+bias)(+rowbias per sample)(+LoRA)(+residual): decide the product's form, then allocate and record it (the
+        keywords are _decide's).  A product that folds a LayerNorm may be refused and goes through ln_gemm instead."""
+        p = self._decide(x, wname, N, name, **kw)
+        assert p is not None, f"{name}: no tile takes this product"
+        return self._emit(p)
+
+    def _decide(self, x: Src, wname: str, N: int, name: str, bias: bool = True, conv: Optional[dict] = None,
+                rowbias: Optional[Tuple[int, int]] = None, residual: Optional[Act] = None,
+                lora_paths: Optional[List[str]] = None, geglu: bool = False, vt_heads: Optional[int] = None,
+                ln_stats: bool = False, ln_fold: Optional[Act] = None, geglu_pre: Optional[Act] = None,
+                ln_mr: bool = False, geglu16: bool = False, xattn: Optional[dict] = None,
+                ln_norm: Optional[str] = None) -> Optional[Product]:
+        """The form of one product, settled before anything is allocated or recorded: builds the descriptor - placeholder pointers
+        (PH, 8, 16) for what _emit will allocate - and asks choose_tile.  Touches no arena, no tape, no list of the plan.  Returns None
+        when the LayerNorm it was asked to fold (ln_fold) cannot be folded on the tile that would run: the caller (ln_gemm) then
+        records the LayerNorm launch and the plain product.
+        conv: {'stride','xform'} for 3x3.
+        vt_heads: the product is a fused q|k|v projection of that many heads; where the kernel supports it (head_dim % 64 == 0) its
+        V third is written head-transposed for slh_attn_fwd straight from the epilogue (Product.d.vt_out; the returned
+        activation's .vt names the buffer) - one launch and one HBM round trip of V less per self-attention.
+        ln_stats: also leave per-row statistics of the result for a LayerNorm folded into the NEXT product (the returned
+        activation's .ln, only when the tile that will run supports it).  ln_fold = the un-normalised activation x whose producer
+        left such statistics: this product computes Linear(LayerNorm(x)) from x itself with the gamma-scaled copy of the weights
+        (weights.py _put_ln_folded).
         Training passes: geglu_pre receives proj(x) itself next to the GEGLU output (the backward's pre-activation; the tape
-        records this product with it as its output), ln_mr the rows' (mean, rstd) of a folded LayerNorm, and tape_x stands
-        in for the normalised tensor that was never written (a key for the gradient chain: nothing reads its memory).
+        records this product with it as its output); ln_mr: the product also leaves the rows' (mean, rstd) of the folded LayerNorm
+        (the caller allocates the buffer once the fold is accepted).
         xattn = {k, vt_ptr, vt_heads, Tk, Tq, scale}: the product is attn2.to_q and, when the tile that runs is the 128 x 128 ring
         tile, the cross-attention behind it happens in its epilogue (slh_gemm_desc.xa_*): the returned activation is then the
-        attention output and self.xattn_done says so.
+        attention output (.attended).
         ln_fold together with lora_paths (ln_norm = the LayerNorm's weight name): the adapter's down-projection is folded as well
         (slh_gemm_desc.ln_lora_*; A . gamma and its row sums / offsets are rebuilt from the live parameters by ONE
         slh_lora_ln_fold launch at the head of the program) - only on the ping-pong tiles; None when another tile would run."""
-        self.xattn_done = False
         x0, x1 = _src_parts(x)
         cin = x0.C + (x1.C if x1 else 0)
-        B = x0.B
         if conv is not None:
             sh = 1 if conv.get("xform", 0) else 0
             HL, WL = x0.H << sh, x0.W << sh
@@ -289,56 +351,44 @@ class UNetPlan:
             K = 9 * cin
         else:
             Ho, Wo, K = x0.H, x0.W, cin
-        M = B * Ho * Wo
-        Nout = N // 2 if geglu else N
-        if out is None:
-            out = self.act(B, Ho, Wo, Nout, name)
+        M = x0.B * Ho * Wo
         grp = self._lora_group(lora_paths) if lora_paths else None
-        T = None
-        fused = grp is not None and os.environ.get("SLIDERS_LORA_UNFUSED") is None
-        if grp is not None:
-            R = sum(e.target.rank for e in grp)
-            if fused:
-                # lora_down rides inside the GEMM (third operand tile); T is only written out for the backward
-                T = self.f32((M, R), name + ".T") if self.train else None
-            else:
-                T = self.skinny(x, self.lora.down_ptr(grp[0]), R, K, conv, M, Ho, Wo, name + ".lora_down")
+        fused = grp is not None and not self.sw.lora_unfused       # lora_down rides inside the GEMM (third operand tile)
+        if ln_fold is not None and grp is not None and (not fused or ln_norm is None):
+            return None                       # (the adapter's fold needs the fused adapter and the LayerNorm's parameters)
         sfx = "16" if geglu16 else ""      # GEGLU.proj in the 16 | 16 block order (slh_gemm_desc.geglu = 3)
         assert not geglu16 or (geglu and geglu_pre is None and not lora_paths)
-        d = lib.GemmDesc(a0=x0.ptr, a1=x1.ptr if x1 else 0,
-                         w=w_ptr if w_ptr is not None else self.w.ptr(wname + ".w" + sfx),
-                         bias=(bias_ptr if bias_ptr is not None else (self.w.ptr(wname + ".b" + sfx) if bias else 0)),
+        fold = ln_fold is not None
+        d = lib.GemmDesc(a0=x0.ptr, a1=x1.ptr if x1 else 0, w=self.w.ptr(wname + (".lnw" if fold else ".w") + sfx),
+                         bias=self.w.ptr(wname + ".b" + sfx) if (bias and not fold) else 0,
                          rowbias=rowbias[0] if rowbias else 0,
-                         lora_t=T.ptr if (T and not fused) else 0, lora_up=self.lora.up_ptr(grp[0]) if grp else 0,
+                         lora_t=PH if (grp is not None and not fused) else 0, lora_up=self.lora.up_ptr(grp[0]) if grp else 0,
                          lora_down=self.lora.down_ptr(grp[0]) if fused else 0,
-                         lora_t_out=T.ptr if (T and fused and self.train) else 0,
+                         lora_t_out=PH if (fused and self.train) else 0,      # (T is only written out for the backward)
                          lora_rank=(4 * len(grp)) if fused else 0,
                          lora_scale=self.lora_scale_ptr if grp else 0,
-                         residual=residual.ptr if residual else 0, c=out.ptr,
+                         residual=residual.ptr if residual else 0, c=PH,
                          lda0=x0.ld, lda1=x1.ld if x1 else 0, ca0=x0.C, ca1=x1.C if x1 else 0,
                          mode=0, stride=1, ldw=K, M=M, N=N, K=K,
                          ld_rowbias=rowbias[1] if rowbias else 0, rows_per_sample=Ho * Wo,
                          ld_t=(4 * len(grp)) if grp else 0, lora_groups=len(grp) if grp else 0,
-                         ld_res=residual.ld if residual else 0, ldc=out.ld, geglu=(3 if geglu16 else 1) if geglu else 0, tile=0,
-                         w_layout=1 if (w_ptr is None and self.w.packed) else 0)
+                         ld_res=residual.ld if residual else 0, ldc=N // 2 if geglu else N,
+                         geglu=(3 if geglu16 else 1) if geglu else 0, tile=0,
+                         w_layout=1 if self.w.packed else 0)
         if conv is not None:
             self._conv_fields(d, x0, conv, Ho, Wo)
-        if ln_fold is not None:
-            if grp is not None and (not fused or ln_norm is None):
-                return None                       # (the adapter's fold needs the fused adapter and the LayerNorm's parameters)
-            d.w, d.bias = self.w.ptr(wname + ".lnw" + sfx), 0
+        if fold:
             d.ln_in, d.ln_in_chunks, d.ln_eps = ln_fold.ln[0].ptr, ln_fold.ln[1], 1e-5
             d.ln_s, d.ln_b = self.w.ptr(wname + ".lns" + sfx), self.w.ptr(wname + ".lnb" + sfx)
-            if ln_mr is not None:
-                d.ln_mr_out = ln_mr.ptr
+            if ln_mr:
+                d.ln_mr_out = PH
         if geglu_pre is not None:
             assert geglu and geglu_pre.C == N
             d.geglu_pre, d.ld_pre = geglu_pre.ptr, geglu_pre.ld
-        train_fold = self.train and os.environ.get("SLIDERS_TRAIN_NO_LN_FOLD") is None
-        want_ln_out = bool(ln_stats and (not self.train or train_fold) and not geglu and N % 64 == 0)
+        want_ln_out = bool(ln_stats and (not self.train or not self.sw.train_no_ln_fold) and not geglu and N % 64 == 0)
         vt = None
-        if vt_heads and not geglu and conv is None and os.environ.get("SLIDERS_NO_FUSED_VT") is None and \
-                (not self.train or os.environ.get("SLIDERS_TRAIN_NO_FUSED_VT") is None):
+        if vt_heads and not geglu and conv is None and not self.sw.no_fused_vt and \
+                (not self.train or not self.sw.train_no_fused_vt):
             Cq = N // 3
             Dh, Tk = Cq // vt_heads, Ho * Wo
             if Dh % 64 == 0 and (2 * Cq) % 128 == 0 and Tk % 64 == 0:
@@ -352,29 +402,49 @@ class UNetPlan:
         ln_cols = choose_tile(d, ln_out=want_ln_out, vt=vt, xa=xa)
         if ln_cols is None:
             return None
-        self.xattn_done = bool(d.xa_k)
-        if ln_fold is not None and grp is not None:
+        rec = dict(op="gemm", x=x, out=None, wname=wname, N=N, K=K, conv=conv, grp=grp, T=None, residual=residual, rowbias=rowbias,
+                   name=name, Ho=Ho, Wo=Wo)
+        return Product(d, ln_cols, fused, x, geglu_pre, ln_norm, rec)
+
+    def _emit(self, p: Product) -> Act:
+        """Allocate what the product settled by _decide needs, fill in the real pointers, record the launch and its tape record.  The
+        order of the allocations is part of the plan (addresses): output; T (unfused adapter: T, then the down-projection's launch);
+        the folded adapter's A . gamma and sums; split-K workspace; statistics chunks; V^T."""
+        d, rec = p.d, p.rec
+        name, grp, M, N, K, Ho, Wo = rec["name"], rec["grp"], d.M, d.N, d.K, rec["Ho"], rec["Wo"]
+        B = _src_parts(p.x)[0].B
+        out = self.act(B, Ho, Wo, d.ldc, name)
+        d.c = out.ptr
+        T = None
+        if grp is not None:
+            R = sum(e.target.rank for e in grp)
+            if not p.fused:
+                T = self.skinny(p.x, self.lora.down_ptr(grp[0]), R, K, rec["conv"], M, Ho, Wo, name + ".lora_down")
+                d.lora_t = T.ptr
+            elif self.train:
+                T = self.f32((M, R), name + ".T")
+                d.lora_t_out = T.ptr
+        if d.ln_in and grp is not None:
             R = 4 * len(grp)
             a2 = self.arena.alloc((R, K), torch.bfloat16, name + ".lnA")
             sc = self.f32((2, 16), name + ".lnA_sc")
             d.lora_down, d.ln_lora_s, d.ln_lora_c = a2.ptr, sc.ptr, sc.ptr + 64
-            self.lnfold_items.append((self.lora.down_ptr(grp[0]), self.w.ptr(ln_norm + ".g"), self.w.ptr(ln_norm + ".b"),
+            self.lnfold_items.append((self.lora.down_ptr(grp[0]), self.w.ptr(p.ln_norm + ".g"), self.w.ptr(p.ln_norm + ".b"),
                                       a2.ptr, sc.ptr, sc.ptr + 64, R | (K << 32)))
         provision_splitk(self, d, name)
-        if ln_cols:
-            st = self.f32((N // ln_cols, M, 2), name + ".ln_chunks")
+        if p.ln_cols:
+            st = self.f32((N // p.ln_cols, M, 2), name + ".ln_chunks")
             d.ln_out = st.ptr
-            out.ln = (st, N // ln_cols)
-        self.last_vt = None
+            out.ln = (st, N // p.ln_cols)
         if d.vt_out:
-            vtb = self.arena.alloc((B, vt_heads, d.vt_D, d.vt_tokens), torch.bfloat16, name + ".vt")
+            vtb = self.arena.alloc((B, d.vt_heads, d.vt_D, d.vt_tokens), torch.bfloat16, name + ".vt")
             d.vt_out = vtb.ptr
-            self.last_vt = (vtb.ptr, 0)
-        self.prog.add(lib.OP_GEMM, d, name)
+            out.vt = (vtb.ptr, 0)
+        out.attended = bool(d.xa_k)
+        self.add(lib.OP_GEMM, d, name)
         if self.train:
-            self.tape.append(dict(op="gemm", x=tape_x if tape_x is not None else x,
-                                  out=geglu_pre if geglu_pre is not None else out, wname=wname, N=N, K=K, conv=conv, grp=grp,
-                                  T=T, residual=residual, rowbias=rowbias, name=name, Ho=Ho, Wo=Wo))
+            rec["out"], rec["T"] = p.geglu_pre if p.geglu_pre is not None else out, T
+            self.tape.append(rec)
         return out
 
     def groupnorm(self, x: Src, wname: str, eps: float, act: int, name: str) -> Act:
@@ -393,13 +463,13 @@ class UNetPlan:
                        stats=stats.ptr, y=y.ptr, ldx0=x0.ld, ldx1=x1.ld if x1 else 0, c0=x0.C, c1=x1.C if x1 else 0,
                        batch=B, hw=H * W, groups=G, ldy=y.ld, eps=eps, act=act, partial=part.ptr, ticket=ticket.ptr)
         one = lib.gn_fused_ok(C, H * W, G)      # 1: tiny tensor, one workgroup per group set; 2: cache-resident slab, sibling workgroups
-        if one == 2 and os.environ.get("SLIDERS_GN_ONE", "1") == "0":
+        if one == 2 and self.sw.gn_split_slab:
             one = 0
-        if one and os.environ.get("SLIDERS_GN_TWO_LAUNCH") is None:
-            self.prog.add(lib.OP_GN_FUSED, d, name + ".fused")
+        if one and not self.sw.gn_two_launch:
+            self.add(lib.OP_GN_FUSED, d, name + ".fused")
         else:
-            self.prog.add(lib.OP_GN_STATS, d, name + ".stats")
-            self.prog.add(lib.OP_GN_APPLY, d, name + ".apply")
+            self.add(lib.OP_GN_STATS, d, name + ".stats")
+            self.add(lib.OP_GN_APPLY, d, name + ".apply")
         if self.train:
             self.tape.append(dict(op="gn", x=x, out=y, wname=wname, eps=eps, act=act, stats=stats, name=name))
         return y
@@ -409,7 +479,7 @@ class UNetPlan:
         mr = self.f32((x.M, 2), name + ".mean_rstd") if self.train else None
         d = lib.LnDesc(x=x.ptr, gamma=self.w.ptr(wname + ".g"), beta=self.w.ptr(wname + ".b"), y=y.ptr,
                        mean_rstd=mr.ptr if mr else 0, M=x.M, C=x.C, ldx=x.ld, ldy=y.ld, eps=1e-5)
-        self.prog.add(lib.OP_LAYERNORM, d, name)
+        self.add(lib.OP_LAYERNORM, d, name)
         if self.train:
             self.tape.append(dict(op="ln", x=x, out=y, wname=wname, mr=mr, name=name))
         return y
@@ -417,48 +487,31 @@ class UNetPlan:
     def ln_gemm(self, h: Act, norm: str, wname: str, N: int, bias: bool = True, lora_paths: Optional[List[str]] = None,
                 geglu: bool = False, vt_heads: Optional[int] = None, geglu_pre: Optional[Act] = None, geglu16: bool = False,
                 xattn: Optional[dict] = None) -> Act:
-        """Linear(LayerNorm(h)): folded into one product when h's producer left row statistics, the consumer carries no adapter
-        and the pass keeps no tape; the LayerNorm launch + the plain product otherwise."""
+        """Linear(LayerNorm(h)): folded into one product when h's producer left row statistics and _decide finds a tile that takes
+        the fold; the LayerNorm launch + the plain product otherwise.  Nothing is allocated or recorded before the fold is settled."""
         grp = self._lora_group(lora_paths) if lora_paths else None
         foldable = h.ln is not None and getattr(self.w, "ln_fold", False) and \
             self.w.has(wname + ".lnw") and h.C % 64 == 0 and h.C <= 1280 and h.ld == h.C
-        if grp is not None and foldable and not self.train and not geglu and os.environ.get("SLIDERS_NO_LORA_LN_FOLD") is None:
-            # adapter-carrying consumer (q|k|v under noxattn): the fold covers the adapter's down-projection too
-            amark, nallocs, nitems = self.arena.mark(), len(self.arena.allocs), len(self.lnfold_items)
-            pmark = self.prog.mark()
-            y = self.gemm(h, wname, N, wname, bias=False, lora_paths=lora_paths, vt_heads=vt_heads, ln_fold=h, ln_norm=norm)
-            if y is not None:
-                return y
-            self.arena.reset(amark)
-            del self.arena.allocs[nallocs:]
-            del self.lnfold_items[nitems:]
-            self.prog.truncate(pmark)             # (an unfused adapter's down-projection may have been recorded ahead of the refusal)
-        if grp is None and foldable:
-            if not self.train:
-                amark, nallocs, pmark = self.arena.mark(), len(self.arena.allocs), self.prog.mark()
-                y = self.gemm(h, wname, N, wname, bias=False, geglu=geglu, vt_heads=vt_heads, ln_fold=h,
-                              geglu16=geglu16 and self.w.has(wname + ".lnw16"), xattn=xattn)
-                if y is not None:
-                    return y
-                self.arena.reset(amark)           # fold refused: the output it had reserved goes back
-                del self.arena.allocs[nallocs:]
-                self.prog.truncate(pmark)
-            elif os.environ.get("SLIDERS_TRAIN_NO_LN_FOLD") is None:
-                # training pass: the same fold; the product also leaves (mean, rstd) per row for the LayerNorm backward, and the
-                # tape keeps the LayerNorm and the product as two records around a stand-in for the normalised tensor
-                amark, nallocs, pmark = self.arena.mark(), len(self.arena.allocs), self.prog.mark()
+        p = None
+        if foldable and grp is not None:
+            if not self.train and not geglu and not self.sw.no_lora_ln_fold:
+                # adapter-carrying consumer (q|k|v under noxattn): the fold covers the adapter's down-projection too
+                p = self._decide(h, wname, N, wname, bias=False, lora_paths=lora_paths, vt_heads=vt_heads, ln_fold=h, ln_norm=norm)
+        elif foldable and not self.train:
+            p = self._decide(h, wname, N, wname, bias=False, geglu=geglu, vt_heads=vt_heads, ln_fold=h,
+                             geglu16=geglu16 and self.w.has(wname + ".lnw16"), xattn=xattn)
+        elif foldable and not self.sw.train_no_ln_fold:
+            # training pass: the same fold; the product also leaves (mean, rstd) per row for the LayerNorm backward, and the
+            # tape keeps the LayerNorm and the product as two records around a stand-in for the normalised tensor (a key for the
+            # gradient chain: nothing reads its memory)
+            p = self._decide(h, wname, N, wname, bias=False, geglu=geglu, ln_fold=h, ln_mr=True, geglu_pre=geglu_pre)
+            if p is not None:
                 mr = self.f32((h.M, 2), norm + ".mean_rstd")
                 stand_in = self.key_act(h.B, h.H, h.W, h.C, norm + ".unwritten")
-                mark = len(self.tape)
                 self.tape.append(dict(op="ln", x=h, out=stand_in, wname=norm, mr=mr, name=norm))
-                y = self.gemm(h, wname, N, wname, bias=False, geglu=geglu, ln_fold=h, ln_mr=mr, tape_x=stand_in,
-                              geglu_pre=geglu_pre)
-                if y is not None:
-                    return y
-                del self.tape[mark:]              # fold refused (split-K tile): give the arena back and drop anything recorded
-                self.arena.reset(amark)
-                del self.arena.allocs[nallocs:]
-                self.prog.truncate(pmark)
+                p.d.ln_mr_out, p.rec["x"] = mr.ptr, stand_in
+        if p is not None:
+            return self._emit(p)
         n = self.layernorm(h, norm, norm)
         return self.gemm(n, wname, N, wname, bias=bias, lora_paths=lora_paths, geglu=geglu, vt_heads=vt_heads,
                          geglu_pre=geglu_pre, geglu16=geglu16 and geglu_pre is None and self.w.has(wname + ".w16"), xattn=xattn)
@@ -473,8 +526,8 @@ class UNetPlan:
         ldt = (Tk + 63) // 64 * 64
         if vt_pre is None:
             vt = self.arena.alloc((B, heads, Dp, ldt), torch.bfloat16, name + ".vt")
-            self.prog.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(src=v.ptr, dst=vt.ptr, B=B, H=heads, T=Tk, ld=v.ld,
-                                                                    ldt=ldt, D=D), name + ".vt")
+            self.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(src=v.ptr, dst=vt.ptr, B=B, H=heads, T=Tk, ld=v.ld,
+                                                               ldt=ldt, D=D), name + ".vt")
             vt_ptr, vt_heads = vt.ptr, 0
         else:
             vt_ptr, vt_heads = vt_pre
@@ -482,7 +535,7 @@ class UNetPlan:
         lse = self.f32((B * heads * Tq + 64,), name + ".lse") if self.train else None   # padded: bwd reads by 64s
         d = lib.AttnDesc(q=q.ptr, k=k.ptr, vt=vt_ptr, o=o.ptr, lse=lse.ptr if lse else 0, B=B, H=heads, Tq=Tq, Tk=Tk,
                          ldq=q.ld, ldk=k.ld, ldvt=ldt, ldo=o.ld, scale=D ** -0.5, D=D, vt_batch_heads=vt_heads)
-        self.prog.add(lib.OP_ATTN_FWD, d, name)
+        self.add(lib.OP_ATTN_FWD, d, name)
         if self.train:
             self.tape.append(dict(op="attn", q=q, k=k, v=v, o=o, lse=lse, Tk=Tk, heads=heads, name=name))
         return o
@@ -496,8 +549,8 @@ class UNetPlan:
         c0 = cfg.block_out_channels[0]
         a = self.arena
         t_in = a.alloc((B, c0), torch.bfloat16, "temb.sin")
-        self.prog.add(lib.OP_TEMBED, lib.TembedDesc(vals=self.io["t"].ptr, out=t_in.ptr, nb=B, n_vals=1, dim=c0,
-                                                    ldo=c0, col0=0), "time_proj")
+        self.add(lib.OP_TEMBED, lib.TembedDesc(vals=self.io["t"].ptr, out=t_in.ptr, nb=B, n_vals=1, dim=c0,
+                                               ldo=c0, col0=0), "time_proj")
         h1 = a.alloc((B, ted), torch.bfloat16, "temb.h1")
         self._gemv(t_in.ptr, c0, "time_embedding.linear_1", ted, c0, h1.ptr, ted, 0, name="time_embedding.linear_1")
         emb = a.alloc((B, ted), torch.bfloat16, "temb.emb")
@@ -505,9 +558,9 @@ class UNetPlan:
         if cfg.is_xl:
             add_in = self.io["add_in"]
             pin = cfg.projection_class_embeddings_input_dim
-            self.prog.add(lib.OP_TEMBED, lib.TembedDesc(vals=self.io["time_ids"].ptr, out=add_in.ptr, nb=B, n_vals=6,
-                                                        dim=cfg.addition_time_embed_dim, ldo=pin,
-                                                        col0=cfg.pooled_dim), "add_time_proj")
+            self.add(lib.OP_TEMBED, lib.TembedDesc(vals=self.io["time_ids"].ptr, out=add_in.ptr, nb=B, n_vals=6,
+                                                   dim=cfg.addition_time_embed_dim, ldo=pin,
+                                                   col0=cfg.pooled_dim), "add_time_proj")
             g1 = a.alloc((B, ted), torch.bfloat16, "aemb.h1")
             self._gemv(add_in.ptr, pin, "add_embedding.linear_1", ted, pin, g1.ptr, ted, 0, name="add_embedding.linear_1")
             emb2 = a.alloc((B, ted), torch.bfloat16, "temb.emb_sum")
@@ -526,7 +579,7 @@ class UNetPlan:
             lt = self.f32((B, 4 * L), "temb.lora_T")
             d = lib.GemvDesc(x=emb.ptr, w=self.lora.params.data_ptr() + 2 * self.lora.temb_down_off, y=lt.ptr,
                              nb=B, N=4 * L, K=ted, ldx=ted, ldy=4 * L, in_act=1, out_f32=1)
-            self.prog.add(lib.OP_GEMV, d, "temb.lora_down")
+            self.add(lib.OP_GEMV, d, "temb.lora_down")
             if not hasattr(self.lora, "temb_tcol"):
                 tcol = torch.empty(tot, dtype=torch.int32)
                 for i, p in enumerate(w.resnet_paths):
@@ -543,14 +596,14 @@ class UNetPlan:
             d.lora_tcol = self.lora.temb_tcol.data_ptr()
             d.lora_up = self.lora.params.data_ptr() + 2 * self.lora.temb_up_off
             d.lora_scale = self.lora_scale_ptr
-        self.prog.add(lib.OP_GEMV, d, "time_emb_proj_all")
+        self.add(lib.OP_GEMV, d, "time_emb_proj_all")
         self.temb_lora_T = lt
 
     def _gemv(self, x_ptr, ldx, wname, N, K, y_ptr, ldy, in_act, addend=None, name=""):
         d = lib.GemvDesc(x=x_ptr, w=self.w.ptr(wname + ".w"), bias=self.w.ptr(wname + ".b"), y=y_ptr,
                          addend=addend[0] if addend else 0, ld_add=addend[1] if addend else 0,
                          nb=self.B, N=N, K=K, ldx=ldx, ldy=ldy, in_act=in_act, out_f32=0)
-        self.prog.add(lib.OP_GEMV, d, name)
+        self.add(lib.OP_GEMV, d, name)
 
     def _resnet(self, x: Src, path: str, cout: int) -> Act:
         x0, x1 = _src_parts(x)
@@ -579,7 +632,7 @@ class UNetPlan:
         qkv = self.ln_gemm(h, path + ".norm1", a1 + ".qkv", 3 * C, bias=False,
                            lora_paths=[a1 + ".to_q", a1 + ".to_k", a1 + ".to_v"], vt_heads=heads)
         T = h.HW
-        o1 = self.attention(qkv.cols(0, C), qkv.cols(C, C), qkv.cols(2 * C, C), T, heads, a1 + ".sdpa", vt_pre=self.last_vt)
+        o1 = self.attention(qkv.cols(0, C), qkv.cols(C, C), qkv.cols(2 * C, C), T, heads, a1 + ".sdpa", vt_pre=qkv.vt)
         h1 = self.gemm(o1, a1 + ".out", C, a1 + ".out", residual=h, lora_paths=[a1 + ".to_out.0"], ln_stats=True)
         vt_pre = None
         if self.kv_all is not None:
@@ -600,22 +653,22 @@ class UNetPlan:
         # (the gate restates slh_gemm's own checks for xa_*: head dim 64 with whole 64-column heads, 65..96 keys - two 64-key V^T
         # tiles are always staged, so xa_ldvt = roundup(ctx_len, 64) must reach 128 - and whole 128-row query tiles per sample)
         if not self.train and vt_pre is not None and D2 == 64 and C % 64 == 0 and 64 < self.ctx_len <= 96 and h.HW % 128 == 0 and \
-                self._lora_group([a2 + ".to_q"]) is None and os.environ.get("SLIDERS_NO_FUSED_XATTN") is None:
+                self._lora_group([a2 + ".to_q"]) is None and not self.sw.no_fused_xattn:
             xa = dict(k=k2, vt_ptr=vt_pre[0], vt_heads=vt_pre[1], Tk=self.ctx_len, Tq=h.HW, scale=D2 ** -0.5,
                       ldvt=(self.ctx_len + 63) // 64 * 64)
         q2 = self.ln_gemm(h1, path + ".norm2", a2 + ".q", C, bias=False, lora_paths=[a2 + ".to_q"], xattn=xa)
-        if xa is not None and self.xattn_done:
+        if q2.attended:
             o2 = q2
         else:
             o2 = self.attention(q2, k2, v2, self.ctx_len, heads, a2 + ".sdpa", vt_pre=vt_pre)
         h2 = self.gemm(o2, a2 + ".out", C, a2 + ".out", residual=h1, lora_paths=[a2 + ".to_out.0"], ln_stats=True)
         if self.train and (self._lora_group([path + ".ff.net.0.proj"]) is not None or
-                           os.environ.get("SLIDERS_TRAIN_UNFUSED_GEGLU") is not None):
+                           self.sw.train_unfused_geglu):
             n3 = self.layernorm(h2, path + ".norm3", path + ".norm3")
             pre = self.gemm(n3, path + ".ff1", 8 * C, path + ".ff1", lora_paths=[path + ".ff.net.0.proj"])
             ff = self.act(h.B, h.H, h.W, 4 * C, path + ".geglu")
-            self.prog.add(lib.OP_ELEMENTWISE, lib.EwDesc(a=pre.ptr, out=ff.ptr, M=pre.M, C=4 * C, lda=pre.ld, ldo=ff.ld,
-                                                         op=lib.EW_GEGLU_FWD), path + ".geglu")
+            self.add(lib.OP_ELEMENTWISE, lib.EwDesc(a=pre.ptr, out=ff.ptr, M=pre.M, C=4 * C, lda=pre.ld, ldo=ff.ld,
+                                                    op=lib.EW_GEGLU_FWD), path + ".geglu")
             self.tape.append(dict(op="geglu", pre=pre, out=ff, name=path + ".geglu"))
         elif self.train:
             # one launch: the GEGLU epilogue also stores proj(x) for the backward (and norm3 folds into it when h2's producer
@@ -650,7 +703,7 @@ class UNetPlan:
         # profiles/r03_first_call.txt.  SLIDERS_TRAIN_KV_PER_BLOCK=1 restores the old form for A/B runs.)
         self.kv_all = self.vt_all = None
         kvo = getattr(self.w, "kv_all_offset", None)
-        if kvo and not (self.train and os.environ.get("SLIDERS_TRAIN_KV_PER_BLOCK")) and \
+        if kvo and not (self.train and self.sw.train_kv_per_block) and \
                 all(self._lora_group([a + ".to_k", a + ".to_v"]) is None for a in kvo):
             n_all = self.w.gemm_shape["attn2_kv_all.w"][0]
             self.kv_all = self.gemm(self.ctx, "attn2_kv_all", n_all, "attn2_kv_all", bias=False)
@@ -664,15 +717,15 @@ class UNetPlan:
                 self.vt_all_heads = vb // D
                 Dp, ldt = (D + 63) // 64 * 64, (self.ctx_len + 63) // 64 * 64
                 self.vt_all = self.arena.alloc((B, self.vt_all_heads, Dp, ldt), torch.bfloat16, "attn2_vt_all")
-                self.prog.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(
+                self.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(
                     src=self.kv_all.ptr + 2 * vb, dst=self.vt_all.ptr, B=B, H=self.vt_all_heads, T=self.ctx_len,
                     ld=self.kv_all.ld, ldt=ldt, D=D), "attn2_vt_all")
         h = self.act(B, H, W, boc[0], "conv_in")
         self.nograd = {ctxb.ptr, h.buf.ptr}     # nothing trainable upstream of these
         self.nograd_kv = set()
-        self.prog.add(lib.OP_CONV_IN, lib.ConvInDesc(x=self.io["sample"].ptr, w=self.w.ptr("conv_in.w"),
-                                                     bias=self.w.ptr("conv_in.b"), y=h.ptr, batch=B,
-                                                     cin=cfg.in_channels, h=H, wd=W, cout=boc[0], ldy=h.ld), "conv_in")
+        self.add(lib.OP_CONV_IN, lib.ConvInDesc(x=self.io["sample"].ptr, w=self.w.ptr("conv_in.w"),
+                                                bias=self.w.ptr("conv_in.b"), y=h.ptr, batch=B,
+                                                cin=cfg.in_channels, h=H, wd=W, cout=boc[0], ldy=h.ld), "conv_in")
         skips = [h]
         # block name -> the activation diffusers' block returns (after its down / upsampler): read by the parity tests' per-block
         # error ledger after a pass (no buffer is reused inside a pass, so they are all still there); nothing else uses it
@@ -739,7 +792,9 @@ class BackwardPlan:
         self.b0, self.nb = b0, nb
         self.one_ptr = one_ptr
         self.scale_ptr = fwd.lora_scale_ptr
+        self.sw = fwd.sw                      # one environment for a forward plan and its backward
         self.prog = lib.Program()
+        self._splitk_tickets = None
         self._g: Dict[int, Act] = {}          # base buffer ptr -> full-width gradient buffer (nb samples)
         self._written = set()
         zmark = self.zarena.mark()
@@ -754,22 +809,22 @@ class BackwardPlan:
         self._wants_dot: Dict[int, Tuple[int, int]] = {}
         self._dot_made: Dict[int, Tuple] = {}
         for rec in fwd.tape:
-            if rec["op"] == "attn" and rec["k"].buf.ptr not in fwd.nograd_kv and os.environ.get("SLIDERS_BWD_DOT_LAUNCH") is None:
+            if rec["op"] == "attn" and rec["k"].buf.ptr not in fwd.nograd_kv and not self.sw.bwd_dot_launch:
                 self._wants_dot[rec["o"].buf.ptr] = (rec["heads"], rec["q"].HW)
         # GEGLU outputs -> their tape record: the backward-data product of the Linear that consumes one writes d(proj) itself
         self._geglu_of: Dict[int, dict] = {}
-        if os.environ.get("SLIDERS_BWD_UNFUSED_GEGLU") is None:
+        if not self.sw.bwd_unfused_geglu:
             for rec in fwd.tape:
                 if rec["op"] == "geglu":
                     self._geglu_of[rec["out"].buf.ptr] = rec
         self._tr_batch: List = []
         self._wg_batch: Dict[int, List] = {4: [], 12: []}
         self._keep: List = []            # device tables of the batched launches
-        self.batched = os.environ.get("SLIDERS_BWD_UNBATCHED") is None
+        self.batched = not self.sw.bwd_unbatched
         # weight gradients reduced over their M splits in a fixed order (slabs + tickets) instead of fp32 atomics: the LoRA
         # gradient buffer is bit-reproducible.  SLIDERS_WGRAD_ATOMIC=1: the old form (A/B)
-        self.wgrad_fixed_order = os.environ.get("SLIDERS_WGRAD_ATOMIC") is None
-        self.fuse_u = os.environ.get("SLIDERS_BWD_UNFUSED_U") is None
+        self.wgrad_fixed_order = not self.sw.wgrad_atomic
+        self.fuse_u = not self.sw.bwd_unfused_u
         self._uses_up_t = False
         self._walk()
         dev = None if self.arena.virtual else fwd.lora.params.device
@@ -971,167 +1026,190 @@ class BackwardPlan:
         y = rec["out"]
         if not self.has_grad(y):
             return
-        f = self.f
         name = "bwd." + rec["name"]
         gy, _ = self.grad(y, write=False)
         x0, x1 = _src_parts(rec["x"])
-        conv, grp, N, K = rec["conv"], rec["grp"], rec["N"], rec["K"]
-        Ho, Wo = rec["Ho"], rec["Wo"]
-        Ms = self.nb * Ho * Wo
-        # residual branch: d(out)/d(residual) = identity
+        need0 = x0.buf.ptr not in self.f.nograd
+        need1 = x1 is not None and x1.buf.ptr not in self.f.nograd
+        self._b_gemm_residual(rec, gy, name)
+        if rec.get("temb_path") and self.lora.temb_entries:
+            self._b_gemm_temb(rec, gy, name)
+        U, up_t_off, dA_after = self._b_gemm_lora(rec, gy, name, need0 or need1) if rec["grp"] is not None else (None, None, [])
+        if not (need0 or need1):
+            return
+        if rec["conv"] is None:
+            self._b_gemm_linear(rec, gy, name, need0, need1, U, up_t_off, dA_after)
+        else:
+            self._b_gemm_conv(rec, gy, name, U)
+
+    def _b_gemm_residual(self, rec, gy: Act, name: str):
+        """residual branch: d(out)/d(residual) = identity"""
         r = rec["residual"]
-        if r is not None and r.buf.ptr not in f.nograd:
+        if r is not None and r.buf.ptr not in self.f.nograd:
             if r.buf.ptr not in self._g and r.ld == r.C and gy.ld == gy.C and r.C == gy.C:
                 self.alias_grad(r, gy)
             else:
                 self.add_into(r, gy, name + ".res")
-        # time-embedding add: gradient w.r.t. the per-sample bias feeds the time_emb_proj adapter
-        if rec.get("temb_path") and self.lora.temb_entries:
-            path = rec["temb_path"]
-            i = f.w.resnet_paths.index(path)
-            e = self.lora.temb_entries[i]
-            gsum = self.zarena.alloc((self.nb, N), torch.float32, name + ".gtemb")
-            self._ew(lib.EW_COLSUM, gy, Act(gsum.ptr, self.nb, 1, 1, N, N, gsum), name=name + ".colsum", iarg2=Ho * Wo)
-            ted = self.cfg.time_embed_dim
-            L4 = f.temb_lora_T.shape[1]
-            for s in range(self.nb):
-                d = lib.TembLoraBwdDesc(g=gsum.ptr + 4 * s * N, t=f.temb_lora_T.ptr + 4 * ((self.b0 + s) * L4 + 4 * i),
-                                        up=self.lora.up_ptr(e), emb=f.emb.ptr + 2 * (self.b0 + s) * ted,
-                                        d_up=self.lora.gup_ptr(e), d_down=self.lora.gdown_ptr(e), scale=self.scale_ptr,
-                                        C=N, ted=ted)
-                self.prog.add(lib.OP_TEMB_LORA_BWD, d, name + ".temb_lora")
-        # LoRA: U = dY . B_up per fused member; dB = s dY^T T ; dA = s U^T X
-        U = None
-        fused_u = False
+
+    def _b_gemm_temb(self, rec, gy: Act, name: str):
+        """time-embedding add: gradient w.r.t. the per-sample bias feeds the time_emb_proj adapter"""
+        f, N, Ho, Wo = self.f, rec["N"], rec["Ho"], rec["Wo"]
+        path = rec["temb_path"]
+        i = f.w.resnet_paths.index(path)
+        e = self.lora.temb_entries[i]
+        gsum = self.zarena.alloc((self.nb, N), torch.float32, name + ".gtemb")
+        self._ew(lib.EW_COLSUM, gy, Act(gsum.ptr, self.nb, 1, 1, N, N, gsum), name=name + ".colsum", iarg2=Ho * Wo)
+        ted = self.cfg.time_embed_dim
+        L4 = f.temb_lora_T.shape[1]
+        for s in range(self.nb):
+            d = lib.TembLoraBwdDesc(g=gsum.ptr + 4 * s * N, t=f.temb_lora_T.ptr + 4 * ((self.b0 + s) * L4 + 4 * i),
+                                    up=self.lora.up_ptr(e), emb=f.emb.ptr + 2 * (self.b0 + s) * ted,
+                                    d_up=self.lora.gup_ptr(e), d_down=self.lora.gdown_ptr(e), scale=self.scale_ptr,
+                                    C=N, ted=ted)
+            self.prog.add(lib.OP_TEMB_LORA_BWD, d, name + ".temb_lora")
+
+    def _b_gemm_lora(self, rec, gy: Act, name: str, dgrad: bool):
+        """LoRA: U = dY . B_up per fused member; dB = s dY^T T ; dA = s U^T X.  dgrad: a backward-data product follows.  Returns
+        (U, the offset of the group's k-major up matrices when U comes out of that product - else None -, the down-gradients that
+        must wait for it)."""
+        f = self.f
+        x0, x1 = _src_parts(rec["x"])
+        conv, grp, N, K, r = rec["conv"], rec["grp"], rec["N"], rec["K"], rec["residual"]
+        Ho, Wo = rec["Ho"], rec["Wo"]
+        Ms = self.nb * Ho * Wo
         dA_after = []
-        need0 = x0.buf.ptr not in f.nograd
-        need1 = x1 is not None and x1.buf.ptr not in f.nograd
-        if grp is not None:
-            ng = len(grp)
-            Ng = N // ng
-            U = self.arena.alloc((Ms, 4 * ng), torch.float32, name + ".U")
-            T = rec["T"]
-            Ts = T.ptr + 4 * self.b0 * (Ho * Wo) * 4 * ng
-            # U = dY . B (the up matrices as a rank-4 down-projection of the output gradient): inside the backward-data GEMM
-            # of a dense module - third operand tile = the k-major copy of B (LoraStore.up_t), written out through lora_t_out
-            # for the down-gradient - unless that product does not exist (no gradient needed upstream)
-            up_t_off = self.lora.up_t_offset(grp) if (self.fuse_u and conv is None and x1 is None and (need0 or need1)) else None
-            if up_t_off is not None:
-                fused_u = True          # (split-K included: the slice that arrives last reduces T as well)
-            if not fused_u:
-                for g_i, e in enumerate(grp):
-                    d = lib.SkinnyDesc(a0=gy.ptr + 2 * g_i * Ng, w=self.lora.up_ptr(e), out=U.ptr + 4 * 4 * g_i, lda0=gy.ld,
-                                       ca0=Ng, mode=0, stride=1, M=Ms, R=4, K=Ng, ldo=4 * ng, w_kmajor=1)
-                    self.prog.add(lib.OP_SKINNY, d, name + f".U{g_i}")
-            d = lib.WgradDesc(z0=gy.ptr, v=Ts, out=self.lora.gup_ptr(grp[0]), scale=self.scale_ptr, ldz0=gy.ld, c0=N,
-                              mode=0, stride=1, M=Ms, R=4, ldv=4 * ng, ldo=4, out_rmajor=0,
-                              vgroup_cols=Ng if ng > 1 else 0)
-            # dY of a module with a residual input may be the residual's gradient buffer too (alias_grad above): it keeps
-            # accumulating after this point, so its up-gradient cannot wait for the batched launch at the tail
-            self._wgrad(d, name + ".dB", defer=r is None or r.buf.ptr in f.nograd)
-            x0s = self._sl(x0)
-            x1s = self._sl(x1) if x1 is not None else None
-            # the down matrices of a fused q|k|v group are adjacent ([12][K]) and so are their U columns: one R = 12 launch
-            # reads X once instead of three times
-            one = ng == 3 and conv is None
-            for g_i, e in enumerate(grp[:1] if one else grp):
-                d = lib.WgradDesc(z0=x0s.ptr, z1=x1s.ptr if x1s else 0, v=U.ptr + 4 * 4 * g_i, out=self.lora.gdown_ptr(e),
-                                  scale=self.scale_ptr, ldz0=x0s.ld, ldz1=x1s.ld if x1s else 0, c0=x0.C,
-                                  c1=x1.C if x1 is not None else 0, mode=0, stride=1, M=Ms, R=12 if one else 4, ldv=4 * ng,
-                                  ldo=K, out_rmajor=1, vgroup_cols=0)
-                if conv is not None:
-                    d.mode, d.batch, d.hs, d.ws = 1, self.nb, x0.H, x0.W
-                    d.src_xform, d.stride, d.ho, d.wo = conv.get("xform", 0), conv.get("stride", 1), Ho, Wo
-                if fused_u:
-                    dA_after.append((d, name + f".dA{g_i}"))            # U is written by the dgrad launch below
-                else:
-                    self._wgrad(d, name + f".dA{g_i}", defer=True)      # forward activations and U: final
-        # backward data
-        if not (need0 or need1):
-            return
+        ng = len(grp)
+        Ng = N // ng
+        U = self.arena.alloc((Ms, 4 * ng), torch.float32, name + ".U")
+        T = rec["T"]
+        Ts = T.ptr + 4 * self.b0 * (Ho * Wo) * 4 * ng
+        # U = dY . B (the up matrices as a rank-4 down-projection of the output gradient): inside the backward-data GEMM
+        # of a dense module - third operand tile = the k-major copy of B (LoraStore.up_t), written out through lora_t_out
+        # for the down-gradient - unless that product does not exist (no gradient needed upstream)
+        up_t_off = self.lora.up_t_offset(grp) if (self.fuse_u and conv is None and x1 is None and dgrad) else None
+        fused_u = up_t_off is not None          # (split-K included: the slice that arrives last reduces T as well)
+        if not fused_u:
+            for g_i, e in enumerate(grp):
+                d = lib.SkinnyDesc(a0=gy.ptr + 2 * g_i * Ng, w=self.lora.up_ptr(e), out=U.ptr + 4 * 4 * g_i, lda0=gy.ld,
+                                   ca0=Ng, mode=0, stride=1, M=Ms, R=4, K=Ng, ldo=4 * ng, w_kmajor=1)
+                self.prog.add(lib.OP_SKINNY, d, name + f".U{g_i}")
+        d = lib.WgradDesc(z0=gy.ptr, v=Ts, out=self.lora.gup_ptr(grp[0]), scale=self.scale_ptr, ldz0=gy.ld, c0=N,
+                          mode=0, stride=1, M=Ms, R=4, ldv=4 * ng, ldo=4, out_rmajor=0,
+                          vgroup_cols=Ng if ng > 1 else 0)
+        # dY of a module with a residual input may be the residual's gradient buffer too (alias_grad above): it keeps
+        # accumulating after this point, so its up-gradient cannot wait for the batched launch at the tail
+        self._wgrad(d, name + ".dB", defer=r is None or r.buf.ptr in f.nograd)
+        x0s = self._sl(x0)
+        x1s = self._sl(x1) if x1 is not None else None
+        # the down matrices of a fused q|k|v group are adjacent ([12][K]) and so are their U columns: one R = 12 launch
+        # reads X once instead of three times
+        one = ng == 3 and conv is None
+        for g_i, e in enumerate(grp[:1] if one else grp):
+            d = lib.WgradDesc(z0=x0s.ptr, z1=x1s.ptr if x1s else 0, v=U.ptr + 4 * 4 * g_i, out=self.lora.gdown_ptr(e),
+                              scale=self.scale_ptr, ldz0=x0s.ld, ldz1=x1s.ld if x1s else 0, c0=x0.C,
+                              c1=x1.C if x1 is not None else 0, mode=0, stride=1, M=Ms, R=12 if one else 4, ldv=4 * ng,
+                              ldo=K, out_rmajor=1, vgroup_cols=0)
+            if conv is not None:
+                d.mode, d.batch, d.hs, d.ws = 1, self.nb, x0.H, x0.W
+                d.src_xform, d.stride, d.ho, d.wo = conv.get("xform", 0), conv.get("stride", 1), Ho, Wo
+            if fused_u:
+                dA_after.append((d, name + f".dA{g_i}"))            # U is written by the dgrad launch below
+            else:
+                self._wgrad(d, name + f".dA{g_i}", defer=True)      # forward activations and U: final
+        return U, up_t_off, dA_after
+
+    def _b_gemm_linear(self, rec, gy: Act, name: str, need0: bool, need1: bool, U, up_t_off, dA_after):
+        """backward data of a Linear / 1x1 convolution"""
+        x0, x1 = _src_parts(rec["x"])
+        grp, N, Ho, Wo = rec["grp"], rec["N"], rec["Ho"], rec["Wo"]
+        Ms = self.nb * Ho * Wo
         cin = x0.C + (x1.C if x1 is not None else 0)
         wT = self.w.ptr(rec["wname"] + ".wT")
-        gyimg = Act(gy.ptr, self.nb, Ho, Wo, N, gy.ld, gy.buf, gy.name)
-        if conv is None:
-            geglu_rec = self._geglu_of.get(x0.buf.ptr) if (x1 is None and grp is None and not self.has_grad(x0)) else None
-            if geglu_rec is not None and x0.C % 32 == 0:
-                # the Linear behind a GEGLU (ff.net.2): its backward-data product writes d(proj) directly (GEGLU backward in
-                # the epilogue, slh_gemm_desc.geglu = 2) - no d(ff) tensor, no elementwise launch
-                pre = geglu_rec["pre"]
-                gp, pacc = self.grad(pre)
-                assert not pacc
-                ps = self._sl(pre)
-                d = lib.GemmDesc(a0=gy.ptr, w=wT, c=gp.ptr, lda0=gy.ld, ca0=N, mode=0, stride=1, ldw=N, M=Ms, N=cin, K=N,
-                                 ldc=gp.ld, rows_per_sample=Ho * Wo, geglu=2, geglu_pre=ps.ptr, ld_pre=ps.ld,
-                                 w_layout=1 if self.w.packed else 0)
-                self._tile(d, name)
-                self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-                return
-            if x1 is None:
-                gx, acc = self.grad(x0)
-                tgt, tacc = gx, acc
-            else:
-                tb = self.arena.alloc((Ms, cin), torch.bfloat16, name + ".gxcat")
-                tgt, tacc = Act(tb.ptr, self.nb, x0.H, x0.W, cin, cin, tb), False
-            d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=0,
-                             stride=1, ldw=N, M=Ms, N=cin, K=N, ld_res=tgt.ld, ldc=tgt.ld, rows_per_sample=Ho * Wo,
+        geglu_rec = self._geglu_of.get(x0.buf.ptr) if (x1 is None and grp is None and not self.has_grad(x0)) else None
+        if geglu_rec is not None and x0.C % 32 == 0:
+            # the Linear behind a GEGLU (ff.net.2): its backward-data product writes d(proj) directly (GEGLU backward in
+            # the epilogue, slh_gemm_desc.geglu = 2) - no d(ff) tensor, no elementwise launch
+            pre = geglu_rec["pre"]
+            gp, pacc = self.grad(pre)
+            assert not pacc
+            ps = self._sl(pre)
+            d = lib.GemmDesc(a0=gy.ptr, w=wT, c=gp.ptr, lda0=gy.ld, ca0=N, mode=0, stride=1, ldw=N, M=Ms, N=cin, K=N,
+                             ldc=gp.ld, rows_per_sample=Ho * Wo, geglu=2, geglu_pre=ps.ptr, ld_pre=ps.ld,
                              w_layout=1 if self.w.packed else 0)
-            if grp is not None:
-                d.ld_t, d.lora_up, d.lora_scale = 4 * len(grp), self.lora.down_ptr(grp[0]), self.scale_ptr
-                d.lora_groups, d.lora_rank, d.lora_up_rmajor = 1, 4 * len(grp), 1
-                if fused_u:
-                    self._uses_up_t = True
-                    base = 0x2000 if self.arena.virtual else self.lora.up_t.data_ptr()
-                    d.lora_down, d.lora_t_out = base + 2 * up_t_off, U.ptr
-                else:
-                    d.lora_t = U.ptr
-            want = self._wants_dot.get(x0.buf.ptr) if (x1 is None and not tacc and tgt.ptr == gx.ptr) else None
-            vt = None
-            if want is not None:
-                heads, Tq = want
-                Dh = cin // heads
-                if Dh % 64 == 0 and Tq % 64 == 0 and Ms == self.nb * Tq and cin == x0.C and tgt.ld % 8 == 0:
-                    vt = dict(vt_col0=0, vt_D=Dh, vt_heads=heads, vt_tokens=Tq, vt_ld=Tq, vt_also_c=1)
-            self._tile(d, name, vt)
-            if d.vt_out:
-                dot = self.arena.alloc((self.nb, heads, Dh, Tq), torch.bfloat16, name + ".dot")
-                d.vt_out = dot.ptr
-                self._dot_made[x0.buf.ptr] = (dot, Tq)
-            self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-            for dA, nm in dA_after:
-                self._wgrad(dA, nm, defer=True)
-            if x1 is not None:
-                if need0:
-                    self.add_into(x0, tgt.cols(0, x0.C), name + ".gx0")
-                if need1:
-                    self.add_into(x1, tgt.cols(x0.C, x1.C), name + ".gx1")
-        else:
-            assert x1 is None
-            xform, stride = conv.get("xform", 0), conv.get("stride", 1)
-            if xform == 1:     # forward read a nearest-2x upsampled image: dgrad lands on the 2h x 2w grid first
-                HL, WL = 2 * x0.H, 2 * x0.W
-                tb = self.arena.alloc((self.nb * HL * WL, cin), torch.bfloat16, name + ".gx_up")
-                tgt, tacc = Act(tb.ptr, self.nb, HL, WL, cin, cin, tb), False
-            else:
-                HL, WL = x0.H, x0.W
-                tgt, tacc = self.grad(x0)
-            d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=1,
-                             batch=self.nb, hs=Ho, ws=Wo, src_xform=2 if stride == 2 else 0, stride=1, ho=HL, wo=WL,
-                             ldw=9 * N, M=self.nb * HL * WL, N=cin, K=9 * N, ld_res=tgt.ld, ldc=tgt.ld,
-                             rows_per_sample=HL * WL, w_layout=1 if self.w.packed else 0)
             self._tile(d, name)
             self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-            if grp is not None:
-                d2 = lib.LoraCdgradDesc(u=U.ptr, a_down=self.lora.down_ptr(grp[0]), scale=self.scale_ptr, gx=tgt.ptr,
-                                        batch=self.nb, hl=HL, wl=WL, ho=Ho, wo=Wo, stride=stride, cin=cin, ldu=4,
-                                        ldgx=tgt.ld, accumulate=1)
-                self.prog.add(lib.OP_LORA_CONV_DGRAD, d2, name + ".lora_dgrad")
-            if xform == 1:
-                gx, acc = self.grad(x0)
-                if acc:
-                    t2b = self.arena.alloc((self.nb * x0.HW, cin), torch.bfloat16, name + ".gx_dn")
-                    t2 = Act(t2b.ptr, self.nb, x0.H, x0.W, cin, cin, t2b)
-                    self._ew(lib.EW_UPSAMPLE_BWD, tgt, t2, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=t2.M)
-                    self._ew(lib.EW_ADD, gx, gx, t2, name + ".add")
-                else:
-                    self._ew(lib.EW_UPSAMPLE_BWD, tgt, gx, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=gx.M)
+            return
+        if x1 is None:
+            gx, acc = self.grad(x0)
+            tgt, tacc = gx, acc
+        else:
+            tb = self.arena.alloc((Ms, cin), torch.bfloat16, name + ".gxcat")
+            tgt, tacc = Act(tb.ptr, self.nb, x0.H, x0.W, cin, cin, tb), False
+        d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=0,
+                         stride=1, ldw=N, M=Ms, N=cin, K=N, ld_res=tgt.ld, ldc=tgt.ld, rows_per_sample=Ho * Wo,
+                         w_layout=1 if self.w.packed else 0)
+        if grp is not None:
+            d.ld_t, d.lora_up, d.lora_scale = 4 * len(grp), self.lora.down_ptr(grp[0]), self.scale_ptr
+            d.lora_groups, d.lora_rank, d.lora_up_rmajor = 1, 4 * len(grp), 1
+            if up_t_off is not None:
+                self._uses_up_t = True
+                base = 0x2000 if self.arena.virtual else self.lora.up_t.data_ptr()
+                d.lora_down, d.lora_t_out = base + 2 * up_t_off, U.ptr
+            else:
+                d.lora_t = U.ptr
+        want = self._wants_dot.get(x0.buf.ptr) if (x1 is None and not tacc and tgt.ptr == gx.ptr) else None
+        vt = None
+        if want is not None:
+            heads, Tq = want
+            Dh = cin // heads
+            if Dh % 64 == 0 and Tq % 64 == 0 and Ms == self.nb * Tq and cin == x0.C and tgt.ld % 8 == 0:
+                vt = dict(vt_col0=0, vt_D=Dh, vt_heads=heads, vt_tokens=Tq, vt_ld=Tq, vt_also_c=1)
+        self._tile(d, name, vt)
+        if d.vt_out:
+            dot = self.arena.alloc((self.nb, heads, Dh, Tq), torch.bfloat16, name + ".dot")
+            d.vt_out = dot.ptr
+            self._dot_made[x0.buf.ptr] = (dot, Tq)
+        self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
+        for dA, nm in dA_after:
+            self._wgrad(dA, nm, defer=True)
+        if x1 is not None:
+            if need0:
+                self.add_into(x0, tgt.cols(0, x0.C), name + ".gx0")
+            if need1:
+                self.add_into(x1, tgt.cols(x0.C, x1.C), name + ".gx1")
+
+    def _b_gemm_conv(self, rec, gy: Act, name: str, U):
+        """backward data of a 3x3 convolution"""
+        x0, x1 = _src_parts(rec["x"])
+        conv, grp, N, Ho, Wo = rec["conv"], rec["grp"], rec["N"], rec["Ho"], rec["Wo"]
+        cin = x0.C
+        wT = self.w.ptr(rec["wname"] + ".wT")
+        assert x1 is None
+        xform, stride = conv.get("xform", 0), conv.get("stride", 1)
+        if xform == 1:     # forward read a nearest-2x upsampled image: dgrad lands on the 2h x 2w grid first
+            HL, WL = 2 * x0.H, 2 * x0.W
+            tb = self.arena.alloc((self.nb * HL * WL, cin), torch.bfloat16, name + ".gx_up")
+            tgt, tacc = Act(tb.ptr, self.nb, HL, WL, cin, cin, tb), False
+        else:
+            HL, WL = x0.H, x0.W
+            tgt, tacc = self.grad(x0)
+        d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=1,
+                         batch=self.nb, hs=Ho, ws=Wo, src_xform=2 if stride == 2 else 0, stride=1, ho=HL, wo=WL,
+                         ldw=9 * N, M=self.nb * HL * WL, N=cin, K=9 * N, ld_res=tgt.ld, ldc=tgt.ld,
+                         rows_per_sample=HL * WL, w_layout=1 if self.w.packed else 0)
+        self._tile(d, name)
+        self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
+        if grp is not None:
+            d2 = lib.LoraCdgradDesc(u=U.ptr, a_down=self.lora.down_ptr(grp[0]), scale=self.scale_ptr, gx=tgt.ptr,
+                                    batch=self.nb, hl=HL, wl=WL, ho=Ho, wo=Wo, stride=stride, cin=cin, ldu=4,
+                                    ldgx=tgt.ld, accumulate=1)
+            self.prog.add(lib.OP_LORA_CONV_DGRAD, d2, name + ".lora_dgrad")
+        if xform == 1:
+            gx, acc = self.grad(x0)
+            if acc:
+                t2b = self.arena.alloc((self.nb * x0.HW, cin), torch.bfloat16, name + ".gx_dn")
+                t2 = Act(t2b.ptr, self.nb, x0.H, x0.W, cin, cin, t2b)
+                self._ew(lib.EW_UPSAMPLE_BWD, tgt, t2, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=t2.M)
+                self._ew(lib.EW_ADD, gx, gx, t2, name + ".add")
+            else:
+                self._ew(lib.EW_UPSAMPLE_BWD, tgt, gx, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=gx.M)

@@ -258,41 +258,33 @@ class _EpsBridge(torch.autograd.Function):
 
 
 class _VirtualWeights:
-    """Pointer-less stand-in so the planner can be dry-run for sizing."""
+    """Pointer-less stand-in so the planner can be dry-run for sizing: the WeightStore itself (every attribute the planner asks -
+    layouts, switches, has() - is forwarded, so a new one cannot be forgotten here) with one placeholder for every address."""
 
     def __init__(self, w: WeightStore):
         self._w = w
-        self.temb_offsets = w.temb_offsets
-        self.temb_total = w.temb_total
-        self.resnet_paths = w.resnet_paths
-        self.packed = w.packed
-        self.kv_all_offset = w.kv_all_offset
-        self.kv_all_vbase = w.kv_all_vbase
-        self.gemm_shape = w.gemm_shape
-        self.ln_fold = w.ln_fold
-        self.geglu16 = getattr(w, "geglu16", False)    # the dry run must plan GEGLU.proj on the tile the real plan will take
+
+    def __getattr__(self, name):
+        if name == "_w":
+            raise AttributeError(name)
+        return getattr(self._w, name)
 
     def ptr(self, name):
         return 0x1000
 
-    def has(self, name):
-        return self._w.has(name)
-
 
 class _VirtualLora:
+    """The LoraStore with placeholders for its addresses and device tensors (everything else is forwarded)."""
+
     def __init__(self, s: LoraStore):
         self._s = s
-        self.temb_entries = s.temb_entries
-        self.temb_down_off = s.temb_down_off
-        self.temb_up_off = s.temb_up_off
         self.temb_tcol = _FakeTensor()
         self.params = _FakeTensor()
 
-    def fused_group(self, paths):
-        return self._s.fused_group(paths)
-
-    def up_t_offset(self, grp):
-        return self._s.up_t_offset(grp)
+    def __getattr__(self, name):
+        if name == "_s":
+            raise AttributeError(name)
+        return getattr(self._s, name)
 
     def down_ptr(self, e):
         return 0x2000

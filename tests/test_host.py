@@ -233,7 +233,7 @@ def test_tile_and_its_extras_are_chosen_together(monkeypatch):
     x = p.act(1, 32, 32, K, "x")
     monkeypatch.setitem(tuning.table(), f"{x.M},{N},{K},m0,s1,x0,g0,l0,no", 0x5425)
     out = p.gemm(x, "probe", N, "probe", bias=False, vt_heads=10, ln_stats=True)
-    o, d = p.prog.ops[-1]
+    o, d, _ = p.ops[-1]                        # (recorded behind the finished plan: not part of p.prog, which was serialised once)
     assert o == lib.OP_GEMM and d.tile == 0x5425
     lib.gemm_kernel_name(d)
     assert out.ln is not None and d.ln_out == out.ln[0].ptr
@@ -801,14 +801,6 @@ def test_refused_layernorm_fold_leaves_nothing_in_the_program(monkeypatch):
     # every recorded skinny launch writes a buffer that no LATER allocation overlaps (the stale launch wrote into re-allocated bytes)
     spans = sorted((s, e) for s, e, _ in va.allocs)
     assert all(spans[i][1] <= spans[i + 1][0] for i in range(len(spans) - 1))
-    # Program.truncate itself
-    prog = lib.Program()
-    prog.memset(0x1000, 16, 0, "a")
-    m = prog.mark()
-    prog.memset(0x2000, 16, 0, "b")
-    prog.memset(0x3000, 16, 0, "c")
-    prog.truncate(m)
-    assert prog.n_ops == 1 and prog.op_names == ["a"] and len(prog.ops) == 1
 
 
 class _FakeWeightsKvAll(_FakeWeights):
@@ -1417,3 +1409,44 @@ def test_attention_matrix_is_not_hollow():
     assert any(c.Tk % 64 and c.need_dkv for c in am.BWD_CASES) and {"n", "o"} <= {c.do_cls for c in am.BWD_CASES}
     gpu = open(os.path.join(ROOT, "tests", "test_attention_matrix_gpu.py")).read()
     assert "skip" not in gpu and "xfail" not in gpu
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The planner's programs, byte by byte (tests/plan_digest.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_planned_programs_match_the_recorded_digests():
+    """Every dry-run plan of tests/plan_digest.py's matrix - seven configurations x adapters off / on / training forward + backward in
+    the default environment, SDXL 64^2 with every planner switch flipped on its own - records the command buffers, parked batch
+    descriptors, lnfold items, arena allocations and tape length whose SHA-256 tests/data/plan_digests.json holds.  A refactor of the
+    planner leaves the file alone; a pull request that changes a plan re-records it (python -m tests.plan_digest --write) and shows
+    which plans moved; `--dump DIR` on both trees and a diff name the first op that differs."""
+    from tests import plan_digest as pd
+    rec = json.load(open(pd.DATA))
+    got = pd.digests()
+    assert sorted(got) == sorted(rec), f"plans without a record, or records without a plan: {sorted(set(got) ^ set(rec))}"
+    diff = {k: (got[k], rec[k]) for k in got if got[k] != rec[k]}
+    assert not diff, f"planned now / recorded: {diff}"
+    assert len(got) >= 93 and os.path.getsize(pd.DATA) < 64 * 1024
+    # the matrix is not hollow: every switch moves at least one plan (three of them only at 128^2: plan_digest.WIDE_SWITCHES)
+    for var, val in pd.switches():
+        moved = [k for k in got if k.endswith(f"|{var}={val}") and got[k]["sha256"] != got[k[:k.rindex("|")]]["sha256"]]
+        assert moved, f"{var}={val} changes no plan it is flipped for"
+
+
+@pytest.mark.parametrize("name,hw,method", [("sdxl", 64, "noxattn"), ("sdxl", 128, "full"), ("sd1", 64, "full")])
+def test_a_refused_layernorm_fold_plans_what_no_fold_plans(monkeypatch, name, hw, method):
+    """A LayerNorm fold that the tile choice refuses must leave no trace: with planner.choose_tile refusing every product that folds
+    one (ln_in), the plans - adapters off / on / training forward + backward - are, byte for byte, allocation for allocation and tape
+    record for tape record, the plans of a weight store without folded weights (ln_fold = False), which never tries.  Reaches the
+    no-adapter refusals (no-grad and training) that no configuration of the digest matrix does."""
+    from sliders_amd import planner
+    from tests import plan_digest as pd
+    real = planner.choose_tile
+    for mode in pd.MODES:
+        want = pd.record(*pd.planned((name, hw, method, mode), None, ln_fold=False))
+        with monkeypatch.context() as m:
+            m.setattr(planner, "choose_tile", lambda d, **kw: None if d.ln_in else real(d, **kw))
+            p, bw, va, vz = pd.planned((name, hw, method, mode), None)
+            got = pd.record(p, bw, va, vz)
+        assert not any(d.ln_in for o, d in p.prog.ops if o == lib.OP_GEMM)
+        assert got == want, mode
