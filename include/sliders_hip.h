@@ -171,6 +171,12 @@ int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream);
  * every present and future tile.  Needs no device and launches nothing.  0, or the status slh_gemm would return for d.
  * (bench.py / scripts/make_pmc_traffic.py pair in-situ event times and PMC rows by this name.) */
 int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap);
+/* slh_gemm_kernel_name plus the launch: the grid (workgroups), the block size (threads) and a 64-bit FNV-1a hash of the bytes of the
+ * argument struct the kernel would receive (zeroed before it is filled, padding included).  A function of the descriptor alone: the two
+ * inputs slh_gemm takes from the machine are fixed in a query - 256 CUs behind the weight touch, same-XCD split-K slab reads on - so
+ * the answer is the same without a device and on an MI355X (tests/data/gemm_dispatch.json pins it: a change of the dispatch that keeps
+ * every result but moves a grid, a group_m or a split-K cut shows there).  0, or the status slh_gemm would return for d. */
+int slh_gemm_launch_query(const slh_gemm_desc* d, char* name, int cap, int32_t* grid, int32_t* block, uint64_t* args_hash);
 /* The 64 x 160 tile (tile codes 0x5425: 4-slot LDS ring, 0x5525: 5 slots - no other 0x5xxx code is accepted; csrc/gemm5.hip): 4 waves
  * of 32 x 80 on the 16 x 16 x 32 MFMA - the M = 2048, N = 1280 products as 256 workgroups = one full round of the chip.  Dense single-source products with packed
  * weights (w_layout = 1), M % 64 == 0, N % 160 == 0; epilogue: bias, residual, ln_out - whose chunks are then 80 COLUMNS wide:
@@ -186,7 +192,8 @@ int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap);
 /* 1 where the tile named by d->tile (0: the one slh_gemm's own heuristic picks) can run d's shape and features: every check of
  * slh_gemm except what a caller provisions once the tile is chosen - the split-K slab / ticket workspace and its slab count, and
  * ln_lora_s / ln_lora_c.  slh_gemm runs this check first and returns its status, so a query and a launch cannot disagree.  Needs
- * no device. */
+ * no device.  The tile code is taken apart in one place (csrc/gemm_dispatch.h: GemmTile) and every contract is stated once, for all
+ * families; a refusal names the condition and, once the code is decoded, the tile ("... (64 x 160 tile, 0x5425)"). */
 int slh_gemm_tile_ok(const slh_gemm_desc* d);
 /* Width of the LayerNorm chunks (ln_out) d's tile writes: 80 columns on the 64 x 160 tile and on 0x7645, 64 on the other tiles
  * that take ln_out (128-column ring tiles, 0x8042, 0x7648) - the producer's ln_out is [N / width][M][2] and its consumers'

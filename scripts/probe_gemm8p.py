@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from sliders_amd import lib
+from sliders_amd.tuning import tile_fields
 from sliders_amd.weights import pack_gemm_w
 
 DENSE = "2048x10240x1280,2048x1280x5120,2048x3840x1280,2048x1280x1280,8192x5120x640,8192x640x2560,8192x1920x640,8192x640x640,4096x4096x4096"
@@ -61,7 +62,7 @@ for shp in [v for v in a.shapes.split(",") if v]:
         descs = [lib.GemmDesc(a0=x.data_ptr(), w=wp.data_ptr(), bias=bias.data_ptr(), residual=res.data_ptr(), c=c.data_ptr(),
                               lda0=K, ca0=K, mode=0, stride=1, ldw=0, M=M, N=N, K=K, ld_res=N, ldc=N, rows_per_sample=M, tile=tile,
                               w_layout=1) for wp in wps]
-        if tile >> 16:     # split-K (bits 16-19) / stream-K (bits 20-21): slab workspace + zeroed tickets
+        if tile_fields(tile).splitk:     # split-K: slab workspace + zeroed tickets
             nsl = 8
             ws = torch.empty(nsl * ((M + 255) // 256 * 256) * ((N + 127) // 128 * 128), device=dev, dtype=torch.float32)
             tk = torch.zeros(4096, device=dev, dtype=torch.int64)

@@ -14,7 +14,7 @@ from sliders_amd import lib
 from sliders_amd.config import CONFIGS
 from sliders_amd.lora_store import LoraStore
 from sliders_amd.random_init import random_state_dict
-from sliders_amd.tuning import gemm_key
+from sliders_amd.tuning import gemm_key, tile_fields
 from sliders_amd.unet import UNetEngine
 
 ap = argparse.ArgumentParser()
@@ -57,9 +57,9 @@ for key, ds in sorted(shapes.items(), key=lambda kv: -kv[1][0].M * kv[1][0].N * 
     d0 = ds[0]
     res = {}
     for tile in (0x22, 0x21, 0x12, 0x11, 0x4022, 0x4012, 0x4011, 0):
-        if d0.geglu and (tile & 15) == 1:
+        if d0.geglu and tile_fields(tile).ni == 1:
             continue
-        if (tile >> 12) == 4 and d0.M * d0.N < 256 * 128 * 64:
+        if tile_fields(tile).family == 4 and d0.M * d0.N < 256 * 128 * 64:
             continue    # 8-wave tiles only make sense when they still give >= 64 workgroups
         d = type(d0).from_buffer_copy(bytes(d0))
         d.tile = tile

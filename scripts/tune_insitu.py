@@ -17,7 +17,7 @@ from sliders_amd import lib
 from sliders_amd.config import CONFIGS
 from sliders_amd.lora_store import LoraStore
 from sliders_amd.random_init import random_state_dict
-from sliders_amd.tuning import gemm_key, tile_ok
+from sliders_amd.tuning import gemm_key, tile_fields, tile_ok
 from sliders_amd.unet import UNetEngine
 
 ap = argparse.ArgumentParser()
@@ -61,11 +61,12 @@ def launch(op, d):
 
 
 def valid(d, tile):
-    mi, ni, wm = (tile >> 4) & 15, tile & 15, (tile >> 12) & 15
+    f = tile_fields(tile)
+    ni, wm = f.ni, f.family
     if not tile_ok(d, tile):
         return False
-    if (tile >> 16) & 15:                       # split-K candidates only where the planner provisioned a workspace
-        if not d.splitk_c32 or (d.K // 64) < 4 * ((tile >> 16) & 15) or ((tile >> 16) & 15) > d.splitk_slabs:
+    if f.splitk:                                # split-K candidates only where the planner provisioned a workspace
+        if not d.splitk_c32 or (d.K // 64) < 4 * f.splitk or f.splitk > d.splitk_slabs:
             return False
     if d.geglu in (1, 2) and ni != 2:           # (geglu = 3, the 16 | 16 block order, takes any tile)
         return False

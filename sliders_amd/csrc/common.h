@@ -274,17 +274,20 @@ void slh_set_error(const char* fmt, ...);
             return -1;                  \
         }                               \
     } while (0)
-// kernel-name query mode (error.cpp; slh_gemm_kernel_name): the dispatch code runs as for a launch, slh_launch records the chosen
-// instantiation instead of launching it, and the launch checks are skipped (no device is needed)
+// query mode (error.cpp; slh_gemm_kernel_name, slh_gemm_launch_query): the dispatch code runs as for a launch, slh_launch records the
+// chosen instantiation, its grid, its block size and a hash of its argument bytes instead of launching it, and the launch checks are
+// skipped (no device is needed)
 bool slh_name_mode();
 void slh_name_record(const char* fmt, ...);
 void slh_name_sink_set(char* buf, int cap);
+void slh_launch_record(int grid, int block, const void* args, size_t bytes);      // grid, block, 64-bit FNV-1a of the argument bytes
+void slh_launch_recorded(int* grid, int* block, unsigned long long* args_hash);   // what the last slh_launch of this thread recorded
 inline const char* slh_tf(bool b) { return b ? "true" : "false"; }
 // fmt + args spell the instantiation's template arguments from the SAME constants the template is instantiated with, in the one
 // statement that launches it (hipcc's __PRETTY_FUNCTION__ drops the arguments of a function-template pointer, so they are not derived)
 template <auto Kern, class A, class... N>
 inline void slh_launch(int grid, int block, hipStream_t s, const A& a, const char* fmt, N... n) {
-    if (slh_name_mode()) { slh_name_record(fmt, n...); return; }
+    if (slh_name_mode()) { slh_name_record(fmt, n...); slh_launch_record(grid, block, &a, sizeof(A)); return; }
     hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), 0, s, a);
 }
 #define SLH_LAUNCH_CHECK(name)                                              \

@@ -17,6 +17,7 @@
 // GEGLU.proj, FeedForward.net.2, Transformer2DModel.proj_in/out) plus the LoRA branch of
 // trainscripts/textsliders/lora.py:108-112.
 #include "gemm_common.h"
+#include "gemm_dispatch.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -475,12 +476,9 @@ int launch_gemm(const GemmArgs& a, int mode, int stages, hipStream_t s) {
 
 }  // namespace
 
-int slh_gemm5_launch(const slh_gemm_desc* d, slh_stream_t stream);      // gemm5.hip
-int slh_gemm7_launch(const slh_gemm_desc* d, slh_stream_t stream);      // gemm7.hip
-bool gemm5_tile_ok(const slh_gemm_desc* d);                             // gemm5.hip: the 64 x 160 tile's own rule
-bool gemm7_tile_ok(const slh_gemm_desc* d);                             // gemm7.hip: the four-wave tiles' own rule
-
+// CUs behind the weight touch; a query (slh_gemm_launch_query) answers for the MI355X's 256 on any machine
 static int slh_ncu() {
+    if (slh_name_mode()) return 256;
     static const int ncu = [] {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -490,27 +488,59 @@ static int slh_ncu() {
     return ncu;
 }
 
-// tile choice: explicit (d->tile, set by the planner from the tuned table) or a fill-the-chip heuristic
-static void pick_tile(const slh_gemm_desc* d, int& MI, int& NI, int& WM) {
-    MI = 2; NI = 2; WM = 2;
-    if (d->tile) {
-        MI = (d->tile >> 4) & 15; NI = d->tile & 15;
-        const int wcode = (d->tile >> 12) & 15;
-        WM = wcode == 4 ? 4 : 2;
-        if (wcode == 8) WM = 8;      // ping-pong K loops (gemm8p.hip): MI = 4, NI = 2 -> 256 x 256; MI = 1, NI = 3..5 -> 128 x 64*NI
-        if (MI) return;
-        MI = 2; NI = 2; WM = 2;
-    }
-    // untuned shape: the pattern of the measured table (sliders_amd/tuning/gfx950_sdxl_128.json) - the 8-wave 128x128
-    // tile once it yields enough workgroups (or fewer, but with a long K loop to amortise them), 64x64 otherwise
-    const long t128 = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
-    if (d->geglu == 1) {
-        NI = 2; MI = 1; WM = t128 >= 192 ? 4 : 2;
-    } else if (t128 >= 256 || (t128 >= 160 && d->K >= 5760)) {
-        MI = 1; NI = 2; WM = 4;
+// The tile d names - explicit (set by the planner from the tuned table) or, for an all-zero code, a fill-the-chip heuristic - or the
+// refusal of a code that names no kernel: every nibble of bits 0-15 is either read by the dispatch or must be zero.
+int gemm_tile_decode(const slh_gemm_desc* d, GemmTile* t) {
+    const int tile = d->tile, fam = (tile >> 12) & 15, st = (tile >> 8) & 15, hi = (tile >> 4) & 15, lo = tile & 15;
+    SLH_CHECK((tile >> 20) == 0, "slh_gemm: tile 0x%x uses reserved bits (20 and up must be zero)", tile);
+    t->splitk = (tile >> 16) & 15;
+    t->slots = st; t->mi = hi; t->ni = lo; t->wm = 0;
+    if ((tile & 0xffff) == 0) {
+        // untuned shape: the pattern of the measured table (sliders_amd/tuning/gfx950_sdxl_128.json) - the 8-wave 128x128
+        // tile once it yields enough workgroups (or fewer, but with a long K loop to amortise them), 64x64 otherwise
+        const long t128 = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
+        t->family = GEMM_RING;
+        t->mi = 1;
+        if (d->geglu == 1) {
+            t->ni = 2; t->wm = t128 >= 192 ? 4 : 2;
+        } else if (t128 >= 256 || (t128 >= 160 && d->K >= 5760)) {
+            t->ni = 2; t->wm = 4;
+        } else {
+            t->ni = 1; t->wm = 2;
+        }
+    } else if (fam == 5) {                                      // gemm5.hip: 4 waves of 32 x 80
+        SLH_CHECK((tile & 0xfff) == 0x425 || (tile & 0xfff) == 0x525,
+                  "slh_gemm: the 64 x 160 tile is 0x5425 (4 ring slots) or 0x5525 (5 ring slots), not 0x%x", tile & 0xffff);
+        t->family = GEMM_64X160;
+        t->bm = 64; t->bn = 160; t->threads = 256;
+        return 0;
+    } else if (fam == 7) {                                      // gemm7.hip: 0x7<S><XB><WB>
+        // (a 128 x 320 four-wave instantiation, 0x754a, was measured and removed: it lost to the ping-pong tile in the pass and is
+        // superseded by the 256 x 320 tile - profiles/r06_gemm7_insitu_ab.txt, r06_tile_256x320.txt)
+        SLH_CHECK((tile & 0xfff) == 0x648 || (tile & 0xfff) == 0x645 || (tile & 0xfff) == 0x48a,
+                  "slh_gemm: the tiles of gemm7.hip are 0x7648 (128 x 256), 0x7645 (128 x 160) and 0x748a (256 x 320), not 0x%x", tile & 0xffff);
+        t->family = GEMM_FOURWAVE;
+        t->bm = 32 * hi; t->bn = 32 * lo; t->threads = 512;
+        return 0;
     } else {
-        MI = 1; NI = 1; WM = 2;
+        SLH_CHECK(fam == 0 || fam == 2 || fam == 4 || fam == 8,
+                  "slh_gemm: tile 0x%x: bits 12-15 are 0 | 2 (4 waves), 4 (8 waves), 8 (ping-pong), 5 (64 x 160) or 7 (gemm7.hip)", tile);
+        SLH_CHECK(hi != 0, "slh_gemm: tile 0x%x names no block tile (MI = 0): bits 0-15 are all zero (heuristic) or a complete tile code", tile);
+        if (fam == 8) {                                         // gemm8p.hip: one 8-wave workgroup per CU
+            SLH_CHECK(st == 0, "slh_gemm: tile 0x%x: bits 8-11 of a ping-pong tile (0x8042, 0x801<NI>) must be zero", tile);
+            SLH_CHECK((hi == 4 && lo == 2) || (hi == 1 && lo >= 3 && lo <= 5),
+                      "slh_gemm: tile 0x%x: ping-pong tiles are 256 x 256 (0x8042) or 128 x 64*NI (0x801<NI>, NI = 3..5)", tile);
+            t->family = GEMM_PINGPONG; t->wm = 8;
+            t->bm = hi == 1 ? 128 : 256; t->bn = hi == 1 ? 64 * lo : 256; t->threads = 512;
+            return 0;
+        }
+        SLH_CHECK(st == 0 || st == 2 || st == 3 || st == 4, "slh_gemm: tile 0x%x: bits 8-11 (ring slots) are 0 | 2 (double buffer), 3 or 4", tile);
+        t->family = GEMM_RING; t->wm = fam == 4 ? 4 : 2;
+        SLH_CHECK((hi == 1 || hi == 2) && (lo == 1 || lo == 2), "slh_gemm: bad tile 0x%x: MI and NI are 1 or 2", tile);
+        SLH_CHECK(t->wm == 2 || lo == 2 || hi == 1, "slh_gemm: tile 0x%x: 8-wave tiles are 128x64, 128x128 or 256x128", tile);
     }
+    t->bm = 32 * t->mi * t->wm; t->bn = 64 * t->ni; t->threads = 128 * t->wm;
+    return 0;
 }
 
 // L2 blocking: number of m-tile groups G (see the kernel's tile mapping).  An XCD's chunk of the grouped sequence reads
@@ -539,6 +569,20 @@ static int pick_group_m(const slh_gemm_desc* d, int tiles_m) {
     return (tiles_m + G - 1) / G;
 }
 
+// gemm5.hip / gemm7.hip: an XCD's run of tiles_m * tiles_n / 8 tiles is gm row tiles x (run / gm) column tiles; pick the gm (power
+// of two) that minimises the operand rows it pulls through its L2 (bm * gm of X + bn * run / gm of W)
+int gemm_group_m(int tiles_m, int tiles_n, int bm, int bn) {
+    const int run = (tiles_m * tiles_n + 7) / 8;
+    int best = 1;
+    long best_cost = -1;
+    for (int gm = 1; gm <= tiles_m; gm *= 2) {
+        const int gn = (run + gm - 1) / gm;
+        const long cost = (long)bm * gm + (long)bn * (gn < tiles_n ? gn : tiles_n);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = gm; }
+    }
+    return best;
+}
+
 // the name of the kernel instantiation slh_gemm would launch for d, as rocprofv3 prints it ("gemm8pb_kernel<1, 5, 0, false>"): the
 // whole of slh_gemm runs - descriptor checks, tile choice, ring-depth fallback - with the launch itself replaced by a record of the
 // selected template (common.h: slh_launch).  No device needed, nothing launched.  0 / the descriptor's error.
@@ -551,22 +595,79 @@ extern "C" int slh_gemm_kernel_name(const slh_gemm_desc* d, char* buf, int cap) 
     return rc;
 }
 
-// K slices a launch of d runs (1: no split-K): the factor S of tile bits 16-19, cut so that every slice is non-empty - each publishes
-// its whole partial tile, the last one to arrive reads them all; per = K tiles per slice
-static int gemm_splitk(const slh_gemm_desc* d, int& per) {
-    const int nk = d->K / 64, s = (d->tile >> 16) & 15;
+// slh_gemm_kernel_name plus the launch itself: grid, block size and the FNV-1a hash of the argument struct the kernel would receive
+extern "C" int slh_gemm_launch_query(const slh_gemm_desc* d, char* name, int cap, int32_t* grid, int32_t* block, uint64_t* args_hash) {
+    SLH_CHECK(grid && block && args_hash, "slh_gemm_launch_query: null pointer");
+    const int rc = slh_gemm_kernel_name(d, name, cap);
+    if (rc) return rc;
+    int g, b;
+    unsigned long long h;
+    slh_launch_recorded(&g, &b, &h);
+    *grid = g; *block = b; *args_hash = h;
+    return 0;
+}
+
+// K slices a launch of d runs (1: no split-K): the tile's factor, cut so that every slice is non-empty - each publishes its whole
+// partial tile, the last one to arrive reads them all; per = K tiles per slice
+static int gemm_splitk(const slh_gemm_desc* d, const GemmTile& t, int& per) {
+    const int nk = d->K / 64, s = t.splitk;
     per = nk;
     if (s <= 1) return 1;
     per = (nk + s - 1) / s;
     return (nk + per - 1) / per;
 }
 
+// vt_out: the columns from vt_col0 on leave head-transposed; whole heads, whole col_align-column blocks and token_align-row blocks
+int gemm_check_vt(const slh_gemm_desc* d, const GemmTile& t, int col_align, int token_align) {
+    GEMM_CHECK(d->vt_D > 0 && d->vt_D % 64 == 0 && d->vt_col0 % col_align == 0 && d->vt_col0 < d->N && d->vt_heads > 0 &&
+                   (d->N - d->vt_col0) == d->vt_heads * d->vt_D && d->vt_tokens > 0 && d->vt_tokens % token_align == 0 &&
+                   d->M % d->vt_tokens == 0 && d->vt_ld % 8 == 0 && d->vt_ld == d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
+               "vt_out constraints (vt_D %% 64, vt_col0 %% %d, vt_tokens %% %d, M %% vt_tokens, vt_ld == vt_tokens: the padding columns "
+               "slh_transpose_heads zero-fills are not written here, so there must be none; 16-byte aligned; no GEGLU)", col_align, token_align);
+    return 0;
+}
+
+// What the 64 x 160 tile and the tiles of gemm7.hip both are: whole tiles of a dense single-source product with packed weights, results
+// stored in 16-byte row segments, operands read in aligned quads; an adapter only fused in, in the forward form
+int gemm_check_whole_tiles(const slh_gemm_desc* d, const GemmTile& t, int w_align) {
+    GEMM_CHECK(d->mode == 0 && !d->a1 && !d->ca1 && d->w_layout == 1, "this tile runs dense single-source products with packed weights (w_layout = 1) only");
+    GEMM_CHECK(d->M % t.bm == 0 && d->N % t.bn == 0, "this tile needs M %% %d == 0 and N %% %d == 0 (M=%d N=%d)", t.bm, t.bn, d->M, d->N);
+    GEMM_CHECK(!d->lora_t && !d->rowbias && !d->xa_k && !d->geglu_pre && d->geglu != 1 && d->geglu != 2,
+               "this tile takes no row bias, external T, geglu = 1 / 2, geglu_pre or cross-attention");
+    GEMM_CHECK(d->ldc % 8 == 0 && ((uintptr_t)d->c & 15) == 0 && ((uintptr_t)d->a0 & 15) == 0 && ((uintptr_t)d->w & (w_align - 1)) == 0 &&
+                   ((uintptr_t)d->residual & 7) == 0 && ((uintptr_t)d->bias & 7) == 0,
+               "this tile needs ldc %% 8 == 0, 16-byte aligned a0 / c, %d-byte aligned w, 8-byte aligned bias / residual", w_align);
+    if (d->lora_down)
+        GEMM_CHECK(!d->lora_up_rmajor && ((uintptr_t)d->lora_down & 15) == 0 && ((uintptr_t)d->lora_up & 7) == 0 && ((uintptr_t)d->lora_t_out & 15) == 0,
+                   "this tile takes a fused adapter in the forward form only; 16-byte aligned lora_down / lora_t_out, 8-byte aligned lora_up");
+    else
+        GEMM_CHECK(!d->lora_t_out, "lora_t_out without lora_down");
+    return 0;
+}
+
+// gemm.hip / gemm8p.hip: every option exists; which tiles take which
+static int gemm_ring_check(const slh_gemm_desc* d, const GemmTile& t) {
+    const bool pp = t.family == GEMM_PINGPONG;
+    GEMM_CHECK(d->w_layout == 0 || d->w_layout == 1, "bad w_layout");
+    GEMM_CHECK(!pp || !d->lora_down || t.mi == 1, "the 256 x 256 tile does not take a fused adapter (lora_down)");
+    GEMM_CHECK(!pp || !d->vt_out || t.mi == 4 || (t.ni == 4 && d->mode == 0),
+               "vt_out on the ping-pong tiles needs 256 x 256 (0x8042) or the dense 128 x 256 tile (0x8014)");
+    GEMM_CHECK(!pp || d->geglu != 2 || t.mi == 4, "the 128 x 64*NI ping-pong tiles have no GEGLU backward epilogue (geglu = 2)");
+    GEMM_CHECK(d->geglu != 1 || t.ni == 2, "geglu needs NI=2");
+    GEMM_CHECK(!d->ln_out || (t.ni == 2 && d->N % 64 == 0 && !d->vt_out), "ln_out needs a 128-column tile (NI = 2), N %% 64 == 0, no vt_out");
+    GEMM_CHECK(!(d->ln_in && d->lora_down) ||
+                   (pp && t.mi == 1 && t.ni <= 4 && !d->lora_up_rmajor && !d->lora_t_out && !d->ln_mr_out && t.splitk <= 1),
+               "ln_in with a fused adapter runs on the ping-pong 128 x 192 / 128 x 256 tiles (0x8013, 0x8014); forward form, no split-K");
+    return d->vt_out ? gemm_check_vt(d, t, 128, 8) : 0;
+}
+
 // Every check of slh_gemm except what the caller provisions once the tile is chosen (the split-K slab / ticket workspace and its slab
-// count, ln_lora_s / ln_lora_c): 0, or the status slh_gemm returns for d with slh_last_error saying why
-static int gemm_check(const slh_gemm_desc* d) {
+// count, ln_lora_s / ln_lora_c): 0 and the decoded tile, or the status slh_gemm returns for d with slh_last_error saying why.
+// Each contract stands here once; a family's own part says which options it has and on which tiles.
+static int gemm_check(const slh_gemm_desc* d, GemmTile& t) {
+    // ---- the product
     SLH_CHECK(d && d->a0 && d->w && d->c, "slh_gemm: null pointer");
     SLH_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "slh_gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
-    SLH_CHECK((d->tile >> 20) == 0, "slh_gemm: tile 0x%x uses reserved bits (20 and up must be zero)", d->tile);
     SLH_CHECK(d->K % 64 == 0, "slh_gemm: K=%d must be a multiple of 64", d->K);
     SLH_CHECK(d->N % 4 == 0, "slh_gemm: N=%d must be a multiple of 4", d->N);
     SLH_CHECK(d->ca0 % 64 == 0 && d->ca1 % 64 == 0, "slh_gemm: channel counts must be multiples of 64");
@@ -586,165 +687,108 @@ static int gemm_check(const slh_gemm_desc* d) {
         SLH_CHECK(d->src_xform >= 0 && d->src_xform <= 2, "slh_gemm: bad src_xform");
         SLH_CHECK(d->M == d->batch * d->ho * d->wo, "slh_gemm: conv M mismatch");
     }
+    SLH_CHECK(d->geglu >= 0 && d->geglu <= 3, "slh_gemm: geglu is 0, 1 / 3 (forward epilogue, 32 | 32 or 16 | 16 weight blocks) or 2 (backward form)");
+    // ---- the tile, and its family's part
+    if (gemm_tile_decode(d, &t)) return -1;
+    const int rc = t.family == GEMM_FOURWAVE ? gemm7_check(d, t) : t.family == GEMM_64X160 ? gemm5_check(d, t) : gemm_ring_check(d, t);
+    if (rc) return rc;
+    // ---- adapters
     if (d->lora_down) {
-        SLH_CHECK(!d->lora_t && d->lora_up && d->lora_scale && !d->geglu, "slh_gemm: fused lora_down excludes an external T / geglu");
+        GEMM_CHECK(!d->lora_t && d->lora_up && d->lora_scale && !d->geglu, "fused lora_down excludes an external T / geglu");
         if (d->lora_up_rmajor) {
             // backward-data form: lora_down = the k-major copy of the up matrices ([rank][K], block-diagonal over a fused
             // q|k|v group), lora_up = the down matrices as stored ([rank][N]); U = dY . B leaves through lora_t_out
-            SLH_CHECK(d->lora_groups == 1 && (d->lora_rank == 4 || d->lora_rank == 8 || d->lora_rank == 12),
-                      "slh_gemm: fused r-major lora needs groups = 1, rank in {4, 8, 12}");
+            GEMM_CHECK(d->lora_groups == 1 && (d->lora_rank == 4 || d->lora_rank == 8 || d->lora_rank == 12),
+                       "fused r-major lora needs groups = 1, rank in {4, 8, 12}");
         } else {
-            SLH_CHECK(d->lora_groups >= 1 && d->lora_groups <= 3 && d->lora_rank == 4 * d->lora_groups &&
-                          d->N % d->lora_groups == 0 && (d->N / d->lora_groups) % 4 == 0,
-                      "slh_gemm: fused lora needs rank = 4 * groups");
+            GEMM_CHECK(d->lora_groups >= 1 && d->lora_groups <= 3 && d->lora_rank == 4 * d->lora_groups &&
+                           d->N % d->lora_groups == 0 && (d->N / d->lora_groups) % 4 == 0,
+                       "fused lora needs rank = 4 * groups");
         }
-        if (d->lora_t_out) SLH_CHECK(d->ld_t >= d->lora_rank && d->ld_t % 4 == 0, "slh_gemm: ld_t for lora_t_out");
+        if (d->lora_t_out) GEMM_CHECK(d->ld_t >= d->lora_rank && d->ld_t % 4 == 0, "ld_t for lora_t_out");
     }
     if (d->lora_t) {
-        SLH_CHECK(d->lora_up && d->lora_scale, "slh_gemm: lora pointers");
-        SLH_CHECK(d->lora_groups >= 1 && d->lora_groups <= 3 && d->N % d->lora_groups == 0 &&
-                      d->ld_t >= 4 * d->lora_groups && d->ld_t % 4 == 0,
-                  "slh_gemm: bad lora grouping");
+        GEMM_CHECK(d->lora_up && d->lora_scale, "lora pointers");
+        GEMM_CHECK(d->lora_groups >= 1 && d->lora_groups <= 3 && d->N % d->lora_groups == 0 &&
+                       d->ld_t >= 4 * d->lora_groups && d->ld_t % 4 == 0,
+                   "bad lora grouping");
         if (d->lora_up_rmajor)
-            SLH_CHECK(d->lora_groups == 1 && (d->lora_rank == 4 || d->lora_rank == 8 || d->lora_rank == 12) &&
-                          d->ld_t >= d->lora_rank,
-                      "slh_gemm: r-major lora_up needs groups=1 and rank in {4,8,12}");
-        SLH_CHECK((d->N / d->lora_groups) % 4 == 0, "slh_gemm: lora group width");
+            GEMM_CHECK(d->lora_groups == 1 && (d->lora_rank == 4 || d->lora_rank == 8 || d->lora_rank == 12) &&
+                           d->ld_t >= d->lora_rank,
+                       "r-major lora_up needs groups=1 and rank in {4,8,12}");
+        GEMM_CHECK((d->N / d->lora_groups) % 4 == 0, "lora group width");
     }
-    if (d->rowbias) SLH_CHECK(d->rows_per_sample > 0 && d->ld_rowbias % 4 == 0, "slh_gemm: rowbias");
-    if (d->residual) SLH_CHECK(d->ld_res % 4 == 0, "slh_gemm: ld_res");
-    if (d->geglu == 1) SLH_CHECK(d->N % 64 == 0 && !d->lora_t && !d->residual && !d->rowbias, "slh_gemm: geglu constraints");
+    // ---- epilogue options
+    if (d->rowbias) GEMM_CHECK(d->rows_per_sample > 0 && d->ld_rowbias % 4 == 0, "rowbias");
+    if (d->residual) GEMM_CHECK(d->ld_res % 4 == 0, "ld_res");
+    if (d->geglu == 1) GEMM_CHECK(d->N % 64 == 0 && !d->lora_t && !d->residual && !d->rowbias, "geglu constraints");
     if (d->geglu == 3)
-        SLH_CHECK(d->N % 32 == 0 && !d->lora_t && !d->lora_down && !d->residual && !d->rowbias && !d->geglu_pre && !d->vt_out && !d->ln_out,
-                  "slh_gemm: geglu = 3 (16 | 16 weight blocks) needs N %% 32 == 0 and excludes adapters, residual, row bias, geglu_pre, vt_out, ln_out");
-    SLH_CHECK(d->geglu >= 0 && d->geglu <= 3, "slh_gemm: geglu is 0, 1 / 3 (forward epilogue, 32 | 32 or 16 | 16 weight blocks) or 2 (backward form)");
-
-    {
-        // a tile code names a kernel or is refused: every nibble of bits 0-15 is either read by the dispatch or must be zero
-        const int fam = (d->tile >> 12) & 15, st = (d->tile >> 8) & 15, code = d->tile & 0xffff;
-        SLH_CHECK(fam == 0 || fam == 2 || fam == 4 || fam == 5 || fam == 7 || fam == 8,
-                  "slh_gemm: tile 0x%x: bits 12-15 are 0 | 2 (4 waves), 4 (8 waves), 8 (ping-pong), 5 (64 x 160) or 7 (gemm7.hip)", d->tile);
-        SLH_CHECK(code == 0 || fam == 5 || fam == 7 || ((code >> 4) & 15) != 0,
-                  "slh_gemm: tile 0x%x names no block tile (MI = 0): bits 0-15 are all zero (heuristic) or a complete tile code", d->tile);
-        if (fam == 5)
-            SLH_CHECK((d->tile & 0xfff) == 0x425 || (d->tile & 0xfff) == 0x525,
-                      "slh_gemm: the 64 x 160 tile is 0x5425 (4 ring slots) or 0x5525 (5 ring slots), not 0x%x", code);
-        if ((fam == 0 || fam == 2 || fam == 4) && code)
-            SLH_CHECK(st == 0 || st == 2 || st == 3 || st == 4,
-                      "slh_gemm: tile 0x%x: bits 8-11 (ring slots) are 0 | 2 (double buffer), 3 or 4", d->tile);
-        if (fam == 8) SLH_CHECK(st == 0, "slh_gemm: tile 0x%x: bits 8-11 of a ping-pong tile (0x8042, 0x801<NI>) must be zero", d->tile);
-    }
-    if (((d->tile >> 12) & 15) == 7) {
-        SLH_CHECK(gemm7_tile_ok(d),
-                  "slh_gemm: the tiles of gemm7.hip (0x7<S><XB><WB>: 0x7648 = 128 x 256, 0x7645 = 128 x 160, 0x748a = 256 x 320) run dense "
-                  "single-source products with packed weights, M %% (32 XB) == 0, N %% (32 WB) == 0, K >= 32 S; bias / residual / ln_out / ln_in / "
-                  "fused adapter (128 x 256) / vt_out / geglu = 3 only (256 x 320: bias / residual / ln_in / geglu = 3) (tile 0x%x M=%d N=%d K=%d)",
-                  d->tile, d->M, d->N, d->K);
-        return 0;
-    }
-    if (((d->tile >> 12) & 15) == 5) {
-        SLH_CHECK(gemm5_tile_ok(d),
-                  "slh_gemm: the 64 x 160 tile (0x5xxx) runs dense single-source products with packed weights, M %% 64 == 0, N %% 160 == 0, "
-                  "bias / residual / ln_out / ln_in / one fused rank-4 adapter only (M=%d N=%d K=%d)", d->M, d->N, d->K);
-        SLH_CHECK(((d->tile >> 16) & 15) <= 1, "slh_gemm: the 64 x 160 tile has no split-K");
-        return 0;
-    }
-    int MI = 2, NI = 2, WM = 2;
-    pick_tile(d, MI, NI, WM);
-    if (WM == 8) {
-        SLH_CHECK((MI == 4 && NI == 2) || (MI == 1 && NI >= 3 && NI <= 5),
-                  "slh_gemm: ping-pong tiles are 256 x 256 (0x8042) or 128 x 64*NI (0x801<NI>, NI = 3..5)");
-        SLH_CHECK(!d->lora_down || MI == 1, "slh_gemm: the 256 x 256 tile does not take a fused adapter (lora_down)");
-        SLH_CHECK(!d->vt_out || (MI == 4 && NI == 2) || (MI == 1 && NI == 4 && d->mode == 0),
-                  "slh_gemm: vt_out on the ping-pong tiles needs 256 x 256 (0x8042) or the dense 128 x 256 tile (0x8014)");
-        // (geglu = 1 and ln_out need NI = 2, below)
-        SLH_CHECK(d->geglu != 2 || MI == 4, "slh_gemm: the 128 x 64*NI ping-pong tiles have no GEGLU backward epilogue (geglu = 2)");
-    } else {
-        SLH_CHECK((MI == 1 || MI == 2) && (NI == 1 || NI == 2), "slh_gemm: bad tile");
-        SLH_CHECK(WM == 2 || NI == 2 || MI == 1, "slh_gemm: 8-wave tiles are 128x64, 128x128 or 256x128");
-    }
-    SLH_CHECK(d->w_layout == 0 || d->w_layout == 1, "slh_gemm: bad w_layout");
-    if (d->geglu == 1) SLH_CHECK(NI == 2, "slh_gemm: geglu needs NI=2");
-    if (d->vt_out) {
-        SLH_CHECK(d->vt_D > 0 && d->vt_D % 64 == 0 && d->vt_col0 % 128 == 0 && d->vt_col0 < d->N && d->vt_heads > 0 &&
-                      (d->N - d->vt_col0) == d->vt_heads * d->vt_D && d->vt_tokens % 8 == 0 && d->M % d->vt_tokens == 0 &&
-                      d->vt_ld % 8 == 0 && d->vt_ld == d->vt_tokens && !d->geglu && ((uintptr_t)d->vt_out & 15) == 0,
-                  "slh_gemm: vt_out constraints (vt_D %% 64, vt_col0 %% 128, vt_tokens %% 8, M %% vt_tokens, vt_ld == vt_tokens: the padding columns "
-                  "slh_transpose_heads zero-fills are not written here, so there must be none; 16-byte aligned; no GEGLU)");
-    }
-    if (d->ln_out) {
-        SLH_CHECK(NI == 2 && d->N % 64 == 0 && !d->geglu && !d->vt_out,
-                  "slh_gemm: ln_out needs a 128-column tile (NI = 2), N %% 64 == 0, no GEGLU / vt_out");
-        SLH_CHECK(((uintptr_t)d->ln_out & 7) == 0, "slh_gemm: ln_out alignment");
-    }
-    if (d->ln_in) {
-        SLH_CHECK(d->mode == 0 && !d->a1 && d->ln_s && d->ln_b && !d->bias && !d->lora_t,
-                  "slh_gemm: ln_in needs a dense single-source product, ln_s / ln_b, no bias (folded into ln_b), no external T");
-        if (d->lora_down)
-            SLH_CHECK(WM == 8 && MI == 1 && NI <= 4 && !d->lora_up_rmajor && !d->lora_t_out && !d->ln_mr_out && ((d->tile >> 16) & 15) <= 1,
-                      "slh_gemm: ln_in with a fused adapter runs on the ping-pong 128 x 192 / 128 x 256 tiles (0x8013, 0x8014); forward form, "
-                      "no split-K");
-        SLH_CHECK(d->ln_in_chunks >= 1 && d->ln_in_chunks <= 20 && d->K % d->ln_in_chunks == 0 &&
-                      (d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks),
-                  "slh_gemm: ln_in_chunks must be K / 64 (producer on a 64 / 128-column tile) or K / 80 (producer on the 64 x 160 tile), <= 20");
-        SLH_CHECK(((uintptr_t)d->ln_in & 7) == 0 && ((uintptr_t)d->ln_s & 15) == 0 && ((uintptr_t)d->ln_b & 15) == 0,
-                  "slh_gemm: ln_in / ln_s / ln_b alignment");
-    }
-    SLH_CHECK(!d->vt_also_c || d->vt_out, "slh_gemm: vt_also_c without vt_out");
-    SLH_CHECK(!d->ln_mr_out || d->ln_in, "slh_gemm: ln_mr_out without ln_in");
-    SLH_CHECK(!d->geglu_pre || (d->geglu && d->ld_pre >= (d->geglu == 2 ? 2 * d->N : d->N) && d->ld_pre % 4 == 0 &&
-                                ((uintptr_t)d->geglu_pre & 7) == 0),
-              "slh_gemm: geglu_pre needs the GEGLU epilogue, ld_pre >= N (2N in the backward form), 8-byte alignment");
+        GEMM_CHECK(d->N % 32 == 0 && !d->lora_t && !d->lora_down && !d->residual && !d->rowbias && !d->geglu_pre && !d->vt_out && !d->ln_out,
+                   "geglu = 3 (16 | 16 weight blocks) needs N %% 32 == 0 and excludes adapters, residual, row bias, geglu_pre, vt_out, ln_out");
+    GEMM_CHECK(!d->geglu_pre || (d->geglu && d->ld_pre >= (d->geglu == 2 ? 2 * d->N : d->N) && d->ld_pre % 4 == 0 &&
+                                 ((uintptr_t)d->geglu_pre & 7) == 0),
+               "geglu_pre needs the GEGLU epilogue, ld_pre >= N (2N in the backward form), 8-byte alignment");
     if (d->geglu == 2)
-        SLH_CHECK(d->geglu_pre && d->N % 32 == 0 && d->ldc >= 2 * d->N && d->ldc % 4 == 0 && !d->bias && !d->rowbias && !d->residual &&
-                      !d->lora_t && !d->lora_down && !d->vt_out && !d->ln_in && !d->ln_out,
-                  "slh_gemm: geglu = 2 (backward form) needs geglu_pre, N %% 32 == 0, ldc >= 2N and a bare product");
-    int per;
-    const int splitk = gemm_splitk(d, per);
-    if (splitk > 1) {
-        SLH_CHECK((long)splitk * ((d->M + 255) / 256 * 256L) * ((d->N + 255) / 256 * 256L) * 4 < (1L << 31),
-                  "slh_gemm: split-K slabs beyond 2 GB");
-        if (WM == 8) {
-            // the slab workspace is sized by contract (include/sliders_hip.h: roundup(M, 256) x roundup(N, 128) floats per slice)
-            const int bm = MI == 1 ? 128 : 256, bn = 64 * NI * (MI == 4 ? 2 : 1);
-            SLH_CHECK((long)((d->M + bm - 1) / bm) * bm * ((d->N + bn - 1) / bn) * bn <= ((d->M + 255) / 256 * 256L) * ((d->N + 127) / 128 * 128L),
-                      "slh_gemm: split-K slabs of %d x %d tiles exceed the workspace contract for M=%d N=%d", bm, bn, d->M, d->N);
-        }
+        GEMM_CHECK(d->geglu_pre && d->N % 32 == 0 && d->ldc >= 2 * d->N && d->ldc % 4 == 0 && !d->bias && !d->rowbias && !d->residual &&
+                       !d->lora_t && !d->lora_down && !d->vt_out && !d->ln_in && !d->ln_out,
+                   "geglu = 2 (backward form) needs geglu_pre, N %% 32 == 0, ldc >= 2N and a bare product");
+    GEMM_CHECK(!d->vt_also_c || d->vt_out, "vt_also_c without vt_out");
+    // ---- LayerNorm fold: producer side, consumer side
+    if (d->ln_out) GEMM_CHECK(!d->geglu && ((uintptr_t)d->ln_out & 7) == 0, "ln_out needs 8-byte alignment and no GEGLU");
+    if (d->ln_in) {
+        GEMM_CHECK(d->mode == 0 && !d->a1 && d->ln_s && d->ln_b && !d->bias && !d->lora_t,
+                   "ln_in needs a dense single-source product, ln_s / ln_b, no bias (folded into ln_b), no external T");
+        GEMM_CHECK(d->ln_in_chunks >= 1 && d->ln_in_chunks <= 20 && (d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks),
+                   "ln_in_chunks must be K / 64 (producer on a 64 / 128-column tile) or K / 80 (producer on the 64 x 160 tile), <= 20");
+        GEMM_CHECK(((uintptr_t)d->ln_in & 7) == 0 && ((uintptr_t)d->ln_s & 15) == 0 && ((uintptr_t)d->ln_b & 15) == 0,
+                   "ln_in / ln_s / ln_b alignment");
     }
+    GEMM_CHECK(!d->ln_mr_out || d->ln_in, "ln_mr_out without ln_in");
+    // ---- split-K
+    int per;
+    const int splitk = gemm_splitk(d, t, per);
+    if (splitk > 1) {
+        GEMM_CHECK((long)splitk * ((d->M + 255) / 256 * 256L) * ((d->N + 255) / 256 * 256L) * 4 < (1L << 31), "split-K slabs beyond 2 GB");
+        // the slab workspace is sized by contract (include/sliders_hip.h: roundup(M, 256) x roundup(N, 128) floats per slice)
+        GEMM_CHECK((long)((d->M + t.bm - 1) / t.bm) * t.bm * ((d->N + t.bn - 1) / t.bn) * t.bn <= ((d->M + 255) / 256 * 256L) * ((d->N + 127) / 128 * 128L),
+                   "split-K slabs of %d x %d tiles exceed the workspace contract for M=%d N=%d", t.bm, t.bn, d->M, d->N);
+    }
+    // ---- cross-attention behind the query projection
     if (d->xa_k) {
-        SLH_CHECK(WM == 4 && MI == 1 && NI == 2 && ((d->tile >> 8) & 15) == 4 && splitk == 1,
-                  "slh_gemm: the fused cross-attention runs on the 128 x 128 8-wave ring tile (0x4412), no split-K");
-        SLH_CHECK(d->mode == 0 && !d->lora_down && !d->lora_t && !d->residual && !d->rowbias && !d->geglu && !d->ln_out && !d->vt_out,
-                  "slh_gemm: xa_k excludes adapters, residual, row bias, GEGLU, ln_out, vt_out");
-        SLH_CHECK(d->xa_vt && d->N % 64 == 0 && d->xa_tk >= 1 && d->xa_tk <= 96 && d->xa_tq > 0 && d->xa_tq % 128 == 0 &&
-                      d->M % d->xa_tq == 0 && d->xa_ldvt >= 128 && d->xa_ldvt % 8 == 0 && d->xa_ldk % 8 == 0 &&
-                      d->xa_vt_heads >= d->N / 64 && ((uintptr_t)d->xa_k & 15) == 0 && ((uintptr_t)d->xa_vt & 15) == 0,
-                  "slh_gemm: xa_* need head dim 64 (N %% 64 == 0), 1 <= xa_tk <= 96, xa_tq %% 128 == 0, M %% xa_tq == 0, "
-                  "xa_ldvt >= 128 (two 64-key tiles are staged), 16-byte aligned keys / values");
+        GEMM_CHECK(t.family == GEMM_RING && t.wm == 4 && t.mi == 1 && t.ni == 2 && t.slots == 4 && splitk == 1,
+                   "the fused cross-attention runs on the 128 x 128 8-wave ring tile (0x4412), no split-K");
+        GEMM_CHECK(d->mode == 0 && !d->lora_down && !d->lora_t && !d->residual && !d->rowbias && !d->geglu && !d->ln_out && !d->vt_out,
+                   "xa_k excludes adapters, residual, row bias, GEGLU, ln_out, vt_out");
+        GEMM_CHECK(d->xa_vt && d->N % 64 == 0 && d->xa_tk >= 1 && d->xa_tk <= 96 && d->xa_tq > 0 && d->xa_tq % 128 == 0 &&
+                       d->M % d->xa_tq == 0 && d->xa_ldvt >= 128 && d->xa_ldvt % 8 == 0 && d->xa_ldk % 8 == 0 &&
+                       d->xa_vt_heads >= d->N / 64 && ((uintptr_t)d->xa_k & 15) == 0 && ((uintptr_t)d->xa_vt & 15) == 0,
+                   "xa_* need head dim 64 (N %% 64 == 0), 1 <= xa_tk <= 96, xa_tq %% 128 == 0, M %% xa_tq == 0, "
+                   "xa_ldvt >= 128 (two 64-key tiles are staged), 16-byte aligned keys / values");
     }
     return 0;
 }
 
-extern "C" int slh_gemm_tile_ok(const slh_gemm_desc* d) { return gemm_check(d) == 0; }
+extern "C" int slh_gemm_tile_ok(const slh_gemm_desc* d) {
+    GemmTile t;
+    return gemm_check(d, t) == 0;
+}
 
 extern "C" int slh_gemm_ln_chunk_cols(const slh_gemm_desc* d) {
-    if (!d || !d->ln_out || gemm_check(d) != 0) return 0;
-    const int fam = (d->tile >> 12) & 15;
-    if (fam == 5) return 80;                                    // a wave of the 64 x 160 tile owns 80 columns
-    if (fam == 7) return (d->tile & 15) == 5 ? 80 : 64;         // four-wave tiles: 0x7645's waves own 80 columns, 0x7648's 128
-    return 64;                                                  // the 128-column tiles of gemm.hip / gemm8p.hip
+    GemmTile t;
+    if (!d || !d->ln_out || gemm_check(d, t) != 0) return 0;
+    return t.bn == 160 ? 80 : 64;      // a wave of the 64 x 160 tile and of 0x7645 owns 80 columns; every other tile's chunks are 64 wide
 }
 
 extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
-    const int rc = gemm_check(d);
+    GemmTile t;
+    const int rc = gemm_check(d, t);
     if (rc) return rc;
     SLH_CHECK(!(d->ln_in && d->lora_down) || (d->ln_lora_s && d->ln_lora_c),
               "slh_gemm: ln_in with a fused adapter needs ln_lora_s / ln_lora_c (lora_down = A . gamma)");
-    if (((d->tile >> 12) & 15) == 7) return slh_gemm7_launch(d, stream);      // the four-wave tiles (gemm7.hip)
-    if (((d->tile >> 12) & 15) == 5) return slh_gemm5_launch(d, stream);      // the 64 x 160 tile (gemm5.hip)
-    int MI = 2, NI = 2, WM = 2;
-    pick_tile(d, MI, NI, WM);
+    if (t.family == GEMM_FOURWAVE) return slh_gemm7_launch(d, t, stream);
+    if (t.family == GEMM_64X160) return slh_gemm5_launch(d, t, stream);
     GemmArgs a;
+    memset(&a, 0, sizeof(a));      // padding included: a field this function forgets is zero in the kernel, and the query hashes these bytes
     a.a0 = (const __bf16*)d->a0; a.a1 = (const __bf16*)d->a1; a.w = (const __bf16*)d->w;
     a.bias = (const __bf16*)d->bias; a.rowbias = (const __bf16*)d->rowbias; a.lora_t = d->lora_t;
     a.lora_up = (const __bf16*)d->lora_up; a.lora_scale = d->lora_scale;
@@ -768,7 +812,7 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
     a.ln_mr_out = d->ln_mr_out;
     a.geglu_pre = (__bf16*)d->geglu_pre; a.ld_pre = d->ld_pre;
     a.vt_also_c = d->vt_also_c;
-    // same-XCD slab reads (gemm_common.h, split-K epilogue): gfx950 only, SLIDERS_SPLITK_LOCAL=0 turns them off
+    // same-XCD slab reads (gemm_common.h, split-K epilogue): gfx950 only, SLIDERS_SPLITK_LOCAL=0 turns them off (a query answers 1)
     static const int splitk_local_ok = [] {
         const char* e = getenv("SLIDERS_SPLITK_LOCAL");
         if (e && atoi(e) == 0) return 0;
@@ -777,8 +821,8 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
         return strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 0;
     }();
-    a.splitk_local = splitk_local_ok;
-    a.splitk = gemm_splitk(d, a.kper);
+    a.splitk_local = slh_name_mode() ? 1 : splitk_local_ok;
+    a.splitk = gemm_splitk(d, t, a.kper);
     if (a.splitk > 1) {
         SLH_CHECK(d->splitk_c32, "slh_gemm: split-K needs the fp32 slab workspace splitk_c32");
         SLH_CHECK(d->splitk_slabs >= a.splitk, "slh_gemm: split-K into %d slices but the workspace holds %d slabs", a.splitk,
@@ -793,34 +837,26 @@ extern "C" int slh_gemm(const slh_gemm_desc* d, slh_stream_t stream) {
     a.xa_k = (const __bf16*)d->xa_k; a.xa_vt = (const __bf16*)d->xa_vt;
     a.xa_tk = d->xa_tk; a.xa_tq = d->xa_tq; a.xa_ldk = d->xa_ldk; a.xa_ldvt = d->xa_ldvt; a.xa_vt_heads = d->xa_vt_heads;
     a.xa_scale = d->xa_scale;
-    a.pf_ptr = nullptr; a.pf_bytes = 0; a.pf_blocks = 0;
-    if (WM == 8) {
-        const int bm = MI == 1 ? 128 : 256, bn = 64 * NI * (MI == 4 ? 2 : 1);
-        a.tiles_m = (d->M + bm - 1) / bm;
-        a.tiles_n = (d->N + bn - 1) / bn;
-        a.group_m = pick_group_m(d, a.tiles_m);
-        return launch_gemm8p(a, d->mode, MI == 4 ? 0 : NI, (hipStream_t)stream);
-    }
-    a.tiles_m = (d->M + 32 * MI * WM - 1) / (32 * MI * WM);
-    a.tiles_n = (d->N + 64 * NI - 1) / (64 * NI);
+    a.tiles_m = (d->M + t.bm - 1) / t.bm;
+    a.tiles_n = (d->N + t.bn - 1) / t.bn;
     a.group_m = pick_group_m(d, a.tiles_m);
-    if (d->pf_ptr && d->pf_bytes >= 16 && WM == 4 && MI == 1 && NI == 2 && ((d->tile >> 8) & 15) == 4) {
+    hipStream_t s = (hipStream_t)stream;
+    if (t.family == GEMM_PINGPONG) return launch_gemm8p(a, d->mode, t.mi == 4 ? 0 : t.ni, s);
+    if (d->pf_ptr && d->pf_bytes >= 16 && t.wm == 4 && t.mi == 1 && t.ni == 2 && t.slots == 4) {
         // the weight touch is a hint: taken only on the 128 x 128 ring tile (0x4412: one workgroup per CU) and only when the launch
         // leaves CUs idle
         SLH_CHECK(((uintptr_t)d->pf_ptr & 15) == 0, "slh_gemm: pf_ptr must be 16-byte aligned");
         const int idle = slh_ncu() - a.tiles_m * a.tiles_n * (a.splitk > 1 ? a.splitk : 1);
         if (idle >= 16) { a.pf_ptr = d->pf_ptr; a.pf_bytes = (long)d->pf_bytes; a.pf_blocks = idle < 64 ? idle : 64; }
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int stages = (d->tile >> 8) & 15;   // tile = (WM<<12)|(stages<<8)|(MI<<4)|NI ; stages 0/2 = double buffer
     if (d->xa_k) return launch_gemm_xa(a, s);
-    if (WM == 4) {
-        if (MI == 2) return launch_gemm<2, 2, 4>(a, d->mode, stages, s);   // 256 x 128, 8 waves
-        if (NI == 1) return launch_gemm<1, 1, 4>(a, d->mode, stages, s);   // 128 x 64, 8 waves
-        return launch_gemm<1, 2, 4>(a, d->mode, stages, s);                // 128 x 128, 8 waves
+    if (t.wm == 4) {
+        if (t.mi == 2) return launch_gemm<2, 2, 4>(a, d->mode, t.slots, s);   // 256 x 128, 8 waves
+        if (t.ni == 1) return launch_gemm<1, 1, 4>(a, d->mode, t.slots, s);   // 128 x 64, 8 waves
+        return launch_gemm<1, 2, 4>(a, d->mode, t.slots, s);                  // 128 x 128, 8 waves
     }
-    if (MI == 2 && NI == 2) return launch_gemm<2, 2, 2>(a, d->mode, stages, s);
-    if (MI == 2 && NI == 1) return launch_gemm<2, 1, 2>(a, d->mode, stages, s);
-    if (MI == 1 && NI == 2) return launch_gemm<1, 2, 2>(a, d->mode, stages, s);
-    return launch_gemm<1, 1, 2>(a, d->mode, stages, s);
+    if (t.mi == 2 && t.ni == 2) return launch_gemm<2, 2, 2>(a, d->mode, t.slots, s);
+    if (t.mi == 2 && t.ni == 1) return launch_gemm<2, 1, 2>(a, d->mode, t.slots, s);
+    if (t.mi == 1 && t.ni == 2) return launch_gemm<1, 2, 2>(a, d->mode, t.slots, s);
+    return launch_gemm<1, 1, 2>(a, d->mode, t.slots, s);
 }

@@ -17,6 +17,8 @@
 // Replaces F.linear inside diffusers' Attention.to_out[0] / Transformer2DModel.proj_out / FeedForward.net[2] as called from
 // trainscripts/textsliders/train_util.py:242-247.
 #include "gemm_common.h"
+#include "gemm_dispatch.h"
+#include <cstring>
 
 using namespace slh_gemm_detail;
 
@@ -350,67 +352,39 @@ __global__ __launch_bounds__(256) void gemm5_kernel(const G5Args p) {
 
 }  // namespace
 
-// group_m of the grouped tile order: an XCD's run of tiles_m * tiles_n / 8 tiles is gm row tiles x (run / gm) column tiles; pick the
-// gm (power of two) that minimises the operand rows it pulls through its L2 (64 * gm of X + 160 * run / gm of W)
-static int g5_group_m(int tiles_m, int tiles_n) {
-    const int run = (tiles_m * tiles_n + 7) / 8;
-    int best = 1;
-    long best_cost = -1;
-    for (int gm = 1; gm <= tiles_m; gm *= 2) {
-        const int gn = (run + gm - 1) / gm;
-        const long cost = 64L * gm + 160L * (gn < tiles_n ? gn : tiles_n);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = gm; }
-    }
-    return best;
+// the 64 x 160 tile's part of the rule (gemm.hip: gemm_check): bias / residual / ln_out / ln_in / one fused rank-4 adapter only
+int gemm5_check(const slh_gemm_desc* d, const GemmTile& t) {
+    if (const int rc = gemm_check_whole_tiles(d, t, 16)) return rc;
+    GEMM_CHECK(t.splitk <= 1, "this tile has no split-K");
+    GEMM_CHECK(!d->geglu && !d->vt_out, "this tile takes no GEGLU epilogue and no vt_out");
+    GEMM_CHECK(!d->lora_down || (d->lora_groups == 1 && d->lora_rank == 4 && !d->ln_in && !d->ln_lora_s),
+               "this tile takes one fused rank-4 adapter, not behind a folded LayerNorm (ln_in, ln_lora_s)");
+    GEMM_CHECK(((uintptr_t)d->ln_mr_out & 7) == 0, "ln_mr_out alignment");
+    return 0;
 }
 
-// the 64 x 160 tile's part of slh_gemm_tile_ok (gemm.hip: tile codes whose bits 12-15 are 5; split-K is refused there)
-bool gemm5_tile_ok(const slh_gemm_desc* d) {
-    if (d->mode != 0 || d->a1 || d->ca1 || d->w_layout != 1) return 0;
-    if (d->M <= 0 || d->M % 64 || d->N <= 0 || d->N % 160 || d->K < 64 || d->K % 64 || d->ca0 != d->K) return 0;
-    if (d->lora_t || d->rowbias || d->geglu || d->vt_out || d->vt_also_c || d->xa_k || d->geglu_pre) return 0;
-    if (d->ln_in) {          // consumer side of a folded LayerNorm (as the 128-row tiles: gemm7.hip), without an adapter
-        if (!d->ln_s || !d->ln_b || d->bias || d->lora_down || ((uintptr_t)d->ln_in & 7) || ((uintptr_t)d->ln_s & 15) || ((uintptr_t)d->ln_b & 15)) return 0;
-        if (d->ln_in_chunks < 1 || d->ln_in_chunks > 20 || !(d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks)) return 0;
-        if (d->ln_mr_out && ((uintptr_t)d->ln_mr_out & 7)) return 0;
-    } else if (d->ln_mr_out) {
-        return 0;
-    }
-    if (d->lora_down) {      // one fused rank-4 adapter, forward form
-        if (!d->lora_up || !d->lora_scale || d->lora_up_rmajor || d->lora_groups != 1 || d->lora_rank != 4 || d->ln_lora_s) return 0;
-        if (((uintptr_t)d->lora_down & 15) || ((uintptr_t)d->lora_up & 7)) return 0;
-        if (d->lora_t_out && (d->ld_t < 4 || d->ld_t % 4 || ((uintptr_t)d->lora_t_out & 15))) return 0;
-    } else if (d->lora_t_out) {
-        return 0;
-    }
-    if (d->lda0 % 8 || d->ldc % 8 || ((uintptr_t)d->c & 15) || ((uintptr_t)d->a0 & 15) || ((uintptr_t)d->w & 15)) return 0;
-    if (d->residual && (d->ld_res % 4 || ((uintptr_t)d->residual & 7))) return 0;
-    if (d->bias && ((uintptr_t)d->bias & 7)) return 0;
-    if (d->ln_out && ((uintptr_t)d->ln_out & 7)) return 0;
-    return 1;
-}
-
-// slh_gemm (gemm.hip) has checked d with slh_gemm_tile_ok
-int slh_gemm5_launch(const slh_gemm_desc* d, slh_stream_t stream) {
+// slh_gemm (gemm.hip) has checked d
+int slh_gemm5_launch(const slh_gemm_desc* d, const GemmTile& t, slh_stream_t stream) {
     G5Args a;
+    memset(&a, 0, sizeof(a));      // padding included (gemm.hip: slh_gemm)
     a.a = (const __bf16*)d->a0; a.w = (const __bf16*)d->w; a.bias = (const __bf16*)d->bias; a.residual = (const __bf16*)d->residual;
     a.c = (__bf16*)d->c; a.ln_out = d->ln_out;
     a.lora_down = (const __bf16*)d->lora_down; a.lora_up = (const __bf16*)d->lora_up; a.lora_scale = d->lora_scale;
     a.lora_t_out = d->lora_t_out; a.ld_t = d->ld_t;
     a.ln_in = d->ln_in; a.ln_s = d->ln_s; a.ln_b = d->ln_b; a.ln_mr_out = d->ln_mr_out; a.ln_in_chunks = d->ln_in_chunks; a.ln_eps = d->ln_eps;
     a.lda = d->lda0; a.ldc = d->ldc; a.ld_res = d->ld_res; a.M = d->M; a.N = d->N; a.K = d->K;
-    a.tiles_m = d->M / G5_BM; a.tiles_n = d->N / G5_BN;
-    a.group_m = g5_group_m(a.tiles_m, a.tiles_n);
+    a.tiles_m = d->M / t.bm; a.tiles_n = d->N / t.bn;
+    a.group_m = gemm_group_m(a.tiles_m, a.tiles_n, t.bm, t.bn);
     static const int skew_knob = getenv("SLH_G5_SKEW") ? atoi(getenv("SLH_G5_SKEW")) : 1;      // A/B: 0 = every sibling walks its panels in the same order
     a.skew = skew_knob;
     const int grid = a.tiles_m * a.tiles_n;
     const hipStream_t st = (hipStream_t)stream;
-    if (((d->tile >> 8) & 15) == 5) {      // 5 ring slots
-        if (d->lora_down) slh_launch<gemm5_kernel<true, 5>>(grid, 256, st, a, "gemm5_kernel<true, 5>");
-        else slh_launch<gemm5_kernel<false, 5>>(grid, 256, st, a, "gemm5_kernel<false, 5>");
+    if (t.slots == 5) {
+        if (d->lora_down) slh_launch<gemm5_kernel<true, 5>>(grid, t.threads, st, a, "gemm5_kernel<true, 5>");
+        else slh_launch<gemm5_kernel<false, 5>>(grid, t.threads, st, a, "gemm5_kernel<false, 5>");
     } else {
-        if (d->lora_down) slh_launch<gemm5_kernel<true, 4>>(grid, 256, st, a, "gemm5_kernel<true, 4>");
-        else slh_launch<gemm5_kernel<false, 4>>(grid, 256, st, a, "gemm5_kernel<false, 4>");
+        if (d->lora_down) slh_launch<gemm5_kernel<true, 4>>(grid, t.threads, st, a, "gemm5_kernel<true, 4>");
+        else slh_launch<gemm5_kernel<false, 4>>(grid, t.threads, st, a, "gemm5_kernel<false, 4>");
     }
     SLH_LAUNCH_CHECK("slh_gemm (64 x 160 tile)");
     return 0;

@@ -31,6 +31,8 @@
 // Replaces F.linear inside diffusers' Attention (to_q | to_k | to_v) / FeedForward (GEGLU.proj) as called from
 // trainscripts/textsliders/train_util.py:242-247.
 #include "gemm_common.h"
+#include "gemm_dispatch.h"
+#include <cstring>
 
 using namespace slh_gemm_detail;
 
@@ -808,94 +810,46 @@ __global__ __launch_bounds__(512) void gemm7w_kernel(const G7Args p) {
 
 }  // namespace
 
-// group_m of the grouped tile order (gemm5.hip): the gm that minimises the operand rows an XCD pulls through its L2
-static int g7_group_m(int tiles_m, int tiles_n, int bm, int bn) {
-    const int run = (tiles_m * tiles_n + 7) / 8;
-    int best = 1;
-    long best_cost = -1;
-    for (int gm = 1; gm <= tiles_m; gm *= 2) {
-        const int gn = (run + gm - 1) / gm;
-        const long cost = (long)bm * gm + (long)bn * (gn < tiles_n ? gn : tiles_n);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = gm; }
-    }
-    return best;
+// the part of the rule (gemm.hip: gemm_check) of the tiles of this file.  All three: bias / residual / ln_in / geglu = 3; the 128-row
+// tiles also ln_out, vt_out; 0x7648 also a fused adapter of 1-3 column groups, every tile inside one group
+int gemm7_check(const slh_gemm_desc* d, const GemmTile& t) {
+    const int wb = t.ni;
+    if (const int rc = gemm_check_whole_tiles(d, t, 128)) return rc;
+    GEMM_CHECK(t.splitk == 0, "the tiles of gemm7.hip have no split-K (bits 16-19 must be zero)");
+    GEMM_CHECK(d->K / 32 >= t.slots, "K=%d is shorter than the ring of %d half K tiles", d->K, t.slots);
+    GEMM_CHECK(d->geglu != 3 || wb % 2 == 0, "geglu = 3 needs whole 16 | 16 blocks per wave: not on 0x7645");
+    GEMM_CHECK(t.bm != 256 || (!d->lora_down && !d->vt_out && !d->ln_out), "the 256 x 320 tile takes bias / residual / ln_in / geglu = 3 only");
+    GEMM_CHECK(!d->lora_down || (wb == 8 && d->lora_groups >= 1 && d->N % d->lora_groups == 0 && (d->N / d->lora_groups) % (16 * wb) == 0),
+               "a fused adapter runs on 0x7648 only, every 128-column half tile inside one column group");
+    GEMM_CHECK(d->ln_in || !d->ln_lora_s, "ln_lora_s without ln_in");
+    return d->vt_out ? gemm_check_vt(d, t, 16 * wb, t.bm) : 0;
 }
 
-static bool g7_shape(int tile, int& xb, int& wb, int& s) {
-    s = (tile >> 8) & 15; xb = (tile >> 4) & 15; wb = tile & 15;
-    // (a 128 x 320 four-wave instantiation, 0x754a, was measured and removed: it lost to the ping-pong tile in the pass and is
-    // superseded by the 256 x 320 tile - profiles/r06_gemm7_insitu_ab.txt, r06_tile_256x320.txt)
-    return (xb == 4 && wb == 8 && s == 6) || (xb == 4 && wb == 5 && s == 6) ||
-           (xb == 8 && wb == 10 && s == 4);      // 0x748a: 256 x 320 on eight compute waves
-}
-
-// the four-wave tiles' part of slh_gemm_tile_ok (gemm.hip: tile codes whose bits 12-15 are 7): 1 where the tile named by d->tile can run d
-bool gemm7_tile_ok(const slh_gemm_desc* d) {
-    int xb, wb, s;
-    if (((d->tile >> 12) & 15) != 7 || (d->tile >> 16) || !g7_shape(d->tile, xb, wb, s)) return 0;
-    const int bm = 32 * xb, bn = 32 * wb;
-    if (d->mode != 0 || d->a1 || d->ca1 || d->w_layout != 1) return 0;
-    if (d->M <= 0 || d->M % bm || d->N <= 0 || d->N % bn || d->K % 64 || d->K / 32 < s || d->ca0 != d->K) return 0;
-    if (d->lora_t || d->rowbias || d->xa_k || d->geglu_pre) return 0;
-    if (d->geglu && (d->geglu != 3 || wb % 2 || d->lora_down || d->residual || d->vt_out || d->ln_out || d->ldc % 8)) return 0;
-    if (d->lda0 % 8 || d->ldc % 8 || ((uintptr_t)d->c & 15) || ((uintptr_t)d->a0 & 15) || ((uintptr_t)d->w & 127)) return 0;
-    if (d->residual && (d->ld_res % 4 || ((uintptr_t)d->residual & 7))) return 0;
-    if (d->bias && ((uintptr_t)d->bias & 7)) return 0;
-    if (d->ln_out && (((uintptr_t)d->ln_out & 7) || d->geglu)) return 0;
-    if (d->ln_in) {
-        if (!d->ln_s || !d->ln_b || d->bias || ((uintptr_t)d->ln_in & 7) || ((uintptr_t)d->ln_s & 15) || ((uintptr_t)d->ln_b & 15)) return 0;
-        if (d->ln_in_chunks < 1 || d->ln_in_chunks > 20 || !(d->K == 64 * d->ln_in_chunks || d->K == 80 * d->ln_in_chunks)) return 0;
-    } else if (d->ln_mr_out || d->ln_lora_s) {
-        return 0;
-    }
-    if (xb == 8 && (d->lora_down || d->vt_out || d->ln_out)) return 0;      // the 256-row tile: bias / residual / ln_in / geglu = 3 only
-    if (d->lora_down) {      // fused adapter, forward form: rank 4 * groups <= 12, each tile inside one column group
-        if (wb != 8) return 0;                       // (instantiated on the 128 x 256 tile only)
-        if (!d->lora_up || !d->lora_scale || d->lora_up_rmajor || d->lora_groups < 1 || d->lora_groups > 3 ||
-            d->lora_rank != 4 * d->lora_groups || d->N % d->lora_groups || (d->N / d->lora_groups) % (16 * wb))
-            return 0;
-        if (((uintptr_t)d->lora_down & 15) || ((uintptr_t)d->lora_up & 7)) return 0;
-        if (d->lora_t_out && (d->ld_t < d->lora_rank || d->ld_t % 4 || ((uintptr_t)d->lora_t_out & 15))) return 0;
-    } else if (d->lora_t_out) {
-        return 0;
-    }
-    if (d->vt_out) {
-        if (d->geglu || d->vt_D <= 0 || d->vt_D % 64 || d->vt_col0 % (16 * wb) || d->vt_col0 >= d->N || d->vt_heads <= 0 ||
-            (d->N - d->vt_col0) != d->vt_heads * d->vt_D || d->vt_tokens % bm || d->M % d->vt_tokens || d->vt_ld % 8 ||
-            d->vt_ld != d->vt_tokens || ((uintptr_t)d->vt_out & 15))
-            return 0;
-    } else if (d->vt_also_c) {
-        return 0;
-    }
-    return 1;
-}
-
-// slh_gemm (gemm.hip) has checked d with slh_gemm_tile_ok
-int slh_gemm7_launch(const slh_gemm_desc* d, slh_stream_t stream) {
-    int xb, wb, s;
-    g7_shape(d->tile, xb, wb, s);
+// slh_gemm (gemm.hip) has checked d
+int slh_gemm7_launch(const slh_gemm_desc* d, const GemmTile& t, slh_stream_t stream) {
     G7Args a;
+    memset(&a, 0, sizeof(a));      // padding included (gemm.hip: slh_gemm)
     a.a = (const __bf16*)d->a0; a.w = (const __bf16*)d->w; a.bias = (const __bf16*)d->bias; a.residual = (const __bf16*)d->residual;
     a.c = (__bf16*)d->c; a.ln_out = d->ln_out; a.ln_in = d->ln_in; a.ln_s = d->ln_s; a.ln_b = d->ln_b;
     a.ln_lora_s = d->ln_lora_s; a.ln_lora_c = d->ln_lora_c; a.ln_mr_out = d->ln_mr_out;
     a.lora_down = (const __bf16*)d->lora_down; a.lora_up = (const __bf16*)d->lora_up; a.lora_scale = d->lora_scale;
     a.lora_t_out = d->lora_t_out; a.ld_t = d->ld_t; a.vt = (__bf16*)d->vt_out;
     a.lda = d->lda0; a.ldc = d->ldc; a.ld_res = d->ld_res; a.M = d->M; a.N = d->N; a.K = d->K;
-    a.tiles_m = d->M / (32 * xb); a.tiles_n = d->N / (32 * wb);
-    a.group_m = g7_group_m(a.tiles_m, a.tiles_n, 32 * xb, 32 * wb);
+    a.tiles_m = d->M / t.bm; a.tiles_n = d->N / t.bn;
+    a.group_m = gemm_group_m(a.tiles_m, a.tiles_n, t.bm, t.bn);
     a.ln_in_chunks = d->ln_in_chunks; a.ln_eps = d->ln_eps;
     a.lora_rank = d->lora_rank; a.lora_cols_per_group = d->lora_down ? d->N / d->lora_groups : 1;
     a.vt_col0 = d->vt_col0; a.vt_D = d->vt_D; a.vt_heads = d->vt_heads; a.vt_tokens = d->vt_tokens; a.vt_ld = d->vt_ld;
     a.vt_also_c = d->vt_also_c; a.geglu = d->geglu;
     const int grid = a.tiles_m * a.tiles_n;
     const hipStream_t st = (hipStream_t)stream;
-    if (xb == 8) {
-        slh_launch<gemm7w_kernel<10, 4>>(grid, 512, st, a, "gemm7w_kernel<10, 4>");
-    } else if (wb == 8) {
-        if (d->lora_down) slh_launch<gemm7_kernel<4, 8, 6, true>>(grid, 512, st, a, "gemm7_kernel<4, 8, 6, true>");
-        else slh_launch<gemm7_kernel<4, 8, 6, false>>(grid, 512, st, a, "gemm7_kernel<4, 8, 6, false>");
+    if (t.bm == 256) {
+        slh_launch<gemm7w_kernel<10, 4>>(grid, t.threads, st, a, "gemm7w_kernel<10, 4>");
+    } else if (t.ni == 8) {
+        if (d->lora_down) slh_launch<gemm7_kernel<4, 8, 6, true>>(grid, t.threads, st, a, "gemm7_kernel<4, 8, 6, true>");
+        else slh_launch<gemm7_kernel<4, 8, 6, false>>(grid, t.threads, st, a, "gemm7_kernel<4, 8, 6, false>");
     } else {
-        slh_launch<gemm7_kernel<4, 5, 6, false>>(grid, 512, st, a, "gemm7_kernel<4, 5, 6, false>");
+        slh_launch<gemm7_kernel<4, 5, 6, false>>(grid, t.threads, st, a, "gemm7_kernel<4, 5, 6, false>");
     }
     SLH_LAUNCH_CHECK("slh_gemm (four-wave tile)");
     return 0;

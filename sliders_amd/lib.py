@@ -151,7 +151,7 @@ _ENTRY = {
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
-           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_attn_fwd_kernel_name", "slh_attn_bwd_kernel_names", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
+           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_launch_query", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_attn_fwd_kernel_name", "slh_attn_bwd_kernel_names", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
            "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
 
 
@@ -238,14 +238,14 @@ def gemm_tile_ok(desc) -> bool:
 
 def gemm5_ok(desc) -> bool:
     """The 64 x 160 tile can run this descriptor: slh_gemm_tile_ok for desc.tile, or for TILE_64x160 where desc.tile is of another family"""
-    d = GemmDesc.from_buffer_copy(desc)
-    d.tile = desc.tile if (desc.tile >> 12) & 15 == 5 else TILE_64x160
-    return gemm_tile_ok(d)
+    from .tuning import tile_fields, tile_ok          # (tuning imports this module)
+    return tile_ok(desc, desc.tile if tile_fields(desc.tile).family == 5 else TILE_64x160)
 
 
 def gemm7_ok(desc) -> bool:
     """The tile of csrc/gemm7.hip named by desc.tile (0x7648 / 0x7645 / 0x748a) can run this descriptor (slh_gemm_tile_ok)"""
-    return (desc.tile >> 12) & 15 == 7 and gemm_tile_ok(desc)
+    from .tuning import tile_fields
+    return tile_fields(desc.tile).family == 7 and gemm_tile_ok(desc)
 
 
 def gemm_ln_chunk_cols(desc) -> int:
@@ -373,6 +373,19 @@ def gemm_kernel_name(desc) -> str:
     if rc != 0:
         raise SlidersHipError(f"slh_gemm_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
     return buf.value.decode()
+
+
+def gemm_launch_query(desc):
+    """slh_gemm_launch_query: (kernel name, grid, block size, FNV-1a hash of the kernel's argument bytes) of the launch slh_gemm would
+    make for this descriptor - a function of the descriptor alone, no device needed; raises for a descriptor slh_gemm refuses."""
+    lib = load()
+    lib.slh_gemm_launch_query.argtypes = [C.POINTER(GemmDesc), C.c_char_p, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(C.c_uint64)]
+    lib.slh_gemm_launch_query.restype = c_i32
+    buf, grid, block, h = C.create_string_buffer(160), c_i32(), c_i32(), C.c_uint64()
+    rc = lib.slh_gemm_launch_query(C.byref(desc), buf, 160, C.byref(grid), C.byref(block), C.byref(h))
+    if rc != 0:
+        raise SlidersHipError(f"slh_gemm_launch_query failed ({rc}): {lib.slh_last_error().decode()}")
+    return buf.value.decode(), grid.value, block.value, h.value
 
 
 def call(opcode: int, desc, stream: int):

@@ -143,7 +143,7 @@ def provision_splitk(plan, d, name: str):
     if d.lora_down:
         # one pair of T slabs per slice and per COLUMN TILE (each column tile's last slice reduces its own copy); sized for
         # the narrowest tile (64 columns) unless the tile is fixed
-        ni = tile_fields(d.tile)[4] if (d.tile and not splitk_tuning()) else 1
+        ni = tile_fields(d.tile).ni if (d.tile and not splitk_tuning()) else 1
         tiles_n = (d.N + 64 * ni - 1) // (64 * ni)
         d.splitk_t32 = plan.arena.alloc((tiles_n * 2 * slabs, d.M, d.ld_t), torch.float32, name + ".splitk_T").ptr
 

@@ -10,7 +10,7 @@ from __future__ import annotations
 import glob
 import json
 import os
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 from . import lib
 
@@ -23,9 +23,32 @@ SPLITK_MIN_K = int(os.environ.get("SLIDERS_SPLITK_MIN_K", "2048"))
 SPLITK_TUNING_SLABS = 8          # slabs provisioned per candidate when the in-situ tuner may try any split factor
 
 
-def tile_fields(tile: int):
-    """(split-K factor, family, ring stages, MI, NI) of a tile code: bits 16-19, 12-15, 8-11, 4-7, 0-3 (slh_gemm_desc.tile)"""
-    return (tile >> 16) & 15, (tile >> 12) & 15, (tile >> 8) & 15, (tile >> 4) & 15, tile & 15
+class TileFields(NamedTuple):
+    splitk: int        # bits 16-19: split-K factor (0 | 1: none)
+    family: int        # bits 12-15: 0 (4-wave ring; the alias 2 reads as 0), 4 (8-wave ring), 8 (ping-pong), 5 (64 x 160), 7 (gemm7.hip)
+    slots: int         # bits 8-11: ring slots
+    mi: int            # bits 4-7: MI (gemm7.hip: XB)
+    ni: int            # bits 0-3: NI (gemm7.hip: WB)
+    bm: int            # block tile rows, columns; 0 x 0 for an all-zero code (the library's heuristic picks)
+    bn: int
+
+
+def tile_fields(tile: int) -> TileFields:
+    """A tile code (slh_gemm_desc.tile) taken apart - the only place in Python that reads its bits; which codes name a kernel is the
+    library's knowledge (slh_gemm_tile_ok)."""
+    s, fam, st, mi, ni = (tile >> 16) & 15, (tile >> 12) & 15, (tile >> 8) & 15, (tile >> 4) & 15, tile & 15
+    fam = 0 if fam == 2 else fam
+    if not tile & 0xFFFF:
+        bm, bn = 0, 0
+    elif fam == 5:
+        bm, bn = 64, 160
+    elif fam == 7:
+        bm, bn = 32 * mi, 32 * ni
+    elif fam == 8:
+        bm, bn = (256, 256) if mi == 4 else (128, 64 * ni)
+    else:
+        bm, bn = (128 if fam == 4 else 64) * mi, 64 * ni
+    return TileFields(s, fam, st, mi, ni, bm, bn)
 
 
 def gemm_key(d, with_lora: bool = False) -> str:
@@ -68,7 +91,7 @@ def splitk_wanted(d) -> bool:
         return False
     if splitk_tuning():
         return True
-    return tile_fields(d.tile)[0] > 1 if d.tile else bool(default_splitk(d))
+    return tile_fields(d.tile).splitk > 1 if d.tile else bool(default_splitk(d))
 
 
 def default_splitk(d) -> int:
@@ -84,7 +107,7 @@ def splitk_slabs(d) -> int:
     """Slabs of split-K workspace for d with its chosen tile (0: none): one per K slice, SPLITK_TUNING_SLABS in tuning mode."""
     if not splitk_wanted(d):
         return 0
-    slabs = max(SPLITK_TUNING_SLABS if splitk_tuning() else 0, tile_fields(d.tile)[0])
+    slabs = max(SPLITK_TUNING_SLABS if splitk_tuning() else 0, tile_fields(d.tile).splitk)
     return slabs if slabs >= 2 else 0
 
 
@@ -104,7 +127,7 @@ def table() -> Dict[str, int]:
 
 def _fits(d, tile: int) -> bool:
     """tile_ok and a policy: a folded LayerNorm runs without split-K (the ring tiles could: the last slice normalises the sums)"""
-    return tile_ok(d, tile) and not (d.ln_in and tile_fields(tile)[0] > 1)
+    return tile_ok(d, tile) and not (d.ln_in and tile_fields(tile).splitk > 1)
 
 
 def tuned_tile(d) -> int:
@@ -124,9 +147,9 @@ def tuned_tile(d) -> int:
     if t and not _fits(d, t):
         # an entry names a shape, not a feature set (the key does not see row bias, adapters, training outputs): a 64 x 160 or
         # four-wave entry gives way to the ring tile it replaced, any other to the library's heuristic
-        t = TILE_RING if tile_fields(t)[1] in (5, 7) and tile_ok(d, TILE_RING) else 0
+        t = TILE_RING if tile_fields(t).family in (5, 7) and tile_ok(d, TILE_RING) else 0
     force = os.environ.get("SLIDERS_FORCE_STAGES")     # experiment knob: 2 or 3 for every non-128x128 tile
-    if force and t and (t & 0xFF) != 0x22:
+    if force and t and tile_fields(t)[3:5] != (2, 2):
         t = (t & 0xFF) | (int(force) << 8 if force == "3" else 0)
     return t
 
@@ -169,12 +192,12 @@ def choose_tile(d, ln_out: bool = False, vt: Optional[dict] = None, xa: Optional
         d.ln_out = 8
         if not lib.gemm_ln_chunk_cols(d):
             d.ln_out = 0
-    if vt is not None and not tile_fields(d.tile)[0]:
+    if vt is not None and not tile_fields(d.tile).splitk:
         _put(d, dict(vt, vt_out=16))
         if not lib.gemm_tile_ok(d):
             # V^T policy: a 64 x 160 or four-wave entry gives way to the ring tile it replaced (its entry names a shape, not a
             # feature set); any other tile is kept and the store dropped
-            if tile_fields(d.tile)[1] in (5, 7) and tile_ok(d, TILE_RING):
+            if tile_fields(d.tile).family in (5, 7) and tile_ok(d, TILE_RING):
                 d.tile = TILE_RING
             else:
                 _put(d, dict.fromkeys(list(vt) + ["vt_out"], 0))

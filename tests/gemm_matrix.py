@@ -4,7 +4,9 @@ enumerate_cases() builds one descriptor per (recipe, tile, split-K factor, weigh
 which of them the library accepts (no device needed: the rule only looks at shapes, flags and pointer alignment, so the CPU side
 hands it made-up 256-byte aligned addresses - the alignment every fenced GPU buffer has too).  tests/test_gemm_matrix_gpu.py runs
 every accepted case and one refused case per (tile, recipe); tests/test_host.py pins the accept matrix to
-tests/data/gemm_capability.json (`python -m tests.gemm_matrix --write` records it).
+tests/data/gemm_capability.json (`python -m tests.gemm_matrix --write` records it) and the launch each accepted case and each product
+of the dry-run plans would make - kernel, grid, block size, argument bytes - to tests/data/gemm_dispatch.json (`--write-dispatch`;
+`--dispatch KEY` prints the tuples behind one of its digests).
 
 A case is described without data first (plan_case: scalar descriptor fields + the list of buffers), then materialised into ONE
 device allocation (Arena): every buffer is a slice with at least 4 KiB of pattern on each side and pattern in its padding
@@ -17,6 +19,7 @@ S = the expression of ref on absolute values, n = number of summed terms, R = wh
 derivations of the non-linear recipes are in _geglu_forward / _geglu_backward / _cross_attention.
 """
 import functools
+import hashlib
 import json
 import math
 import os
@@ -31,6 +34,7 @@ from sliders_amd import lib
 from tests.util import BF16_RND, FP32_EPS, elementwise_bound
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "gemm_capability.json")
+DISPATCH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "gemm_dispatch.json")
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # tiles: every code the dispatch of csrc/gemm.hip, gemm8p.hip, gemm5.hip, gemm7.hip instantiates (the tuning tables and the
@@ -483,6 +487,53 @@ def capability_table(acc: List[Case]) -> Dict[str, List[str]]:
         rn, cls, wl, S = c.key
         t.setdefault(f"{rn}|{cls}|wl{wl}|S{S}", []).append(f"0x{c.tile & 0xFFFF:x}")
     return {k: sorted(v, key=lambda s: int(s, 16)) for k, v in sorted(t.items())}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the launch behind every accepted case and every product of the dry-run plans (slh_gemm_launch_query: no device needed)
+# ---------------------------------------------------------------------------------------------------------------------------
+PLAN_CASES = [("tiny_sdxl", 16, "noxattn"), ("tiny_sd1", 16, "full"), ("sdxl", 128, "noxattn"), ("sdxl", 64, "noxattn")]
+PLAN_MODES = ("off", "on", "train")
+
+
+def _launch_line(tile: int, q) -> str:
+    name, grid, block, h = q
+    return f"0x{tile:x} {name} grid {grid} block {block} args {h:016x}"
+
+
+def dispatch_matrix(acc: List[Case]) -> Dict[str, List[str]]:
+    """capability-table key -> the sorted (tile, kernel name, grid, block, args hash) lines of its accepted cases"""
+    t: Dict[str, List[Tuple[int, str]]] = {}
+    for c in acc:
+        rn, cls, wl, S = c.key
+        off, _ = layout(c)
+        q = lib.gemm_launch_query(make_desc(c, _FAKE_BASE, off))
+        t.setdefault(f"{rn}|{cls}|wl{wl}|S{S}", []).append((c.tile, _launch_line(c.tile, q)))
+    return {k: [ln for _, ln in sorted(v)] for k, v in sorted(t.items())}
+
+
+def dispatch_plans() -> Dict[str, List[str]]:
+    """dry-run plan (tests/plan_digest.py: every pointer a function of what it names) -> the launch lines of its OP_GEMM descriptors in
+    program order, the backward program behind the training forward"""
+    from tests import plan_digest
+    out = {}
+    for name, hw, method in PLAN_CASES:
+        for mode in PLAN_MODES:
+            p, bw, _, _ = plan_digest.plan(name, hw, method, mode)
+            progs = [p.prog] + ([bw.prog] if bw is not None else [])
+            out[f"{name}|{hw}|{method}|{mode}"] = [_launch_line(d.tile, lib.gemm_launch_query(d))
+                                                  for pr in progs for o, d in pr.ops if o == lib.OP_GEMM]
+    return out
+
+
+def dispatch_lines(acc: List[Case]) -> Dict[str, Dict[str, List[str]]]:
+    return {"matrix": dispatch_matrix(acc), "plans": dispatch_plans()}
+
+
+def dispatch_digests(acc: List[Case]) -> Dict[str, Dict[str, str]]:
+    """what tests/data/gemm_dispatch.json holds: one SHA-256 per key over its launch lines"""
+    return {sec: {k: hashlib.sha256("\n".join(v).encode()).hexdigest() for k, v in rows.items()}
+            for sec, rows in dispatch_lines(acc).items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -955,6 +1006,17 @@ def _main(argv):
             fh.write(",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in table.items()))
             fh.write("\n}}\n")
         print(f"wrote {DATA} ({os.path.getsize(DATA)} bytes)")
+    if "--write-dispatch" in argv:
+        dig = dispatch_digests(acc)
+        with open(DISPATCH, "w") as fh:                                        # one key per line
+            fh.write("{\n" + ",\n".join('%s: {\n%s\n}' % (json.dumps(sec), ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in rows.items()))
+                                        for sec, rows in dig.items()) + "\n}\n")
+        print(f"wrote {DISPATCH} ({os.path.getsize(DISPATCH)} bytes)")
+    if "--dispatch" in argv:              # the launches behind one digest: --dispatch 'bare|a|wl1|S0' or --dispatch 'sdxl|64|noxattn|on'
+        key = argv[argv.index("--dispatch") + 1]
+        rows = dispatch_lines(acc)
+        found = [ln for sec in rows.values() for ln in sec.get(key, [])]
+        print("\n".join(found) if found else f"no such key: {key}")
 
 
 if __name__ == "__main__":

@@ -102,7 +102,8 @@ def test_lora_backward_helpers(dev):
         A4 = bf(torch.randn(4, Ci, 3, 3, device=dev))
         gxi = bf(torch.randn(B * Hl * Wl, Ci, device=dev))
         g0 = gxi.clone()
-        dd = lib.LoraCdgradDesc(u=p(Uc), a_down=p(A4.permute(0, 2, 3, 1).reshape(4, -1).contiguous()), scale=p(scale),
+        a_down = A4.permute(0, 2, 3, 1).reshape(4, -1).contiguous()      # named: alive until the synchronize behind the launch
+        dd = lib.LoraCdgradDesc(u=p(Uc), a_down=p(a_down), scale=p(scale),
                                 gx=p(gxi), batch=B, hl=Hl, wl=Wl, ho=Ho, wo=Wo, stride=stride, cin=Ci, ldu=4, ldgx=Ci,
                                 accumulate=1)
         lib.call(lib.OP_LORA_CONV_DGRAD, dd, stream())

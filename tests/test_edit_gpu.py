@@ -36,20 +36,6 @@ GUIDANCE = 7.5
 BF, F32 = torch.bfloat16, torch.float32
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _own_memory_pool(dev):
-    """Everything this file allocates on the GPU comes from a pool of its own, so the files that run after it find the caching
-    allocator's free lists as they would without it.  That matters: tests/test_kernels_gpu.py::test_gemm_fused_lora_down hands the
-    kernel pointers of temporaries (`p(bf(_to_pix(...)))`, `p(_pack_conv(w4))`), which are free blocks by the time of the launch;
-    whether a later allocation lands on them depends on the free lists, and with this file allocating from the shared pool ahead
-    of it that test read overwritten operands (rel_l2 1.0)."""
-    import gc
-    pool = torch.cuda.MemPool()
-    with torch.cuda.use_mem_pool(pool, device=dev):
-        yield
-        gc.collect()
-
-
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the kernel, element by element
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1013,6 +1013,21 @@ def test_gemm_capability_matches_the_recorded_table(gemm_matrix_cases):
     assert os.path.getsize(gm.DATA) < 200 * 1024
 
 
+def test_gemm_dispatch_matches_the_recorded_digests(gemm_matrix_cases):
+    """The launch behind every accepted case of the matrix and every product of the dry-run plans (slh_gemm_launch_query: kernel
+    instantiation, grid, block size, FNV-1a of the argument struct's bytes - group_m, tile counts, split-K cut, store16, kper are in
+    there) equals tests/data/gemm_dispatch.json (python -m tests.gemm_matrix --write-dispatch; --dispatch KEY prints the tuples of one
+    key): a change of the dispatch that keeps every result but moves a launch shows here, on any machine."""
+    gm, (acc, _) = gemm_matrix_cases
+    rec = json.load(open(gm.DISPATCH))
+    got = gm.dispatch_digests(acc)
+    assert sorted(got) == sorted(rec) == ["matrix", "plans"]
+    assert len(got["plans"]) == 12 and sorted(got["matrix"]) == sorted(gm.capability_table(acc))
+    bad = [f"{sec}: {k}" for sec in got for k in sorted(set(got[sec]) | set(rec[sec])) if got[sec].get(k) != rec[sec].get(k)]
+    assert not bad, f"{len(bad)} keys launch differently from the recorded dispatch (python -m tests.gemm_matrix --dispatch KEY): {bad}"
+    assert os.path.getsize(gm.DISPATCH) < 200 * 1024
+
+
 def test_gemm_matrix_is_not_hollow(gemm_matrix_cases):
     """Every tile code names a kernel and runs the bare recipe at the exact-multiple shape; every recipe is accepted by at least one
     tile of each family the header (include/sliders_hip.h) says takes it - Recipe.families restates the header's text, so this is
@@ -1107,6 +1122,44 @@ def test_gemm_tile_codes_name_a_kernel_or_are_refused():
             assert not lib.gemm_tile_ok(d), (hex(tile), kw)
             with pytest.raises(lib.SlidersHipError, match="slh_gemm"):
                 lib.gemm_kernel_name(d)
+
+
+def test_gemm_tile_decoder_and_rule_agree_on_every_code():
+    """All 65 536 values of tile bits 0-15, on a bare packed-weight product every family takes at whole-tile shape (512 x 1280 x 320: 64 |
+    128 | 256 rows, 64 | 128 | 160 | 256 | 320 columns): slh_gemm_tile_ok accepts exactly the 30 codes the matrix sweeps, code 0 and
+    the header's two aliases of them (family 2 = 0, ring slots 2 = 0); tuning.tile_fields - the Python decoder - gives each accepted
+    code the family and block size of tests/gemm_matrix.py's own restatement."""
+    from sliders_amd.tuning import tile_fields
+    from tests import gemm_matrix as gm
+    M, N, K = 512, 1280, 320
+    d = lib.GemmDesc(a0=gm._FAKE_BASE, w=gm._FAKE_BASE + (1 << 24), c=gm._FAKE_BASE + (2 << 24), lda0=K, ca0=K, mode=0, stride=1, ldw=0,
+                     M=M, N=N, K=K, ldc=N, rows_per_sample=M, w_layout=1)
+
+    def canonical(code):          # the header's aliases folded: 4-wave family 2 -> 0; ring slots 2 -> 0 (double buffer) on the ring families
+        fam, st = (code >> 12) & 15, (code >> 8) & 15
+        fam = 0 if fam == 2 else fam
+        st = 0 if fam in (0, 4) and st == 2 else st
+        return fam << 12 | st << 8 | (code & 0xFF)
+    swept = set(gm.TILES)
+    assert len(swept) == 31 and 0 in swept
+    want = {0} | {code for code in range(1 << 16) if canonical(code) in swept - {0}}      # (0x2000, 0x0200: aliases of no code)
+    got = set()
+    for code in range(1 << 16):
+        d.tile = code
+        if lib.gemm_tile_ok(d):
+            got.add(code)
+    assert got == want, (sorted(hex(t) for t in got - want)[:20], sorted(hex(t) for t in want - got)[:20])
+    assert len(got) == 31 + 12 + 7 + 4         # + family 2 of the twelve 4-wave codes, + slots 2 of the seven double-buffer ring codes, + both
+    names = {0: "r2", 4: "r4", 8: "pp", 5: "g5", 7: "g7"}
+    for code in sorted(got):
+        f = tile_fields(code)
+        if code == 0:
+            assert gm.family(code) == "auto" and (f.bm, f.bn) == (0, 0)
+            continue
+        c = canonical(code)
+        assert names[f.family] == gm.family(c) and (f.bm, f.bn) == gm.block(c), hex(code)
+        assert (f.splitk, f.slots, f.mi, f.ni) == (0, (code >> 8) & 15, (code >> 4) & 15, code & 15), hex(code)
+    assert tile_fields(0x35425).splitk == 3 and tile_fields(0x20000) == (2, 0, 0, 0, 0, 0, 0)
 
 
 @pytest.mark.parametrize("name,hw,method", [("tiny_sdxl", 16, "noxattn"), ("tiny_sd1", 16, "full"), ("sdxl", 128, "noxattn"), ("sdxl", 64, "noxattn")])

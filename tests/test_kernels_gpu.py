@@ -85,7 +85,8 @@ def test_gemm_packed_weights(dev, tile):
     M = B * Ho * Wo
     c = torch.zeros(M, Co, device=dev, dtype=torch.bfloat16)
     wp = pack_gemm_w(_pack_conv(w4))
-    d = lib.GemmDesc(a0=p(bf(_to_pix(img.float()))), w=p(wp), c=p(c), lda0=Ci, ca0=Ci, mode=1, batch=B, hs=H, ws=W,
+    x_pix = bf(_to_pix(img.float()))          # named: alive until the synchronize behind the launch
+    d = lib.GemmDesc(a0=p(x_pix), w=p(wp), c=p(c), lda0=Ci, ca0=Ci, mode=1, batch=B, hs=H, ws=W,
                      stride=2, ho=Ho, wo=Wo, ldw=0, M=M, N=Co, K=9 * Ci, ldc=Co, rows_per_sample=Ho * Wo, tile=tile,
                      w_layout=1)
     lib.call(lib.OP_GEMM, d, stream())
@@ -271,7 +272,8 @@ def test_gemm_geglu_16_blocks(dev, tile):
     proj = bf(x.float() @ w.float().t() + b.float()).float()
     ref = proj[:, :n_out] * bf(F.gelu(proj[:, n_out:])).float()
     c = torch.zeros(M, n_out, device=dev, dtype=torch.bfloat16)
-    d = lib.GemmDesc(a0=p(x), w=p(_geglu_perm16(w)), bias=p(_geglu_perm16(b)), c=p(c), lda0=K, ca0=K, mode=0, stride=1, ldw=K, M=M, N=N,
+    w16, b16 = _geglu_perm16(w), _geglu_perm16(b)
+    d = lib.GemmDesc(a0=p(x), w=p(w16), bias=p(b16), c=p(c), lda0=K, ca0=K, mode=0, stride=1, ldw=K, M=M, N=N,
                      K=K, ldc=n_out, geglu=3, rows_per_sample=M, tile=tile)
     lib.call(lib.OP_GEMM, d, stream())
     torch.cuda.synchronize()
@@ -769,7 +771,8 @@ def test_gemm_conv_two_source_and_skinny(dev, tile):
     x0, x1 = bf(_to_pix(i0.float())), bf(_to_pix(i1.float()))
     M = B * H * W
     c = torch.zeros(M, Co, device=dev, dtype=torch.bfloat16)
-    d = lib.GemmDesc(a0=p(x0), a1=p(x1), w=p(_pack_conv(w4)), c=p(c), lda0=C0, lda1=C1, ca0=C0, ca1=C1, mode=1,
+    w4p = _pack_conv(w4)
+    d = lib.GemmDesc(a0=p(x0), a1=p(x1), w=p(w4p), c=p(c), lda0=C0, lda1=C1, ca0=C0, ca1=C1, mode=1,
                      batch=B, hs=H, ws=W, stride=1, ho=H, wo=W, ldw=9 * (C0 + C1), M=M, N=Co, K=9 * (C0 + C1),
                      ldc=Co, rows_per_sample=H * W, tile=tile)
     lib.call(lib.OP_GEMM, d, stream())
@@ -783,7 +786,8 @@ def test_gemm_conv_two_source_and_skinny(dev, tile):
         Ho, Wo = r_img.shape[2:]
         Mo = B * Ho * Wo
         out = torch.zeros(Mo, R, device=dev) if kind == 0 else torch.zeros(B, R, Ho, Wo, device=dev, dtype=torch.bfloat16)
-        sd = lib.SkinnyDesc(a0=p(x0), a1=p(x1), w=p(_pack_conv(wd)), bias=p(bias), out=p(out), lda0=C0, lda1=C1,
+        wdp = _pack_conv(wd)
+        sd = lib.SkinnyDesc(a0=p(x0), a1=p(x1), w=p(wdp), bias=p(bias), out=p(out), lda0=C0, lda1=C1,
                             ca0=C0, ca1=C1, mode=1, batch=B, hs=H, ws=W, stride=stride, ho=Ho, wo=Wo, M=Mo, R=R,
                             K=9 * (C0 + C1), ldo=R, out_kind=kind)
         lib.call(lib.OP_SKINNY, sd, stream())
@@ -1052,7 +1056,8 @@ def test_timestep_embed_and_conv_in(dev):
     w4 = bf(torch.randn(Co, 4, 3, 3, device=dev) / 6)
     bias = bf(torch.randn(Co, device=dev))
     y = torch.zeros(B * H * W, Co, device=dev, dtype=torch.bfloat16)
-    lib.call(lib.OP_CONV_IN, lib.ConvInDesc(x=p(x), w=p(_pack_conv(w4)), bias=p(bias), y=p(y), batch=B, cin=4, h=H, wd=W,
+    w4p = _pack_conv(w4)
+    lib.call(lib.OP_CONV_IN, lib.ConvInDesc(x=p(x), w=p(w4p), bias=p(bias), y=p(y), batch=B, cin=4, h=H, wd=W,
                                             cout=Co, ldy=Co), stream())
     torch.cuda.synchronize()
     report("conv_in", y, _to_pix(F.conv2d(x.float(), w4.float(), bias.float(), padding=1)), TOL)
@@ -1266,7 +1271,8 @@ def test_lora_wgrad(dev):
     img = bf(torch.randn(B, Ci, H, W, device=dev))
     U = torch.randn(B * H * W, 4, device=dev)
     out = torch.zeros(4, 9 * Ci, device=dev)
-    lib.call(lib.OP_WGRAD, lib.WgradDesc(z0=p(bf(_to_pix(img.float()))), v=p(U), out=p(out), scale=p(scale), ldz0=Ci,
+    x_pix = bf(_to_pix(img.float()))
+    lib.call(lib.OP_WGRAD, lib.WgradDesc(z0=p(x_pix), v=p(U), out=p(out), scale=p(scale), ldz0=Ci,
                                          c0=Ci, mode=1, batch=B, hs=H, ws=W, stride=1, ho=H, wo=W, M=B * H * W, R=4,
                                          ldv=4, ldo=9 * Ci, out_rmajor=1, vgroup_cols=0), stream())
     torch.cuda.synchronize()
@@ -1487,7 +1493,8 @@ def test_gemm_fused_lora_down(dev, tile):
     M = B * Ho * Wo
     c = torch.zeros(M, Co, device=dev, dtype=torch.bfloat16)
     Tout = torch.zeros(M, 4, device=dev)
-    d = lib.GemmDesc(a0=p(bf(_to_pix(img.float()))), w=p(_pack_conv(w4)), c=p(c), lora_down=p(_pack_conv(a4)), lora_up=p(up),
+    x_pix, w4p, a4p = bf(_to_pix(img.float())), _pack_conv(w4), _pack_conv(a4)
+    d = lib.GemmDesc(a0=p(x_pix), w=p(w4p), c=p(c), lora_down=p(a4p), lora_up=p(up),
                      lora_scale=p(scale), lora_t_out=p(Tout), lda0=Ci, ca0=Ci, mode=1, batch=B, hs=H, ws=W, stride=2, ho=Ho,
                      wo=Wo, ldw=9 * Ci, M=M, N=Co, K=9 * Ci, ldc=Co, rows_per_sample=Ho * Wo, ld_t=4, lora_groups=1,
                      lora_rank=4, tile=tile)
@@ -1657,7 +1664,8 @@ def test_gemm_splitk(dev, tile):
     Mc = B * H * W
     cc = torch.zeros(Mc, Co, device=dev, dtype=torch.bfloat16)
     wsc = torch.full((S, 256, 128), float("nan"), device=dev)
-    d = lib.GemmDesc(a0=p(x0), a1=p(x1), w=p(_pack_conv(w4)), c=p(cc), lda0=C0, lda1=C1, ca0=C0, ca1=C1, mode=1, batch=B, hs=H,
+    w4p = _pack_conv(w4)
+    d = lib.GemmDesc(a0=p(x0), a1=p(x1), w=p(w4p), c=p(cc), lda0=C0, lda1=C1, ca0=C0, ca1=C1, mode=1, batch=B, hs=H,
                      ws=W, stride=1, ho=H, wo=W, ldw=9 * (C0 + C1), M=Mc, N=Co, K=9 * (C0 + C1), ldc=Co, rows_per_sample=H * W,
                      tile=tile, splitk_c32=p(wsc), splitk_slabs=S, splitk_ticket=p(tickets))
     if (tile >> 12) & 15 == 8 and 128 * 64 * (tile & 15) > 256 * 128:
