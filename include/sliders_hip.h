@@ -459,6 +459,41 @@ typedef struct slh_ddpm_edit_desc {
 } slh_ddpm_edit_desc;
 int slh_ddpm_edit_step(const slh_ddpm_edit_desc* d, slh_stream_t stream);
 
+/* The edit step of a localised edit: e = mu + resid exactly as slh_ddpm_edit_step mode 1 forms it (one piece of code), then, with
+ * k = keep[i] and m = mask[b*hw + i % hw] (one mask value per latent pixel, shared by the channels),
+ *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          fp32, one rounding per operation, no contraction.
+ * keep is the latent the inversion's own chain had after this step: where the mask is 0 the edit stays on the inversion's latents
+ * bit for bit, and where e == keep (an edit at scale 0) out == keep under any mask.  Mask values outside [0, 1] are the caller's
+ * error.  keep and mask must not overlap out. */
+typedef struct slh_ddpm_edit_blend_desc {
+    const void* eps;         /* bf16 [2*nb][chw], uncond half first */
+    const void* eps_text;    /* optional, as slh_cfg_ddim_desc */
+    const float* x;          /* fp32 [nb][chw] master latent x_t */
+    const float* resid;      /* fp32 [nb][chw], read */
+    const float* keep;       /* fp32 [nb][chw]: the inversion's latent after this step */
+    const float* mask;       /* fp32 [nb][hw] in [0, 1]; 1 = edit */
+    float* out;              /* fp32 x_{t-1}; may alias x */
+    void* out_bf16; void* out2_bf16;   /* optional bf16 copies of out */
+    int32_t nb, chw, hw;     /* chw % hw == 0 */
+    float guidance;
+    float c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev, c_dir;   /* as slh_ddpm_edit_desc */
+    int32_t v_prediction;
+} slh_ddpm_edit_blend_desc;
+int slh_ddpm_edit_blend(const slh_ddpm_edit_blend_desc* d, slh_stream_t stream);
+
+/* Where two epsilon predictions differ, per latent pixel: with e = u + guidance * (t - u) of each pair (fp32, no contraction),
+ *   out[b][p] = sum over c = 0 .. chw/hw - 1, ascending, of |e_a - e_b| at (b, c, p).
+ * One thread per pixel, a fixed order and no atomics: bit-reproducible. */
+typedef struct slh_eps_absdiff_desc {
+    const void* eps_a;       /* bf16 [2*nb][chw], uncond half first */
+    const void* eps_a_text;  /* optional: the text half [nb][chw] where it is not stored right after the uncond half */
+    const void* eps_b; const void* eps_b_text;   /* likewise */
+    float* out;              /* fp32 [nb][hw] */
+    int32_t nb, chw, hw;     /* chw % hw == 0 */
+    float guidance;
+} slh_eps_absdiff_desc;
+int slh_eps_absdiff(const slh_eps_absdiff_desc* d, slh_stream_t stream);
+
 /* guidance loss (prompt_util.py:108-148): loss = mean((target - (neutral +- gs*(positive-uncond)))^2);
  * writes loss (fp32 scalar, atomically accumulated: zero it first) and d(loss)/d(target) (bf16). */
 typedef struct slh_loss_desc {
@@ -687,7 +722,7 @@ enum {
     SLH_OP_VAE_CONV_IN = 27, SLH_OP_VAE_MOMENTS = 28, SLH_OP_VAE_SAMPLE = 29, SLH_OP_VAE_POST_QUANT = 30, SLH_OP_LION = 31,
     SLH_OP_WGRAD_BATCH = 32, SLH_OP_TRANSPOSE_BATCH = 33, SLH_OP_GATHER16 = 34, SLH_OP_GN_FUSED = 35,
     SLH_OP_LORA_LN_FOLD = 36,     /* 37 was SLH_OP_PREFETCH (side-stream weight touch: measured slower, removed in round 5) */
-    SLH_OP_LORA_MERGE = 38, SLH_OP_DDPM_EDIT = 39
+    SLH_OP_LORA_MERGE = 38, SLH_OP_DDPM_EDIT = 39, SLH_OP_DDPM_EDIT_BLEND = 40, SLH_OP_EPS_ABSDIFF = 41
 };
 /* SLH_OP_MEMSET: byte fill by a kernel of this library (not hipMemsetAsync: a captured memset node is a runtime blit whose
  * replays were observed to go wrong on the legacy default stream - see the executor's comment) */

@@ -11,10 +11,45 @@
 // nothing here may be contracted - an fma formed in one mode's copy of the code and not in the other's would break the identity, and
 // the fp32 restatement in sliders_amd/edit.py (plain tensor ops, one rounding per operation) would no longer describe the kernel.
 // One element per thread, as cfg_ddim_kernel: a latent is 4 x 128 x 128 values, the launch is a few microseconds of HBM traffic.
+//
+// slh_ddpm_edit_blend: the edit step of a LOCALISED edit.  e = mu + resid as mode 1 above (ddpm_mu: the one piece of code both
+// kernels form mu with), then blended against `keep`, the latent the inversion's own chain had after this step, under a mask with
+// one value per latent pixel:  out = keep where m == 0, e where m == 1 (both exactly), keep + m (e - keep) between.  Where the
+// mask is 0 the edited latent is the inversion's at every step, so the result is the reconstruction there bit for bit; and an edit
+// at scale 0 has e == keep, so keep + m * 0 is keep under any mask.
+//
+// slh_eps_absdiff: sum over the channels of |e_a - e_b| for two CFG-combined epsilon pairs - where a slider acts, for one noise
+// draw (SliderEditor.footprint).  One thread per pixel, the channels in ascending order: no atomics, the same bits every run.
 #include "common.h"
 #include "../../include/sliders_hip.h"
 
 namespace {
+
+// the coefficients both step kernels read from their descriptors
+struct mu_coef {
+    float guidance, c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev, c_dir;
+    int v_prediction;
+};
+template <typename D>
+__device__ __forceinline__ mu_coef coef_of(const D& d) {
+    return mu_coef{d.guidance, d.c_sqrt_beta_t, d.c_inv_sqrt_alpha_t, d.c_sqrt_alpha_t, d.c_sqrt_alpha_prev, d.c_dir, d.v_prediction};
+}
+
+// CFG combine + the DDIM mean of x_{t-1} from the epsilon halves u, t and the master latent x
+__device__ __forceinline__ float ddpm_mu(const mu_coef& c, float u, float t, float x) {
+#pragma clang fp contract(off)
+    // 8 roundings on the longest path from the inputs to mu (epsilon prediction; 7 with v prediction): docs/EDIT.md counts them
+    const float e = u + c.guidance * (t - u);
+    float x0, pe;
+    if (c.v_prediction) {
+        x0 = c.c_sqrt_alpha_t * x - c.c_sqrt_beta_t * e;
+        pe = c.c_sqrt_alpha_t * e + c.c_sqrt_beta_t * x;
+    } else {
+        x0 = (x - c.c_sqrt_beta_t * e) * c.c_inv_sqrt_alpha_t;
+        pe = e;
+    }
+    return c.c_sqrt_alpha_prev * x0 + c.c_dir * pe;
+}
 
 __global__ __launch_bounds__(256) void ddpm_edit_kernel(const slh_ddpm_edit_desc d) {
 #pragma clang fp contract(off)
@@ -24,18 +59,7 @@ __global__ __launch_bounds__(256) void ddpm_edit_kernel(const slh_ddpm_edit_desc
     const __bf16* eps = (const __bf16*)d.eps;
     const float u = (float)eps[i];
     const float t = d.eps_text ? (float)((const __bf16*)d.eps_text)[i] : (float)eps[n + i];
-    const float x = d.x[i];
-    // 8 roundings on the longest path from the inputs to mu (epsilon prediction; 7 with v prediction): docs/EDIT.md counts them
-    const float e = u + d.guidance * (t - u);
-    float x0, pe;
-    if (d.v_prediction) {
-        x0 = d.c_sqrt_alpha_t * x - d.c_sqrt_beta_t * e;
-        pe = d.c_sqrt_alpha_t * e + d.c_sqrt_beta_t * x;
-    } else {
-        x0 = (x - d.c_sqrt_beta_t * e) * d.c_inv_sqrt_alpha_t;
-        pe = e;
-    }
-    const float mu = d.c_sqrt_alpha_prev * x0 + d.c_dir * pe;
+    const float mu = ddpm_mu(coef_of(d), u, t, d.x[i]);
     float r;
     if (d.mode == 0) {
         r = d.target[i] - mu;
@@ -50,7 +74,80 @@ __global__ __launch_bounds__(256) void ddpm_edit_kernel(const slh_ddpm_edit_desc
     if (d.out2_bf16) ((__bf16*)d.out2_bf16)[i] = ob;
 }
 
+__global__ __launch_bounds__(256) void ddpm_edit_blend_kernel(const slh_ddpm_edit_blend_desc d) {
+#pragma clang fp contract(off)
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;          // the entry point refuses nb * chw >= 2^31
+    const unsigned n = (unsigned)d.nb * (unsigned)d.chw;
+    if (i >= n) return;
+    const __bf16* eps = (const __bf16*)d.eps;
+    const float u = (float)eps[i];
+    const float t = d.eps_text ? (float)((const __bf16*)d.eps_text)[i] : (float)eps[n + i];
+    const float mu = ddpm_mu(coef_of(d), u, t, d.x[i]);
+    const float e = mu + d.resid[i];                                   // ddpm_edit_kernel's mode 1, to the bit
+    const float k = d.keep[i];
+    const float m = d.mask[i / (unsigned)d.chw * (unsigned)d.hw + i % (unsigned)d.hw];   // chw is a multiple of hw: i % hw is the pixel
+    // three more roundings where 0 < m < 1: e - k, m *, k +
+    const float o = m == 0.0f ? k : m == 1.0f ? e : k + m * (e - k);
+    d.out[i] = o;
+    const __bf16 ob = (__bf16)o;       // round to nearest even
+    if (d.out_bf16) ((__bf16*)d.out_bf16)[i] = ob;
+    if (d.out2_bf16) ((__bf16*)d.out2_bf16)[i] = ob;
+}
+
+__global__ __launch_bounds__(256) void eps_absdiff_kernel(const slh_eps_absdiff_desc d) {
+#pragma clang fp contract(off)
+    const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;          // b * hw + p; the entry point refuses nb * chw >= 2^31
+    if (j >= (unsigned)d.nb * (unsigned)d.hw) return;
+    const unsigned n = (unsigned)d.nb * (unsigned)d.chw;
+    const __bf16* a = (const __bf16*)d.eps_a;
+    const __bf16* b = (const __bf16*)d.eps_b;
+    const __bf16* at = d.eps_a_text ? (const __bf16*)d.eps_a_text : a + n;
+    const __bf16* bt = d.eps_b_text ? (const __bf16*)d.eps_b_text : b + n;
+    unsigned i = j / (unsigned)d.hw * (unsigned)d.chw + j % (unsigned)d.hw;
+    float acc = 0.0f;
+    for (int c = 0; c < d.chw / d.hw; ++c, i += d.hw) {
+        const float ua = (float)a[i], ub = (float)b[i];
+        const float ea = ua + d.guidance * ((float)at[i] - ua);
+        const float eb = ub + d.guidance * ((float)bt[i] - ub);
+        acc = acc + fabsf(ea - eb);
+    }
+    d.out[j] = acc;
+}
+
+// [a, a + na) and [b, b + nb) bytes share an address
+inline bool overlaps(const void* a, long na, const void* b, long nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
 }  // namespace
+
+extern "C" int slh_ddpm_edit_blend(const slh_ddpm_edit_blend_desc* d, slh_stream_t stream) {
+    SLH_CHECK(d && d->eps && d->x && d->resid && d->out, "slh_ddpm_edit_blend: null eps / x / resid / out");
+    SLH_CHECK(d->keep && d->mask, "slh_ddpm_edit_blend: null keep / mask");
+    SLH_CHECK(d->nb > 0 && d->chw > 0 && d->hw > 0, "slh_ddpm_edit_blend: nb = %d, chw = %d, hw = %d", d->nb, d->chw, d->hw);
+    SLH_CHECK(d->chw % d->hw == 0, "slh_ddpm_edit_blend: chw = %d is not a multiple of hw = %d", d->chw, d->hw);
+    const long n = (long)d->nb * d->chw;
+    SLH_CHECK(n < (1L << 31), "slh_ddpm_edit_blend: nb * chw = %ld: the kernel indexes with 32 bits", n);
+    // keep and mask are the inversion's and the caller's: a step that wrote over them (or read them half written, where they overlap
+    // out at an offset) would leave the next step, and the next edit, another image to keep.  out may alias x, as slh_ddpm_edit_step's
+    SLH_CHECK(!overlaps(d->keep, n * 4, d->out, n * 4), "slh_ddpm_edit_blend: keep aliases out");
+    SLH_CHECK(!overlaps(d->mask, (long)d->nb * d->hw * 4, d->out, n * 4), "slh_ddpm_edit_blend: mask aliases out");
+    hipLaunchKernelGGL(ddpm_edit_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d);
+    SLH_LAUNCH_CHECK("slh_ddpm_edit_blend");
+    return 0;
+}
+
+extern "C" int slh_eps_absdiff(const slh_eps_absdiff_desc* d, slh_stream_t stream) {
+    SLH_CHECK(d && d->eps_a && d->eps_b && d->out, "slh_eps_absdiff: null eps_a / eps_b / out");
+    SLH_CHECK(d->nb > 0 && d->chw > 0 && d->hw > 0, "slh_eps_absdiff: nb = %d, chw = %d, hw = %d", d->nb, d->chw, d->hw);
+    SLH_CHECK(d->chw % d->hw == 0, "slh_eps_absdiff: chw = %d is not a multiple of hw = %d", d->chw, d->hw);
+    SLH_CHECK((long)d->nb * d->chw < (1L << 31), "slh_eps_absdiff: nb * chw = %ld: the kernel indexes with 32 bits", (long)d->nb * d->chw);
+    const long n = (long)d->nb * d->hw;
+    hipLaunchKernelGGL(eps_absdiff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d);
+    SLH_LAUNCH_CHECK("slh_eps_absdiff");
+    return 0;
+}
 
 extern "C" int slh_ddpm_edit_step(const slh_ddpm_edit_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->eps && d->x && d->out, "slh_ddpm_edit_step: null eps / x / out");

@@ -19,8 +19,13 @@ bf16 rounding.
 `ddpm_step_coefficients`                               the per-step scalars, float64
 `ddpm_mu_reference` / `invert_reference` / `edit_reference`  the recurrence in plain torch over a callable predict(x_bf16, t, multiplier):
                                                        float64 = the oracle, float32 = the kernel's operations in the kernel's order
-`NoiseSpace`                                           what an inversion leaves: x0, X_0, the residuals, the reconstruction
-`SliderEditor`                                         SliderSampler + invert / edit_latents / edit on the engine
+`NoiseSpace`                                           what an inversion leaves: x0, X_0, the residuals, the reconstruction, its latents
+`SliderEditor`                                         SliderSampler + invert / edit_latents / edit / footprint on the engine
+
+Localised edits (mask=, --mask / --auto_mask): every step of an edit is blended against the latent the inversion itself had after
+that step (NoiseSpace.visited, slh_ddpm_edit_blend), so outside the mask the result is the reconstruction bit for bit.  The mask
+comes from a file (`load_mask`, `feather_mask`) or from where the slider changes the predicted noise on this image
+(`SliderEditor.footprint`, slh_eps_absdiff; `footprint_mask`).  `blend_reference` restates the blend as the other references do.
 """
 from __future__ import annotations
 
@@ -120,6 +125,8 @@ class NoiseSpace:
     ctx: Optional[torch.Tensor] = None          # the conditioning the inversion ran with (an edit without its own reuses it)
     pooled: Optional[torch.Tensor] = None
     time_ids: Optional[torch.Tensor] = None
+    visited: Optional[torch.Tensor] = None      # [len(timesteps)][bs][4][h][w] the latent after each step of the inversion's own chain
+                                                # (visited[-1] == recon): what a masked edit keeps outside the mask
 
     def _map(self, fn) -> dict:
         return {f.name: fn(getattr(self, f.name)) if torch.is_tensor(getattr(self, f.name)) else getattr(self, f.name) for f in fields(self)}
@@ -131,10 +138,10 @@ class NoiseSpace:
     @classmethod
     def load(cls, path: str, device=None) -> "NoiseSpace":
         d = torch.load(path, map_location="cpu")
-        missing = [f.name for f in fields(cls) if f.name not in d]
+        missing = [f.name for f in fields(cls) if f.name not in d and f.name != "visited"]       # files from before masked edits have none
         if missing:
             raise KeyError(f"{path}: not a saved NoiseSpace (no {missing})")
-        d = {f.name: d[f.name] for f in fields(cls)}
+        d = {f.name: d.get(f.name) for f in fields(cls)}
         d["timesteps"] = [int(t) for t in d["timesteps"]]
         sp = cls(**d)
         return sp.to(device) if device is not None else sp
@@ -154,29 +161,157 @@ def invert_reference(predict: Predict, x0: torch.Tensor, schedule: DDIMSchedule,
     path = build_path(schedule, x0, ts, seed)
     v = schedule.prediction_type == "v_prediction"
     x = path[0].clone()
-    resid = torch.empty_like(path)
+    resid, visited = torch.empty_like(path), torch.empty_like(path)
     for i, t in enumerate(ts):
         eu, et = predict(x.to(torch.bfloat16), t, 0.0)
         mu = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, steps, eta), guidance, v, dtype)
         target = path[i + 1] if i + 1 < len(ts) else x0
         resid[i] = target - mu
         x = mu + resid[i]                     # NOT target: the edit can only recompute mu + d
+        visited[i] = x
     return NoiseSpace(x0=x0, x_start=path[0].clone(), resid=resid, recon=x, timesteps=list(ts), steps=int(steps),
                       skip=steps - len(ts), eta=float(eta), guidance=float(guidance), prediction_type=schedule.prediction_type,
-                      seed=int(seed))
+                      seed=int(seed), visited=visited)
+
+
+def as_mask(mask: torch.Tensor, bs: int, h: int, w: int) -> torch.Tensor:
+    """[h][w], [bs][h][w] or [bs][1][h][w] with values in [0, 1] -> fp32 [bs][1][h][w], contiguous (one value per latent pixel, shared
+    by the channels); anything else is a ValueError"""
+    if not torch.is_tensor(mask):
+        raise ValueError(f"mask: expected a tensor, got {type(mask).__name__}")
+    shape = tuple(mask.shape)
+    if shape not in ((h, w), (bs, h, w), (bs, 1, h, w)):
+        raise ValueError(f"mask of shape {shape}: expected ({h}, {w}), ({bs}, {h}, {w}) or ({bs}, 1, {h}, {w})")
+    if not (mask.dtype.is_floating_point or mask.dtype == torch.bool):
+        raise ValueError(f"mask of dtype {mask.dtype}: expected floating point values in [0, 1] (or bool)")
+    m = mask.detach().to(torch.float32)
+    if not bool(((m >= 0.0) & (m <= 1.0)).all()):            # NaN fails both comparisons
+        raise ValueError("mask values must lie in [0, 1]")
+    return (m[None].expand(bs, h, w) if m.dim() == 2 else m).reshape(bs, 1, h, w).contiguous()
+
+
+def blend_reference(e: torch.Tensor, keep: torch.Tensor, mask: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """The masked step's blend of the edited latent e against the inversion's latent `keep`, mask broadcast over the channels:
+    keep where the mask is 0, e where it is 1 (both exactly), keep + m (e - keep) between.  float64: the oracle.  float32: the
+    operations of ddpm_edit_blend_kernel in its order, one rounding each."""
+    e, k, m = e.to(dtype), keep.to(dtype), mask.to(dtype)
+    out = k + m * (e - k)
+    return torch.where(m == 0, k, torch.where(m == 1, e, out))
 
 
 def edit_reference(predict: Predict, space: NoiseSpace, schedule: DDIMSchedule, scale: float = 0.0, start_noise: int = 750,
-                   guidance: Optional[float] = None, dtype=torch.float32) -> torch.Tensor:
-    """The edit at slider scale `scale` (multiplier 0 while t > start_noise, as SliderSampler.sample_latents)."""
+                   guidance: Optional[float] = None, dtype=torch.float32, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The edit at slider scale `scale` (multiplier 0 while t > start_noise, as SliderSampler.sample_latents).  mask: every step is
+    blended against the inversion's latent after that step (space.visited), so the result is space.recon outside the mask."""
     g = space.guidance if guidance is None else guidance
     v = schedule.prediction_type == "v_prediction"
     x = space.x_start.to(dtype).clone()
+    if mask is not None:
+        space = trajectory_reference(predict, space, schedule, dtype)
+        mask = as_mask(mask, x.shape[0], x.shape[2], x.shape[3])
     for i, t in enumerate(space.timesteps):
         eu, et = predict(x.to(torch.bfloat16), t, 0.0 if t > start_noise else float(scale))
         mu = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, space.steps, space.eta), g, v, dtype)
         x = mu + space.resid[i].to(dtype)
+        if mask is not None:
+            x = blend_reference(x, space.visited[i], mask, dtype)
     return x
+
+
+def trajectory_reference(predict: Predict, space: NoiseSpace, schedule: DDIMSchedule, dtype=torch.float32) -> NoiseSpace:
+    """Fills a missing space.visited by the scale-0 replay (SliderEditor.trajectory over predict); raises if it does not end on recon"""
+    if space.visited is not None:
+        return space
+    v = schedule.prediction_type == "v_prediction"
+    x = space.x_start.to(dtype).clone()
+    visited = torch.empty_like(space.resid, dtype=dtype)
+    for i, t in enumerate(space.timesteps):
+        eu, et = predict(x.to(torch.bfloat16), t, 0.0)
+        x = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, space.steps, space.eta), space.guidance, v, dtype) + space.resid[i].to(dtype)
+        visited[i] = x
+    if not torch.equal(x, space.recon.to(dtype)):
+        raise RuntimeError("trajectory_reference: the scale-0 replay does not end on space.recon bit for bit")
+    space.visited = visited
+    return space
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# masks: from a file, or from the slider's footprint (host tensor ops on one small array per image)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def load_mask(path: str, res: int, invert: bool = False) -> torch.Tensor:
+    """An image file -> the latent-resolution mask [res/8][res/8] fp32 in [0, 1]: grey levels / 255 at res x res (BOX filter), then
+    the mean over each 8 x 8 block of pixels (one latent pixel).  White means edit; invert swaps the sides."""
+    from PIL import Image
+    import numpy as np
+    if res <= 0 or res % 8:
+        raise ValueError(f"load_mask: res = {res}: expected a positive multiple of 8")
+    img = Image.open(path).convert("L").resize((res, res), Image.BOX)
+    m = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(torch.float32) / 255.0
+    m = m.reshape(res // 8, 8, res // 8, 8).mean(dim=(1, 3))
+    return 1.0 - m if invert else m
+
+
+def feather_mask(mask: torch.Tensor, sigma: float) -> torch.Tensor:
+    """Separable Gaussian blur in latent pixels over the last two dimensions: radius ceil(3 sigma), taps normalised to sum 1, replicate
+    padding, fp32, clamped to [0, 1].  sigma = 0 returns the mask as it is."""
+    sigma = float(sigma)
+    if not sigma >= 0.0 or math.isinf(sigma):
+        raise ValueError(f"feather_mask: sigma = {sigma}: expected a finite sigma >= 0")
+    if mask.dim() < 2:
+        raise ValueError(f"feather_mask: mask of shape {tuple(mask.shape)}: expected at least two dimensions")
+    if sigma == 0.0:
+        return mask
+    import torch.nn.functional as F
+    r = int(math.ceil(3.0 * sigma))
+    taps = torch.exp(-0.5 * (torch.arange(-r, r + 1, dtype=torch.float32, device=mask.device) / sigma) ** 2)
+    taps = taps / taps.sum()
+    h, w = mask.shape[-2:]
+    m = mask.to(torch.float32).reshape(-1, 1, h, w)
+    m = F.conv2d(F.pad(m, (r, r, 0, 0), mode="replicate"), taps.reshape(1, 1, 1, -1))
+    m = F.conv2d(F.pad(m, (0, 0, r, r), mode="replicate"), taps.reshape(1, 1, -1, 1))
+    return m.clamp(0.0, 1.0).reshape(mask.shape)
+
+
+def footprint_draws(timesteps: List[int], start_noise: int = 750, draws: int = 8, t_min: int = 200) -> List[int]:
+    """The steps a footprint is measured at: `draws` of the indices i with t_min <= t_i <= start_noise, evenly spaced (all of them
+    if there are fewer)"""
+    if draws < 1:
+        raise ValueError(f"draws = {draws}: expected draws >= 1")
+    ok = [i for i, t in enumerate(timesteps) if t_min <= t <= start_noise]
+    if not ok:
+        raise ValueError(f"no step of the grid {list(timesteps)} has t_min = {t_min} <= t <= start_noise = {start_noise}")
+    if len(ok) <= draws:
+        return ok
+    pick = torch.linspace(0, len(ok) - 1, draws, dtype=torch.float64).round().long().tolist()
+    return [ok[j] for j in sorted(set(pick))]
+
+
+def footprint_mean(A: torch.Tensor) -> torch.Tensor:
+    """A [draws][bs][h][w] (slh_eps_absdiff per draw) -> F [bs][h][w]: every draw divided by its own mean over the pixels (a draw at a
+    noisier level has a larger epsilon difference everywhere), then the mean over the draws; a draw whose mean is 0 contributes 0"""
+    mean = A.mean(dim=(2, 3), keepdim=True)
+    return torch.where(mean > 0, A / mean, torch.zeros_like(A)).mean(dim=0)
+
+
+def footprint_mask(F: torch.Tensor, quantile: float = 0.98, threshold: float = 0.5, dilate: int = 1, feather: float = 1.0) -> torch.Tensor:
+    """A footprint [bs][h][w] (or [h][w]) -> a mask of its shape, DiffEdit's procedure: scale by the `quantile` value of each sample
+    and clamp to [0, 1], binarise at `threshold`, dilate by `dilate` pixels, feather with a Gaussian of sigma `feather`."""
+    import torch.nn.functional as nnf
+    if F.dim() not in (2, 3):
+        raise ValueError(f"footprint_mask: F of shape {tuple(F.shape)}: expected [bs][h][w] or [h][w]")
+    if not 0.0 < quantile <= 1.0 or not 0.0 < threshold <= 1.0 or int(dilate) != dilate or dilate < 0:
+        raise ValueError(f"footprint_mask: quantile = {quantile}, threshold = {threshold}, dilate = {dilate}: expected 0 < quantile <= 1, "
+                         f"0 < threshold <= 1, an integer dilate >= 0")
+    f = F.to(torch.float32).reshape((-1,) + tuple(F.shape[-2:]))
+    hw = f.shape[1] * f.shape[2]
+    q = torch.kthvalue(f.reshape(f.shape[0], hw), max(1, int(math.ceil(quantile * hw))), dim=1).values
+    if not bool((q > 0).all()):
+        raise ValueError("footprint_mask: the slider has no footprint at this scale")
+    m = (f / q[:, None, None]).clamp(0.0, 1.0)
+    m = (m >= threshold).to(torch.float32)
+    if dilate > 0:
+        m = nnf.max_pool2d(m[:, None], 2 * int(dilate) + 1, stride=1, padding=int(dilate))[:, 0]
+    return feather_mask(m, feather).reshape(F.shape)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -213,35 +348,51 @@ class SliderEditor(SliderSampler):
             return p.prog if i == 0 or p.prog_text_cached is None else p.prog_text_cached
         return self._program(p, i, t, scale, start_noise)
 
-    def _chain(self, p, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None):
-        """x (fp32, updated in place) through the grid: path given = invert (resid written), else edit (resid read)"""
+    def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None):
+        """The step's one element-wise launch after the UNet pass, src -> dst (fp32, may be one tensor) and the bf16 halves of `sample`:
+        slh_ddpm_edit_step - mode 0 with a target (resid_i written), else mode 1 (resid_i read) - or, with a mask, slh_ddpm_edit_blend
+        against keep"""
         from . import lib
+        io, bs, chw = p.io, src.shape[0], src[0].numel()
+        smp = io["sample"]
+        common = dict(eps=io["eps"].ptr, x=src.data_ptr(), resid=resid_i.data_ptr(), out=dst.data_ptr(), out_bf16=smp.ptr,
+                      out2_bf16=smp.ptr + bs * chw * 2, nb=bs, chw=chw, guidance=float(guidance),
+                      v_prediction=1 if self.sched.prediction_type == "v_prediction" else 0,
+                      **fp32_coefficients(ddpm_step_coefficients(self.sched, t, steps, eta)))
+        s = torch.cuda.current_stream().cuda_stream
+        if mask is None:
+            d = lib.DdpmEditDesc(target=0 if target is None else target.data_ptr(), mode=0 if target is not None else 1, **common)
+            lib.call(lib.OP_DDPM_EDIT, d, s)
+        else:
+            d = lib.DdpmEditBlendDesc(keep=keep.data_ptr(), mask=mask.data_ptr(), hw=chw // src.shape[1], **common)
+            lib.call(lib.OP_DDPM_EDIT_BLEND, d, s)
+
+    def _chain(self, p, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None, record=None, keep=None, mask=None):
+        """x (fp32) through the grid; returns the final latent.  path given = invert (resid written), else edit (resid read).
+        record None: x is updated in place.  record [len(ts)][bs][4][h][w]: the same launches, but step i reads record[i - 1] (x for
+        i = 0) and writes record[i], so the chain's latents are kept (the inversion, `trajectory`).
+        mask [bs][1][h][w] with keep = the inversion's latents: every step is blended against keep[i] (in place)."""
         eng, io = self.eng, p.io
         bs = x.shape[0]
-        chw = x[0].numel()
         smp = io["sample"]
         xb = x.to(torch.bfloat16)
         smp.tensor[:bs].copy_(xb)
         smp.tensor[bs:].copy_(xb)
         s = torch.cuda.current_stream().cuda_stream
-        v = 1 if self.sched.prediction_type == "v_prediction" else 0
         try:
             for i, t in enumerate(ts):
                 if self.store is not None:
                     eng.set_lora(True, 0.0 if t > start_noise else float(scale))
                 io["t"].tensor.fill_(float(t))
                 self._edit_program(p, i, t, scale, start_noise).run(s)
-                target = 0 if path is None else (path[i + 1] if i + 1 < len(ts) else x0).data_ptr()
-                d = lib.DdpmEditDesc(eps=io["eps"].ptr, x=x.data_ptr(), target=target, resid=resid[i].data_ptr(), out=x.data_ptr(),
-                                     out_bf16=smp.ptr, out2_bf16=smp.ptr + bs * chw * 2, nb=bs, chw=chw, guidance=float(guidance),
-                                     mode=0 if path is not None else 1, v_prediction=v,
-                                     **fp32_coefficients(ddpm_step_coefficients(self.sched, t, steps, eta)))
-                lib.call(lib.OP_DDPM_EDIT, d, s)
+                src, dst = (x, x) if record is None else (x if i == 0 else record[i - 1], record[i])
+                target = None if path is None else (path[i + 1] if i + 1 < len(ts) else x0)
+                self._launch_step(p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask)
         finally:
             self._restore()
             if self.store is not None:
                 eng.set_lora(False)
-        return x
+        return x if record is None else record[-1].clone()
 
     @torch.no_grad()
     def invert(self, ctx: torch.Tensor, x0_latents: torch.Tensor, steps: int = 50, skip: Optional[int] = None, eta: float = 1.0,
@@ -256,25 +407,56 @@ class SliderEditor(SliderSampler):
         bs, _, h, w = x0.shape
         p = self._load_inputs(bs, h, w, ctx, pooled, time_ids)
         path = build_path(self.sched, x0, ts, seed)
-        resid = torch.empty_like(path)
-        x = self._chain(p, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0)
+        resid, visited = torch.empty_like(path), torch.empty_like(path)
+        x = self._chain(p, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0, record=visited)
         return NoiseSpace(x0=x0, x_start=path[0].clone(), resid=resid, recon=x, timesteps=list(ts), steps=int(steps),
                           skip=steps - len(ts), eta=float(eta), guidance=float(guidance_scale),
                           prediction_type=self.sched.prediction_type, seed=int(seed), ctx=ctx.detach().clone(),
                           pooled=None if pooled is None else pooled.detach().clone(),
-                          time_ids=None if time_ids is None else time_ids.detach().clone())
+                          time_ids=None if time_ids is None else time_ids.detach().clone(), visited=visited)
+
+    def _check_prediction(self, space: NoiseSpace):
+        if space.prediction_type != self.sched.prediction_type:
+            raise ValueError(f"the NoiseSpace was inverted with {space.prediction_type}, this editor predicts {self.sched.prediction_type}")
+
+    @staticmethod
+    def _check_conditioning(space: NoiseSpace, what: str):
+        if space.ctx is None:
+            raise ValueError(f"{what}: this NoiseSpace carries no conditioning (set space.ctx to the inversion's)")
+
+    @torch.no_grad()
+    def trajectory(self, space: NoiseSpace) -> NoiseSpace:
+        """Fills space.visited where it is missing (a file saved before masked edits) by one scale-0 replay with the inversion's
+        conditioning and guidance - the inversion's latents again, bit for bit, by the identity the whole method rests on; raises if
+        the replay does not end on space.recon (other weights, another engine: its latents are then not this inversion's)."""
+        if space.visited is not None:
+            return space
+        self._check_prediction(space)
+        self._check_conditioning(space, "trajectory")
+        dev = self.eng.device
+        x = space.x_start.to(dev, torch.float32).clone().contiguous()
+        resid = space.resid.to(dev, torch.float32).contiguous()
+        bs, _, h, w = x.shape
+        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids)
+        visited = torch.empty_like(resid)
+        end = self._chain(p, x, space.timesteps, space.steps, space.eta, space.guidance, 0.0, -1, resid, record=visited)
+        if not torch.equal(end, space.recon.to(dev)):
+            raise RuntimeError("trajectory: the scale-0 replay does not end on space.recon bit for bit: this NoiseSpace was not inverted "
+                               "with these weights and this conditioning")
+        space.visited = visited.to(space.recon.device)
+        return space
 
     @torch.no_grad()
     def edit_latents(self, space: NoiseSpace, ctx: Optional[torch.Tensor] = None, scale: float = 0.0, start_noise: int = 750,
                      guidance_scale: Optional[float] = None, pooled: Optional[torch.Tensor] = None,
-                     time_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> the edited latents (bs, 4, h, w) fp32.  ctx / guidance_scale None: the inversion's own - then scale 0 returns
-        space.recon bit for bit.  Another prompt or guidance is an edit of its own; no reconstruction claim applies."""
-        if space.prediction_type != self.sched.prediction_type:
-            raise ValueError(f"the NoiseSpace was inverted with {space.prediction_type}, this editor predicts {self.sched.prediction_type}")
+        space.recon bit for bit.  Another prompt or guidance is an edit of its own; no reconstruction claim applies.
+        mask ([h][w], [bs][h][w] or [bs][1][h][w], values in [0, 1], 1 = edit): every step is blended against the inversion's latent
+        after that step, so where the mask is 0 the result is space.recon bit for bit - at any scale, prompt or guidance."""
+        self._check_prediction(space)
         if ctx is None:
-            if space.ctx is None:
-                raise ValueError("edit_latents: this NoiseSpace carries no conditioning; pass ctx")
+            self._check_conditioning(space, "edit_latents without ctx")
             ctx = space.ctx
             pooled = space.pooled if pooled is None else pooled
             time_ids = space.time_ids if time_ids is None else time_ids
@@ -282,13 +464,64 @@ class SliderEditor(SliderSampler):
         x = space.x_start.to(dev, torch.float32).clone().contiguous()
         resid = space.resid.to(dev, torch.float32).contiguous()
         bs, _, h, w = x.shape
+        visited = None
+        if mask is not None:
+            mask = as_mask(mask, bs, h, w).to(dev)
+            visited = self.trajectory(space).visited.to(dev, torch.float32).contiguous()
         p = self._load_inputs(bs, h, w, ctx, pooled, time_ids)
         g = space.guidance if guidance_scale is None else guidance_scale
-        return self._chain(p, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid)
+        return self._chain(p, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask)
+
+    @torch.no_grad()
+    def footprint(self, space: NoiseSpace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200) -> torch.Tensor:
+        """Where the slider acts on this image: F [bs][h][w] fp32 = the mean over `draws` noise levels of
+        sum_c |eps(slider at `scale`) - eps(slider off)| (slh_eps_absdiff), each draw divided by its mean over the pixels - DiffEdit's
+        contrast (Couairon et al. 2022) with the slider in place of the second prompt.  The UNet inputs are the inversion's own at
+        those levels (x_start / visited[i - 1]: the image under independent noise draws), conditioning and guidance the inversion's.
+        All slider-off passes run first, then the slider is switched on once (store=: the multiplier; sliders=: one merge, full
+        program on the first pass after it) for the slider-on passes: 2 * len(draws) UNet passes."""
+        from . import lib
+        self._check_prediction(space)
+        self._check_conditioning(space, "footprint")
+        idx = footprint_draws(space.timesteps, start_noise, draws, t_min)
+        eng, dev = self.eng, self.eng.device
+        visited = self.trajectory(space).visited.to(dev, torch.float32)
+        x_start = space.x_start.to(dev, torch.float32)
+        bs, ch, h, w = x_start.shape
+        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids)
+        io = p.io
+        smp = io["sample"]
+        off = torch.empty((len(idx),) + tuple(io["eps"].tensor.shape), dtype=torch.bfloat16, device=dev)
+        A = torch.empty((len(idx), bs, h, w), dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream().cuda_stream
+
+        def unet(n, i, multiplier):
+            """pass n of this call at step i of the grid; n and the multiplier choose the program as in the edit's chain"""
+            xb = (x_start if i == 0 else visited[i - 1]).to(torch.bfloat16)
+            smp.tensor[:bs].copy_(xb)
+            smp.tensor[bs:].copy_(xb)
+            if self.store is not None:
+                eng.set_lora(True, float(multiplier))
+            io["t"].tensor.fill_(float(space.timesteps[i]))
+            self._edit_program(p, n, space.timesteps[i], multiplier, start_noise).run(s)
+        try:
+            for j, i in enumerate(idx):
+                unet(j, i, 0.0)
+                off[j].copy_(io["eps"].tensor)
+            for j, i in enumerate(idx):
+                unet(len(idx) + j, i, scale)
+                d = lib.EpsAbsdiffDesc(eps_a=io["eps"].ptr, eps_b=off[j].data_ptr(), out=A[j].data_ptr(), nb=bs, chw=ch * h * w, hw=h * w,
+                                       guidance=float(space.guidance))
+                lib.call(lib.OP_EPS_ABSDIFF, d, s)
+        finally:
+            self._restore()
+            if self.store is not None:
+                eng.set_lora(False)
+        return footprint_mean(A)
 
     @torch.no_grad()
     def edit(self, space: NoiseSpace, **kw) -> torch.Tensor:
-        """-> uint8 images [bs][H][W][3] (needs a VaeDecoder)."""
+        """-> uint8 images [bs][H][W][3] (needs a VaeDecoder); the arguments of edit_latents, mask= included."""
         if self.decoder is None:
             raise RuntimeError("SliderEditor.edit needs a VaeDecoder")
         return VaeDecoder.to_uint8(self.decoder.decode(self.edit_latents(space, **kw)))
@@ -322,6 +555,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--out", default="edited")
+    p.add_argument("--mask", default=None, help="localise the edits: an image file, white = edit, black = keep the reconstruction bit for bit")
+    p.add_argument("--mask_invert", action="store_true", help="with --mask: black = edit")
+    p.add_argument("--mask_feather", type=float, default=None, metavar="SIGMA",
+                   help="Gaussian feathering of the mask in latent pixels (default 0 with --mask, 1 with --auto_mask)")
+    p.add_argument("--auto_mask", action="store_true", help="localise the edits to the slider's own footprint on this image")
+    p.add_argument("--auto_mask_scale", type=float, default=None, help="slider scale the footprint is measured at (default: the largest |scale| of --scales)")
+    p.add_argument("--auto_mask_draws", type=int, default=None, help="noise levels the footprint averages over (default 8)")
+    p.add_argument("--auto_mask_threshold", type=float, default=None, help="binarisation threshold of the footprint (default 0.5)")
+    p.add_argument("--auto_mask_dilate", type=int, default=None, help="latent pixels the binary footprint is grown by (default 1)")
+    p.add_argument("--save_mask", default=None, help="write the latent-resolution mask here (8-bit PNG)")
     return p
 
 
@@ -344,6 +587,37 @@ def check_args(a):
         scales = [float(v) for v in a.scales.split(",")]
     except ValueError:
         raise SystemExit(f"--scales {a.scales!r}: expected comma-separated numbers")
+    if a.mask and a.auto_mask:
+        raise SystemExit("--mask reads a mask, --auto_mask derives one from the slider: give one of them")
+    if a.mask and not os.path.isfile(a.mask):
+        raise SystemExit(f"--mask {a.mask}: no such file")
+    if a.mask_invert and not a.mask:
+        raise SystemExit("--mask_invert needs --mask")
+    if not (a.mask or a.auto_mask) and (a.mask_feather is not None or a.save_mask):
+        raise SystemExit("--mask_feather / --save_mask need --mask or --auto_mask")
+    if a.mask_feather is not None and not 0.0 <= a.mask_feather < float("inf"):
+        raise SystemExit(f"--mask_feather {a.mask_feather}: expected a finite sigma >= 0")
+    given = [n for n in ("scale", "draws", "threshold", "dilate") if getattr(a, "auto_mask_" + n) is not None]
+    if given and not a.auto_mask:
+        raise SystemExit("--auto_mask_" + given[0] + " needs --auto_mask")
+    if a.auto_mask:
+        if not a.lora_weight and not a.compose:
+            raise SystemExit("--auto_mask is the slider's footprint: it needs --lora_weight (or --compose)")
+        if a.auto_mask_scale is None:
+            a.auto_mask_scale = max(scales, key=abs)
+        if a.auto_mask_scale == 0.0:
+            raise SystemExit("--auto_mask: the footprint is measured at a non-zero scale (--auto_mask_scale, or a non-zero entry of --scales)")
+        if a.auto_mask_draws is not None and a.auto_mask_draws < 1:
+            raise SystemExit(f"--auto_mask_draws {a.auto_mask_draws}: expected at least 1")
+        if a.auto_mask_threshold is not None and not 0.0 < a.auto_mask_threshold <= 1.0:
+            raise SystemExit(f"--auto_mask_threshold {a.auto_mask_threshold}: expected 0 < threshold <= 1")
+        if a.auto_mask_dilate is not None and a.auto_mask_dilate < 0:
+            raise SystemExit(f"--auto_mask_dilate {a.auto_mask_dilate}: expected >= 0")
+        grid = edit_timesteps(DDIMSchedule(), a.steps, skip)
+        try:
+            footprint_draws(grid, a.start_noise, a.auto_mask_draws or 8)
+        except ValueError as e:
+            raise SystemExit(f"--auto_mask: {e}")
     return scales
 
 
@@ -414,6 +688,20 @@ def main(argv=None):
     os.makedirs(a.out, exist_ok=True)
     Image.fromarray(VaeDecoder.to_uint8(dec.decode(space.recon))[0].cpu().numpy()).save(os.path.join(a.out, "recon.png"))
     kw = dict(start_noise=a.start_noise, guidance_scale=a.edit_guidance_scale)
+    if a.mask:
+        kw["mask"] = feather_mask(load_mask(a.mask, 8 * space.x0.shape[-1], a.mask_invert), a.mask_feather or 0.0)    # a saved inversion: its size
+    elif a.auto_mask:
+        try:          # (check_args tried the grid of --steps / --skip; a saved inversion brings its own)
+            F = ed.footprint(space, a.auto_mask_scale, start_noise=a.start_noise, draws=a.auto_mask_draws or 8)
+            kw["mask"] = footprint_mask(F.cpu(), threshold=0.5 if a.auto_mask_threshold is None else a.auto_mask_threshold,
+                                        dilate=1 if a.auto_mask_dilate is None else a.auto_mask_dilate,
+                                        feather=1.0 if a.mask_feather is None else a.mask_feather)
+        except ValueError as e:
+            raise SystemExit(f"--auto_mask: {e}")
+    if a.save_mask:
+        m8 = (kw["mask"].reshape(kw["mask"].shape[-2:]) * 255.0).round().to(torch.uint8)
+        Image.fromarray(m8.cpu().numpy()).save(a.save_mask)
+        print(f"mask saved to {a.save_mask}: mean {float(kw['mask'].mean()):.3f}")
     if a.edit_prompt is not None:
         kw.update(ctx=cond[1][0].to(dev), pooled=None if cond[1][1] is None else cond[1][1].to(dev))
     for s in scales:

@@ -73,6 +73,12 @@ CfgDdimDesc = _struct("CfgDdimDesc", _ptrs("eps", "x", "out", "out2", "eps_text"
 DdpmEditDesc = _struct("DdpmEditDesc", _ptrs("eps", "eps_text", "x", "target", "resid", "out", "out_bf16", "out2_bf16") + _ints("nb", "chw")
                        + [(n, c_f32) for n in ("guidance", "c_sqrt_beta_t", "c_inv_sqrt_alpha_t", "c_sqrt_alpha_t", "c_sqrt_alpha_prev", "c_dir")]
                        + _ints("mode", "v_prediction"))
+DdpmEditBlendDesc = _struct("DdpmEditBlendDesc", _ptrs("eps", "eps_text", "x", "resid", "keep", "mask", "out", "out_bf16", "out2_bf16")
+                            + _ints("nb", "chw", "hw")
+                            + [(n, c_f32) for n in ("guidance", "c_sqrt_beta_t", "c_inv_sqrt_alpha_t", "c_sqrt_alpha_t", "c_sqrt_alpha_prev", "c_dir")]
+                            + _ints("v_prediction"))
+EpsAbsdiffDesc = _struct("EpsAbsdiffDesc", _ptrs("eps_a", "eps_a_text", "eps_b", "eps_b_text", "out") + _ints("nb", "chw", "hw")
+                         + [("guidance", c_f32)])
 LossDesc = _struct("LossDesc", _ptrs("target", "positive", "neutral", "uncond", "loss", "dtarget", "dtarget_pix")
                    + _ints("n") + [("guidance", c_f32)] + _ints("erase", "hw", "nch"))
 WgradDesc = _struct("WgradDesc", _ptrs("z0", "z1", "v", "out", "scale")
@@ -112,7 +118,7 @@ VaeSampleDesc = _struct("VaeSampleDesc", _ptrs("moments", "post_noise", "noise",
 _SIZE_ORDER = [GemmDesc, SkinnyDesc, GemvDesc, GnDesc, GnBwdDesc, LnDesc, LnBwdDesc, AttnDesc, TransposeDesc,
                AttnBwdDesc, TembedDesc, ConvInDesc, EwDesc, CfgDdimDesc, LossDesc, WgradDesc, AdamwDesc, MemsetDesc,
                LoraCdgradDesc, TembLoraBwdDesc, SgemmDesc, Gn32Desc, Softmax32Desc, VaeConvDesc, VaeSampleDesc, LionDesc,
-               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc, DdpmEditDesc]
+               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc, DdpmEditDesc, DdpmEditBlendDesc, EpsAbsdiffDesc]
 
 # opcodes (enum in sliders_hip.h)
 OP_GEMM, OP_SKINNY, OP_GEMV, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTN_FWD, OP_TRANSPOSE_HEADS = range(1, 9)
@@ -125,6 +131,7 @@ OP_WGRAD_BATCH, OP_TRANSPOSE_BATCH, OP_GATHER16, OP_GN_FUSED = 32, 33, 34, 35
 OP_LORA_LN_FOLD = 36
 OP_LORA_MERGE = 38
 OP_DDPM_EDIT = 39
+OP_DDPM_EDIT_BLEND, OP_EPS_ABSDIFF = 40, 41
 
 EW_COPY, EW_ADD, EW_GEGLU_FWD, EW_GEGLU_BWD, EW_UPSAMPLE_BWD, EW_COLSUM = range(6)
 
@@ -148,6 +155,7 @@ _ENTRY = {
     OP_GATHER16: ("slh_gather16", Gather16Desc), OP_GN_FUSED: ("slh_gn_fused", GnDesc),
     OP_LORA_LN_FOLD: ("slh_lora_ln_fold", LoraLnFoldDesc), OP_LORA_MERGE: ("slh_lora_merge", LoraMergeDesc),
     OP_DDPM_EDIT: ("slh_ddpm_edit_step", DdpmEditDesc),
+    OP_DDPM_EDIT_BLEND: ("slh_ddpm_edit_blend", DdpmEditBlendDesc), OP_EPS_ABSDIFF: ("slh_eps_absdiff", EpsAbsdiffDesc),
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
