@@ -218,6 +218,10 @@ typedef struct slh_skinny_desc {
     int32_t w_kmajor;        /* 1: w is [K][4] (R must be 4): U = dY . B with B = lora_up [out][r] as stored */
 } slh_skinny_desc;
 int slh_skinny(const slh_skinny_desc* d, slh_stream_t stream);
+/* The kernel instantiation slh_skinny would launch for d, written to buf (cap >= 32): "skinny<RMAX,LPR>" with RMAX in {4, 12, 16} the
+ * accumulator rows compiled in (rows past R are masked) and LPR in {64, 16} the lanes that share one output row.  Answered by the
+ * selection function slh_skinny itself launches through; no device needed, nothing launched.  0, or the error slh_skinny would give. */
+int slh_skinny_kernel_name(const slh_skinny_desc* d, char* buf, int cap);
 
 /* ------------------------------------------------------------------------------------------------
  * slh_gemv: y[b][n] = x'[b][:] . W[n][:] + bias[n] + addend[b][n] + lora,  b < nb <= 8 (weight-streaming).
@@ -516,7 +520,8 @@ typedef struct slh_wgrad_desc {
     int32_t mode, batch, hs, ws, src_xform, stride, ho, wo;
     int32_t M, R, ldv, ldo;
     int32_t out_rmajor;      /* 1: out is [R][ldo] (down-weight layout), 0: [C][ldo] (up-weight layout) */
-    int32_t vgroup_cols;     /* >0: channel c uses V columns 4*(c/vgroup_cols).. (fused q/k/v up grads) */
+    int32_t vgroup_cols;     /* >0: channel c uses V columns 4*(c/vgroup_cols).. (fused q/k/v up grads).  Contract (refused otherwise): a
+                                multiple of 8 (the offset is taken once per 8-channel chunk) that divides c0 + c1, and R == 4 */
     float* slabs;            /* fixed-order reduction over the M splits (bit-reproducible gradients): slh_lora_wgrad_single_blocks(d)
                                 slabs of 256 * R floats (contents irrelevant) ... */
     void* tickets;           /* ... and as many uint32 arrival tickets, zeroed once (the last arriver re-arms them).  Both NULL:
@@ -525,6 +530,11 @@ typedef struct slh_wgrad_desc {
 } slh_wgrad_desc;
 int slh_lora_wgrad(const slh_wgrad_desc* d, slh_stream_t stream);
 int slh_lora_wgrad_single_blocks(const slh_wgrad_desc* d);
+/* Launch geometry of d's problem as the library's one geometry function gives it, out4 = {gx (column blocks of 256 channels), splits
+ * (of M), taps (9 in conv mode), rows_per_block}, for kind 0 (fp32 atomics, single or batched), 1 (single launch with slabs) or 2 (a
+ * problem of a batch with slabs).  Shape fields only, no device needed.  gx * splits * taps is what slh_lora_wgrad_blocks (kind 2 / 0) and
+ * slh_lora_wgrad_single_blocks (kind 1) return.  0, or -1 + slh_last_error(). */
+int slh_lora_wgrad_geometry(const slh_wgrad_desc* d, int kind, int32_t* out4);
 
 /* Batched launches: n independent problems of one kind in ONE launch (the backward of a UNet pass has ~380 rank-4
  * weight-gradient reductions and ~210 head transposes of forward activations, each far too small to fill the chip).
@@ -538,7 +548,12 @@ typedef struct slh_batch_desc {
     int32_t pad_;
     void* slabs;             /* slh_lora_wgrad_batch: `total` slabs of 256 * R floats + ... */
     void* tickets;           /* ... `total` uint32 tickets (zeroed once): fixed-order reduction, every problem's descriptor built
-                                with a non-NULL slabs; both NULL: fp32 atomics */
+                                with a non-NULL slabs; both NULL: fp32 atomics.  Contract: prefix takes each problem's geometry
+                                from its descriptor's slabs (slh_lora_wgrad_blocks), the kernel takes it from the batch's, and the
+                                table is device memory the launch cannot read back: ALL descriptors of a batch are built with
+                                slabs, or none, and the batch carries slabs exactly when they are - workgroups index past their
+                                problem otherwise.  lib.batch_table refuses a mixed table and lib.call / Program.add a batch whose
+                                slabs disagree with its table */
 } slh_batch_desc;
 int slh_lora_wgrad_blocks(const slh_wgrad_desc* d);
 int slh_lora_wgrad_batch(const slh_batch_desc* d, slh_stream_t stream);
@@ -556,7 +571,9 @@ int slh_gather16(const slh_gather16_desc* d, slh_stream_t stream);
 typedef struct slh_lora_lnfold_item {
     const void* a; const void* gamma; const void* beta;   /* bf16 [rows][K], [K], [K] */
     void* a_out; float* s_out; float* c_out;               /* bf16 [rows][K], fp32 [rows], fp32 [rows] */
-    int32_t rows, K;                                       /* rows <= 16, K % 8 == 0 */
+    int32_t rows, K;                                       /* K % 8 == 0.  Contract: rows <= 16 - the grid is 16 rows per item, further
+                                                              rows would be silently left out; the items live in device memory, so
+                                                              whoever builds them checks (lib.lnfold_item) */
 } slh_lora_lnfold_item;
 typedef struct slh_lora_lnfold_desc { const slh_lora_lnfold_item* items; int32_t n; int32_t pad_; } slh_lora_lnfold_desc;
 int slh_lora_ln_fold(const slh_lora_lnfold_desc* d, slh_stream_t stream);

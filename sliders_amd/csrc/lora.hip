@@ -407,6 +407,19 @@ static int fill_addr(AddrArgs& A, const void* a0, const void* a1, int lda0, int 
     return 0;
 }
 
+// The one place that decides which skinny_kernel<RMAX, LPR> runs a descriptor: slh_skinny launches what this returns and
+// slh_skinny_kernel_name names it through the same launch statements.  RMAX: accumulator rows compiled in (rows past R are masked);
+// LPR: one wave per row while that still gives < ~8 waves per SIMD of work, 16 lanes per row beyond
+struct skinny_form { int rmax, lpr, grid; };
+static skinny_form skinny_choose(int M, int R) {
+    skinny_form f;
+    f.rmax = R <= 4 ? 4 : R <= 12 ? 12 : 16;
+    f.lpr = M <= 16384 ? 64 : 16;
+    const int rows = 256 / f.lpr;
+    f.grid = (M + rows - 1) / rows;
+    return f;
+}
+
 extern "C" int slh_skinny(const slh_skinny_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->a0 && d->w && d->out, "slh_skinny: null pointer");
     SLH_CHECK(d->M > 0 && d->R > 0 && d->R <= 16 && d->K > 0, "slh_skinny: bad shape");
@@ -426,25 +439,37 @@ extern "C" int slh_skinny(const slh_skinny_desc* d, slh_stream_t stream) {
     fill_addr(A, d->a0, d->a1, d->lda0, d->lda1, d->ca0, d->ca1, d->mode, d->hs, d->ws, d->src_xform, d->stride,
               d->ho, d->wo);
     hipStream_t s = (hipStream_t)stream;
-    // one wave per row while that still gives < ~8 waves per SIMD of work; 16 lanes per row beyond
-    const bool wide = d->M <= 16384;
-#define SLH_SKINNY_LAUNCH(RM)                                                                                      \
+    const skinny_form f = skinny_choose(d->M, d->R);
+#define SLH_SKINNY_LAUNCH(RM, LPR)                                                                                 \
     do {                                                                                                           \
-        if (wide)                                                                                                  \
-            hipLaunchKernelGGL((skinny_kernel<RM, 64>), dim3((d->M + 3) / 4), dim3(256), 0, s, A,                  \
-                               (const __bf16*)d->w, (const __bf16*)d->bias, d->out, d->M, d->R, d->K, d->ldo,      \
-                               d->out_kind, d->w_kmajor);                                                          \
+        if (slh_name_mode()) slh_name_record("skinny<%d,%d>", RM, LPR);                                            \
         else                                                                                                       \
-            hipLaunchKernelGGL((skinny_kernel<RM, 16>), dim3((d->M + 15) / 16), dim3(256), 0, s, A,                \
-                               (const __bf16*)d->w, (const __bf16*)d->bias, d->out, d->M, d->R, d->K, d->ldo,      \
-                               d->out_kind, d->w_kmajor);                                                          \
+            hipLaunchKernelGGL((skinny_kernel<RM, LPR>), dim3(f.grid), dim3(256), 0, s, A, (const __bf16*)d->w,    \
+                               (const __bf16*)d->bias, d->out, d->M, d->R, d->K, d->ldo, d->out_kind, d->w_kmajor); \
     } while (0)
-    if (d->R <= 4) SLH_SKINNY_LAUNCH(4);
-    else if (d->R <= 12) SLH_SKINNY_LAUNCH(12);
-    else SLH_SKINNY_LAUNCH(16);
+#define SLH_SKINNY_ROWS(RM)                                                                                        \
+    do {                                                                                                           \
+        if (f.lpr == 64) SLH_SKINNY_LAUNCH(RM, 64);                                                                \
+        else SLH_SKINNY_LAUNCH(RM, 16);                                                                            \
+    } while (0)
+    if (f.rmax == 4) SLH_SKINNY_ROWS(4);
+    else if (f.rmax == 12) SLH_SKINNY_ROWS(12);
+    else SLH_SKINNY_ROWS(16);
+#undef SLH_SKINNY_ROWS
 #undef SLH_SKINNY_LAUNCH
     SLH_LAUNCH_CHECK("slh_skinny");
     return 0;
+}
+
+// the instantiation slh_skinny would launch for d ("skinny<12,16>": RMAX, lanes per row): the whole of slh_skinny runs - descriptor
+// checks, skinny_choose - with the launch replaced by a record of the selected template.  No device needed, nothing launched.
+extern "C" int slh_skinny_kernel_name(const slh_skinny_desc* d, char* buf, int cap) {
+    SLH_CHECK(buf && cap >= 32, "slh_skinny_kernel_name: buffer");
+    slh_name_sink_set(buf, cap);
+    const int rc = slh_skinny(d, nullptr);
+    slh_name_sink_set(nullptr, 0);
+    if (rc == 0 && !buf[0]) { slh_set_error("slh_skinny_kernel_name: internal: no launch site recorded a name"); return -3; }
+    return rc;
 }
 
 extern "C" int slh_gemv(const slh_gemv_desc* d, slh_stream_t stream) {
@@ -467,6 +492,12 @@ static int wgrad_check(const slh_wgrad_desc* d, bool ptrs = true) {
     if (ptrs) SLH_CHECK((d->z1 != nullptr) == (d->c1 > 0), "slh_lora_wgrad: z1/c1 mismatch");
     SLH_CHECK(d->M > 0 && d->c0 + d->c1 > 0, "slh_lora_wgrad: empty problem");
     if (d->mode == 1) SLH_CHECK(d->M == d->batch * d->ho * d->wo, "slh_lora_wgrad: conv M mismatch");
+    // the V column offset 4 * (c / vgroup_cols) is taken once per 8-channel chunk and addresses groups of 4 columns
+    if (d->vgroup_cols > 0)
+        SLH_CHECK(d->vgroup_cols % 8 == 0 && (d->c0 + d->c1) % d->vgroup_cols == 0 && d->R == 4,
+                  "slh_lora_wgrad: vgroup_cols %d needs a multiple of 8 that divides C = %d, and R = 4 (R = %d)", d->vgroup_cols,
+                  d->c0 + d->c1, d->R);
+    SLH_CHECK(d->vgroup_cols >= 0, "slh_lora_wgrad: negative vgroup_cols");
     return 0;
 }
 
@@ -494,6 +525,14 @@ extern "C" int slh_lora_wgrad_single_blocks(const slh_wgrad_desc* d) {
     if (wgrad_check(d, false)) return -1;
     const WgradGeom g = wgrad_geom(d->c0 + d->c1, d->M, d->mode, 1);
     return g.gx * g.splits * g.taps;
+}
+
+extern "C" int slh_lora_wgrad_geometry(const slh_wgrad_desc* d, int kind, int32_t* out4) {
+    if (wgrad_check(d, false)) return -1;
+    SLH_CHECK(kind >= 0 && kind <= 2 && out4, "slh_lora_wgrad_geometry: kind must be 0, 1 or 2");
+    const WgradGeom g = wgrad_geom(d->c0 + d->c1, d->M, d->mode, kind);
+    out4[0] = g.gx; out4[1] = g.splits; out4[2] = g.taps; out4[3] = g.rows_per_block;
+    return 0;
 }
 
 extern "C" int slh_lora_wgrad_batch(const slh_batch_desc* d, slh_stream_t stream) {

@@ -106,6 +106,15 @@ BatchDesc = _struct("BatchDesc", _ptrs("table", "prefix") + _ints("n", "total", 
 Gather16Desc = _struct("Gather16Desc", _ptrs("src", "idx", "out") + [("n", c_i64)])
 LoraLnFoldDesc = _struct("LoraLnFoldDesc", _ptrs("items") + _ints("n", "pad_"))
 LORA_LNFOLD_ITEM_I64 = 7          # slh_lora_lnfold_item as int64 words: a, gamma, beta, a_out, s_out, c_out, rows | K << 32
+LORA_LNFOLD_MAX_ROWS = 16         # the kernel's grid is 16 rows per item
+
+
+def lnfold_item(a: int, gamma: int, beta: int, a_out: int, s_out: int, c_out: int, rows: int, K: int) -> tuple:
+    """One slh_lora_lnfold_item as int64 words.  The items live in device memory where the library cannot check them, so the limits of
+    the kernel are checked here: rows <= 16 (its grid; further rows would be left out silently) and K % 8 == 0."""
+    if not (1 <= rows <= LORA_LNFOLD_MAX_ROWS) or K <= 0 or K % 8:
+        raise SlidersHipError(f"slh_lora_ln_fold item: rows = {rows} must be 1..{LORA_LNFOLD_MAX_ROWS} and K = {K} a positive multiple of 8")
+    return (a, gamma, beta, a_out, s_out, c_out, rows | (K << 32))
 LoraMergeDesc = _struct("LoraMergeDesc", _ptrs("items", "prefix") + _ints("n", "total"))
 # slh_lora_merge_item: one row range of one stored matrix (include/sliders_hip.h)
 LoraMergeItem = _struct("LoraMergeItem", _ptrs("base", "out", "u", "d", "c", "gamma", "beta", "bias", "lns", "lnb")
@@ -160,7 +169,7 @@ _ENTRY = {
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
            "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_launch_query", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_attn_fwd_kernel_name", "slh_attn_bwd_kernel_names", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
-           "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
+           "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_lora_wgrad_geometry", "slh_skinny_kernel_name", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
 
 
 class SlidersHipError(RuntimeError):
@@ -291,6 +300,13 @@ def batch_table(opcode: int, descs, device, arg: int = 0):
     fn.argtypes = [C.POINTER(dtype)]
     fn.restype = c_i32
     prefix = [0]
+    slab_geom = 0
+    if opcode == OP_WGRAD_BATCH:
+        # slh_lora_wgrad_blocks takes the geometry from each descriptor's slabs, the kernel from the batch's: one choice per batch
+        kinds = {bool(d.slabs) for d in descs}
+        if len(kinds) > 1:
+            raise SlidersHipError("slh_lora_wgrad_batch: the problems of one batch must all be built with slabs or all without")
+        slab_geom = int(kinds.pop()) if kinds else 0
     for d in descs:
         assert isinstance(d, dtype)
         nb = fn(C.byref(d))         # host-side geometry only: also in dry-run planning (the arena is sized from it)
@@ -298,11 +314,28 @@ def batch_table(opcode: int, descs, device, arg: int = 0):
             raise SlidersHipError(f"{fn_name}: {last_error()}")
         prefix.append(prefix[-1] + nb)
     if device is None:
-        return BatchDesc(table=0x1000, prefix=0x1000, n=len(descs), total=prefix[-1], arg=arg), ()
+        bd = BatchDesc(table=0x1000, prefix=0x1000, n=len(descs), total=prefix[-1], arg=arg)
+        bd.slab_geom = slab_geom
+        return bd, ()
     raw = b"".join(bytes(d) for d in descs)
     table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
     pre = torch.tensor(prefix, dtype=torch.int32, device=device)
-    return BatchDesc(table=table.data_ptr(), prefix=pre.data_ptr(), n=len(descs), total=prefix[-1], arg=arg), (table, pre)
+    bd = BatchDesc(table=table.data_ptr(), prefix=pre.data_ptr(), n=len(descs), total=prefix[-1], arg=arg)
+    bd.slab_geom = slab_geom          # (a Python attribute, not a field: checked by check_batch before every launch / recording)
+    return bd, (table, pre)
+
+
+def check_batch(opcode: int, desc):
+    """A weight-gradient batch carries slabs exactly when its table was built from descriptors with slabs (batch_table): prefix holds
+    the workgroup counts of that geometry and the kernel picks its geometry from the batch's slabs - refuse a disagreement here, on
+    the host, before anything is launched or recorded."""
+    if opcode == OP_WGRAD_BATCH and isinstance(desc, BatchDesc):
+        geom = getattr(desc, "slab_geom", None)
+        if geom is None:
+            raise SlidersHipError("slh_lora_wgrad_batch: build the batch descriptor with lib.batch_table (it records the table's geometry)")
+        if bool(desc.slabs) != bool(geom):
+            raise SlidersHipError(f"slh_lora_wgrad_batch: the table was built for the {'slab' if geom else 'atomic'} geometry, the batch "
+                                  f"{'carries' if desc.slabs else 'has no'} slabs")
 
 
 def merge_table(items, device):
@@ -332,6 +365,31 @@ def wgrad_single_blocks(desc) -> int:
     if nb <= 0:
         raise SlidersHipError(f"slh_lora_wgrad_single_blocks: {last_error()}")
     return nb
+
+
+def wgrad_geometry(desc, kind: int):
+    """slh_lora_wgrad_geometry: (gx, splits, taps, rows_per_block) of desc's problem for kind 0 (fp32 atomics), 1 (single launch with
+    slabs) or 2 (inside a batch with slabs), from the library's one geometry function; shape fields only, no device needed."""
+    lib = load()
+    lib.slh_lora_wgrad_geometry.argtypes = [C.POINTER(WgradDesc), c_i32, C.POINTER(c_i32)]
+    lib.slh_lora_wgrad_geometry.restype = c_i32
+    out = (c_i32 * 4)()
+    if lib.slh_lora_wgrad_geometry(C.byref(desc), kind, out) != 0:
+        raise SlidersHipError(f"slh_lora_wgrad_geometry: {last_error()}")
+    return tuple(out)
+
+
+def skinny_kernel_name(desc) -> str:
+    """slh_skinny_kernel_name: the instantiation slh_skinny would launch for this descriptor ('skinny<12,16>': accumulator rows, lanes
+    per output row), named by the selection function slh_skinny launches through; raises for a descriptor slh_skinny refuses."""
+    lib = load()
+    lib.slh_skinny_kernel_name.argtypes = [C.POINTER(SkinnyDesc), C.c_char_p, c_i32]
+    lib.slh_skinny_kernel_name.restype = c_i32
+    buf = C.create_string_buffer(64)
+    rc = lib.slh_skinny_kernel_name(C.byref(desc), buf, 64)
+    if rc != 0:
+        raise SlidersHipError(f"slh_skinny_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
+    return buf.value.decode()
 
 
 def attn_carries_touch(desc) -> bool:
@@ -400,6 +458,7 @@ def call(opcode: int, desc, stream: int):
     """Launch one op directly (used by the per-kernel parity tests)."""
     lib = load()
     name, _ = _ENTRY[opcode]
+    check_batch(opcode, desc)
     check(getattr(lib, name)(C.byref(desc), c_vp(stream)), name)
 
 
@@ -437,6 +496,7 @@ class Program:
             pass
 
     def add(self, opcode: int, desc, name: str = ""):
+        check_batch(opcode, desc)
         raw = bytes(desc)
         pad = (-len(raw)) % 8
         hdr = C.c_int32 * 2

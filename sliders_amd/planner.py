@@ -429,8 +429,8 @@ class UNetPlan:
             a2 = self.arena.alloc((R, K), torch.bfloat16, name + ".lnA")
             sc = self.f32((2, 16), name + ".lnA_sc")
             d.lora_down, d.ln_lora_s, d.ln_lora_c = a2.ptr, sc.ptr, sc.ptr + 64
-            self.lnfold_items.append((self.lora.down_ptr(grp[0]), self.w.ptr(p.ln_norm + ".g"), self.w.ptr(p.ln_norm + ".b"),
-                                      a2.ptr, sc.ptr, sc.ptr + 64, R | (K << 32)))
+            self.lnfold_items.append(lib.lnfold_item(self.lora.down_ptr(grp[0]), self.w.ptr(p.ln_norm + ".g"), self.w.ptr(p.ln_norm + ".b"),
+                                                     a2.ptr, sc.ptr, sc.ptr + 64, R, K))
         provision_splitk(self, d, name)
         if p.ln_cols:
             st = self.f32((N // p.ln_cols, M, 2), name + ".ln_chunks")

@@ -1503,3 +1503,209 @@ def test_a_refused_layernorm_fold_plans_what_no_fold_plans(monkeypatch, name, hw
             got = pd.record(p, bw, va, vz)
         assert not any(d.ln_in for o, d in p.prog.ops if o == lib.OP_GEMM)
         assert got == want, mode
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LoRA helper kernels element by element (tests/lora_matrix.py, tests/test_lora_matrix_gpu.py, docs/LORA_MATRIX.md)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _lora_check(lm, c, mutant=None, **kw):
+    """{output: (worst ratio, b) or the failure text} of the stand-in of case c (mutant: with one defect) against reference and bound"""
+    from tests.util import check_elementwise
+    K = lm.KINDS[c.kind]
+    L = K["inputs"](c, torch.device("cpu"), 1)
+    got = K["standin"](c, L, mutant=mutant, **kw) if (mutant or kw) else K["standin"](c, L)
+    out = {}
+    for n, (r, bound) in K["reference"](c, L).items():
+        try:
+            if bound is None:
+                assert torch.equal(got[n], r), f"{c.id} [{n}]: not bit-exact"
+                out[n] = (0.0, None)
+            else:
+                w, _, b = check_elementwise(f"{c.id} [{n}]", got[n], r, bound)
+                out[n] = (w, b)
+        except AssertionError as e:
+            out[n] = str(e)
+    return out
+
+
+def test_lora_kernel_names_and_geometry_come_from_the_library():
+    """slh_skinny_kernel_name runs slh_skinny's own selection (no device, fake pointers) and refuses what slh_skinny refuses;
+    slh_lora_wgrad_geometry is the one geometry function: its products are what slh_lora_wgrad_blocks / _single_blocks return."""
+    from tests import lora_matrix as lm
+    names = {lm.form_of(c) for c in lm.CASES if c.kind == "skinny"}
+    assert names == set(lm.SKINNY_FORMS), names ^ set(lm.SKINNY_FORMS)
+    d = lm.skinny_descs(lm.Case("skinny", M=5, R=4, ca=(64, 0)))[0][1]
+    assert lib.skinny_kernel_name(d) == "skinny<4,64>"
+    d.K = 72
+    with pytest.raises(lib.SlidersHipError, match="slh_skinny"):
+        lib.skinny_kernel_name(d)
+    l = lib.load()
+    l.slh_lora_wgrad_blocks.argtypes = [ctypes.POINTER(lib.WgradDesc)]
+    for c in lm.CASES:
+        if c.kind != "wgrad":
+            continue
+        for d in lm.wgrad_descs(c):
+            for kind in (0, 1, 2):
+                gx, splits, taps, rpb = lib.wgrad_geometry(d, kind)
+                assert gx >= 1 and splits >= 1 and taps in (1, 9) and rpb % 8 == 0 and splits * rpb >= d.M > (splits - 1) * rpb, (c.id, kind)
+                if kind == 1:
+                    assert gx * splits * taps == lib.wgrad_single_blocks(d)
+                else:
+                    d.slabs = 8 if kind == 2 else 0
+                    assert gx * splits * taps == l.slh_lora_wgrad_blocks(ctypes.byref(d))
+    with pytest.raises(lib.SlidersHipError, match="kind"):
+        lib.wgrad_geometry(lm.wgrad_descs(lm.CASES[-1] if lm.CASES[-1].kind == "wgrad" else next(c for c in lm.CASES if c.kind == "wgrad"))[0], 3)
+
+
+def test_lora_contracts_are_refused_on_the_host():
+    """vgroup_cols that the kernel would mis-address, a weight-gradient batch whose table and workspace disagree about the geometry, and
+    a LayerNorm-fold item with more rows than the kernel's grid: all refused before anything is launched (no device needed)."""
+    one = 0x1000
+
+    def wg(**kw):
+        base = dict(z0=one, v=one, out=one, scale=one, ldz0=192, c0=192, mode=0, stride=1, M=64, R=4, ldv=12, ldo=4, vgroup_cols=64)
+        base.update(kw)
+        return lib.WgradDesc(**base)
+
+    assert lib.wgrad_single_blocks(wg()) > 0
+    for what, d in {"not a multiple of 8": wg(vgroup_cols=4), "does not divide C": wg(vgroup_cols=80), "R = 12": wg(R=12, ldo=12),
+                    "divides C but not by 8": wg(vgroup_cols=12), "negative": wg(vgroup_cols=-8)}.items():
+        with pytest.raises(lib.SlidersHipError, match="vgroup_cols"):
+            lib.wgrad_single_blocks(d)
+        with pytest.raises(lib.SlidersHipError, match="vgroup_cols"):
+            lib.call(lib.OP_WGRAD, d, 0)
+        with pytest.raises(lib.SlidersHipError, match="vgroup_cols"):
+            lib.batch_table(lib.OP_WGRAD_BATCH, [d], None, arg=d.R)
+    # batched: one geometry per batch, and the workspace must match it
+    with pytest.raises(lib.SlidersHipError, match="all be built with slabs or all without"):
+        lib.batch_table(lib.OP_WGRAD_BATCH, [wg(slabs=8, tickets=8), wg()], None, arg=4)
+    bd, _ = lib.batch_table(lib.OP_WGRAD_BATCH, [wg(M=2048), wg()], None, arg=4)            # atomic geometry ...
+    bd.slabs, bd.tickets = one, one                                                        # ... but a slab workspace
+    with pytest.raises(lib.SlidersHipError, match="atomic geometry"):
+        lib.call(lib.OP_WGRAD_BATCH, bd, 0)
+    with pytest.raises(lib.SlidersHipError, match="atomic geometry"):
+        lib.Program().add(lib.OP_WGRAD_BATCH, bd)
+    bd, _ = lib.batch_table(lib.OP_WGRAD_BATCH, [wg(M=2048, slabs=8, tickets=8)], None, arg=4)   # slab geometry, no workspace
+    with pytest.raises(lib.SlidersHipError, match="slab geometry"):
+        lib.call(lib.OP_WGRAD_BATCH, bd, 0)
+    with pytest.raises(lib.SlidersHipError, match="lib.batch_table"):
+        lib.call(lib.OP_WGRAD_BATCH, lib.BatchDesc(table=one, prefix=one, n=1, total=1, arg=4), 0)
+    # ln_fold items
+    assert lib.lnfold_item(one, one, one, one, one, one, 16, 320)[-1] == 16 | (320 << 32)
+    for rows, K in ((17, 320), (0, 320), (4, 324)):
+        with pytest.raises(lib.SlidersHipError, match="slh_lora_ln_fold"):
+            lib.lnfold_item(one, one, one, one, one, one, rows, K)
+
+
+def _lora_small(lm):
+    """the cases the CPU proof walks: everything but the rows-by-the-thousand skinny cases (their 16-lane order is walked on small M)"""
+    return [c for c in lm.CASES if not (c.kind == "skinny" and lm._sk_geo(c)[3] > 2000)]
+
+
+def test_lora_bounds_admit_the_standins():
+    """Every case of the matrix (but the skinny ones with more than 2000 rows): the stand-in - fp32 accumulation in the kernel's chunk
+    and lane order, the kernel's internal roundings - meets every bound.  The 16-lanes-per-row order of skinny, which only M > 16384
+    selects on the device, is walked on small M for every RMAX."""
+    from tests import lora_matrix as lm
+    from tests.util import STAT_LIMIT
+    worst = {}
+    for c in _lora_small(lm):
+        res = _lora_check(lm, c)
+        assert all(isinstance(r, tuple) for r in res.values()), (c.id, res)
+        assert all(w <= 1.0 and (b is None or abs(b) <= STAT_LIMIT) for w, b in res.values())
+        f = lm.form_of(c)
+        worst[f] = max(worst.get(f, 0.0), max(w for w, _ in res.values()))
+    for c in lm.CASES:
+        if c.kind == "skinny" and not c.kmajor and c.conv is None and lm._sk_geo(c)[3] <= 2000:
+            res = _lora_check(lm, c, lpr=16, rmax=4 if c.R <= 4 else 12 if c.R <= 12 else 16)
+            assert all(isinstance(r, tuple) for r in res.values()), (c.id, res)
+    for f, w in sorted(worst.items()):
+        print(f"[parity] lora stand-in {f}: worst |got - ref| / bound = {w:.3f}")
+
+
+def test_lora_bounds_reject_the_mutants():
+    """Each mutant of a stand-in leaves the bound of the case lora_matrix.mutant_cases() names for it - a case of the GPU list - and the
+    honest stand-in of that same case passes.  Two remarks on reach, also in docs/LORA_MATRIX.md: a weight gradient that masks its taps
+    as if the stride were 1 computes the same function at stride 2 on EVEN image sizes (no window leaves the image at the far edge),
+    so only the odd sizes catch it; conv_dgrad without its oy >= ho check computes the same function at stride 2 on ODD sizes (the
+    parity check already removes the row), so stride 1 and the even sizes catch it - and only with a sample behind the one that
+    over-reads."""
+    from tests import lora_matrix as lm
+    cases = lm.mutant_cases()
+    assert set(cases) == {f"{k}/{m}" for k, ms in lm.MUTANTS.items() for m in ms}
+    for key, c in cases.items():
+        kind, mutant = key.split("/")
+        assert c.kind == kind and c in lm.CASES
+        good, bad = _lora_check(lm, c), _lora_check(lm, c, mutant)
+        assert all(isinstance(r, tuple) for r in good.values()), (key, good)
+        caught = [r for r in bad.values() if isinstance(r, str)]
+        assert caught, f"{key} passed every check of {c.id}: {bad}"
+        print(f"[parity] lora mutant {key} ({c.id}): caught - {caught[0][:150]}")
+    # the equivalences claimed above
+    even = next(c for c in lm.CASES if c.kind == "wgrad" and len(c.probs) == 1 and c.probs[0]["conv"] == (2, 8, 6) and c.probs[0]["stride"] == 2 and c.probs[0]["xform"] == 0)
+    L = lm.wgrad_inputs(even, torch.device("cpu"), 1)
+    a, b = lm.wgrad_standin(even, L), lm.wgrad_standin(even, L, "taps_as_stride1")
+    assert all(torch.equal(a[n], b[n]) for n in a)
+    odd = next(c for c in lm.CASES if c.kind == "cdgrad" and c.stride == 2 and (c.hl, c.wl) == (7, 5) and c.B == 3)
+    L = lm.cdgrad_inputs(odd, torch.device("cpu"), 1)
+    assert torch.equal(lm.cdgrad_standin(odd, L)["gx"], lm.cdgrad_standin(odd, L, "no_oy_check")["gx"])
+
+
+def test_lora_matrix_is_not_hollow():
+    """Every form has a case; every edge the matrix claims is in the list, asked of the library where the library decides it."""
+    from tests import lora_matrix as lm
+    ids = [c.id for c in lm.CASES]
+    assert len(ids) == len(set(ids))
+    forms = {}
+    for c in lm.CASES:
+        forms.setdefault(lm.form_of(c), []).append(c)
+    assert set(forms) == set(lm.FORMS), set(forms) ^ set(lm.FORMS)
+    sk = [c for c in lm.CASES if c.kind == "skinny"]
+    rows = lambda c: lm._sk_geo(c)[3]
+    assert {c.R for c in sk if not c.conv and not c.kmajor} >= {1, 3, 4, 5, 8, 12, 13, 16}
+    assert {lm._sk_geo(c)[1] for c in sk if not c.conv} >= {8, 64, 320, 512, 520, 136} and {rows(c) for c in sk} >= {1, 5, 333, 16384, 16385, 16391}
+    # the switch between the two lane forms lies between the two neighbouring row counts of the list - wherever the library puts it
+    assert lm.form_of(next(c for c in sk if rows(c) == 16384)) == "skinny<4,64>" and lm.form_of(next(c for c in sk if rows(c) == 16385)) == "skinny<4,16>"
+    for f in lm.SKINNY_FORMS:                                  # every instantiation also with masked rows (R < RMAX)
+        assert any(c.R < int(f[7:].split(",")[0]) for c in forms[f]), f
+    assert any(c.conv and rows(c) > 16384 and c.ca == (8, 0) for c in sk) and any(c.kmajor and rows(c) > 16384 for c in sk)
+    assert {(c.stride, c.xform) for c in sk if c.conv} >= {(s, x) for s in (1, 2) for x in (0, 1, 2)}
+    assert {c.out_kind for c in sk if c.conv} == {0, 1} and any(c.ca[1] and c.conv for c in sk) and any(c.ca[1] and not c.conv for c in sk)
+    gv = [c for c in lm.CASES if c.kind == "gemv"]
+    for opt, vals in dict(nb=(1, 2, 7, 8), N=(1, 5, 37), K=(8, 320, 512, 520, 1280), in_act=(0, 1), out_f32=(0, 1), bias=(0, 1), addend=(0, 1), lora=(0, 1),
+                          tcol=(0, 1)).items():
+        assert {getattr(c, opt) for c in gv} >= set(vals), opt
+    assert any(c.pad for c in gv)
+    wgs = [c for c in lm.CASES if c.kind == "wgrad"]
+    for form in ("atomic", "slab", "batch", "batch_slab"):
+        sub = [c for c in wgs if c.form == form]
+        dense = [(c, p, g) for c in sub for p, g in zip(c.probs, lm.wgrad_geometry(c)) if not p["conv"]]
+        assert {p["M"] for _, p, _ in dense} >= {1, 7, 64, 65, 512, 513, 1024, 1025} or form != "atomic"
+        assert {p["M"] for _, p, _ in dense} >= {512, 513, 1024, 1025}, form
+        assert any(g[1] == 1 for _, _, g in dense) and any(g[1] > 1 for _, _, g in dense), form       # with and without an M split
+        assert any(p["vg"] for c in sub for p in c.probs) and any(p["c"][1] for c in sub for p in c.probs) and any(p["conv"] for c in sub for p in c.probs), form
+        assert {c.R for c in sub} == {4, 12} and {p["rmajor"] for c in sub for p in c.probs} == {0, 1}
+    k2 = {p["M"]: g[1] for c in wgs if c.form == "batch_slab" for p, g in zip(c.probs, lm.wgrad_geometry(c)) if not p["conv"]}
+    assert k2[512] != k2[513], "the kind-2 split edge moved away from 512 / 513: move the cases with it"
+    k1 = {p["M"]: g[1] for c in wgs if c.form == "slab" for p, g in zip(c.probs, lm.wgrad_geometry(c)) if not p["conv"] and p["c"] == (264, 0)}
+    assert k1[1024] != k1[1025], "the min_splits edge moved away from 1024 / 1025: move the cases with it"
+    assert {p["M"] for c in wgs for p in c.probs if not p["conv"]} >= {1, 7, 64, 65}
+    assert {p["c"][0] + p["c"][1] for c in wgs for p in c.probs} >= {8, 64, 264, 320, 192}
+    assert {(p["stride"], p["xform"], p["conv"][1:]) for c in wgs for p in c.probs if p["conv"]} >= {(s, x, hw) for s in (1, 2) for x in (0, 1, 2) for hw in ((7, 5), (8, 6))}
+    assert any(len(c.probs) > 1 and {bool(p["conv"]) for p in c.probs} == {True, False} and any(p["vg"] for p in c.probs) and any(p["c"][1] for p in c.probs) for c in wgs)
+    cd = [c for c in lm.CASES if c.kind == "cdgrad"]
+    assert {(c.stride, c.hl, c.wl) for c in cd} >= {(s, h, w) for s in (1, 2) for h, w in ((7, 5), (8, 6), (1, 1))}
+    assert {c.cin for c in cd} >= {8, 64, 72} and {c.B for c in cd} == {1, 3} and {c.acc for c in cd} == {0, 1} and {c.ldu for c in cd} == {4, 12}
+    assert any(c.ucol for c in cd) and any(c.pad for c in cd) and any((c.B * c.hl * c.wl * c.cin // 8) % 256 for c in cd)
+    assert {(c.C, c.ted) for c in lm.CASES if c.kind == "temb"} == {(320, 1280), (100, 104), (8, 8)}
+    ln = [c for c in lm.CASES if c.kind == "lnfold"]
+    assert {c.K for c in ln} >= {8, 320, 2048, 2056} and {len(c.rows) for c in ln} >= {1, 3} and {r for c in ln for r in c.rows} >= {1, 4, 12, 16}
+    ew = [c for c in lm.CASES if c.kind == "ew"]
+    for op in ("copy", "add", "add_inplace"):
+        assert {c.C for c in ew if c.op == op} >= {8, 72} and all((c.M * c.C // 8) % 256 for c in ew if c.op == op) and all(len(set(c.pads)) == 3 for c in ew if c.op == op)
+    assert {c.geo for c in ew if c.op == "upsample"} == {(2, 3, 5), (2, 6, 10)}
+    cs = [c for c in ew if c.op == "colsum"]
+    assert {c.geo[1] for c in cs} >= {1, 7, 512, 513, 1030} and {c.C for c in cs} == {8, 264} and {c.geo[0] for c in cs} == {1, 3}
+    assert {lm.has_atomics(c) for c in cs} == {True, False}
+    for key, c in lm.mutant_cases().items():
+        assert c in lm.CASES, key
