@@ -498,6 +498,27 @@ typedef struct slh_eps_absdiff_desc {
 } slh_eps_absdiff_desc;
 int slh_eps_absdiff(const slh_eps_absdiff_desc* d, slh_stream_t stream);
 
+/* One attention map per sample from a cross-attention layer's q and k and a weight per key (SliderEditor.word_map):
+ *   term[b][i] = coef * sum_{h < H} sum_{j < Tk} wt[b][j] * P[b0 + b, h, i, j],   P = softmax_j(scale * q_i . k_j) over the Tk keys,
+ *   out = term (accumulate 0) or out + term (accumulate 1).
+ * bf16 inputs, fp32 everywhere else; the softmax keeps a running maximum, no probability, logit or per-head share goes to global
+ * memory; the heads are added in ascending order by the one workgroup that owns the query row, with no atomics and no wait on
+ * another workgroup: bit-reproducible.  Several layers accumulate into one map by stream order.
+ * D % 8 == 0 and 8 <= D <= 192, 1 <= Tk <= 128, Tq >= 1, H >= 1, b0 + nb <= B, ldq and ldk multiples of 8 and >= H * D, q and k
+ * 16-byte aligned; anything else is refused before the launch. */
+typedef struct slh_xattn_map_desc {
+    const void* q;        /* [B][Tq][ldq] bf16, head h at columns [h*D, (h+1)*D) */
+    const void* k;        /* [B][Tk][ldk] bf16, same head layout (a column view of attn2_kv_all is the normal case: ldk >> H*D) */
+    const float* wt;      /* [nb][Tk] fp32 key weights, one row per collected sample */
+    float* out;           /* [nb][Tq] fp32 */
+    int32_t B, b0, nb;    /* samples b0 .. b0+nb-1 of the batch are collected (the text half of a CFG pair: b0 = nb = B/2) */
+    int32_t H, D, Tq, Tk, ldq, ldk;
+    float scale;          /* D^-0.5 */
+    float coef;           /* 1 / (H * layers of this level): the last launch of a level leaves the mean */
+    int32_t accumulate;   /* 0: out = term; 1: out = out + term */
+} slh_xattn_map_desc;
+int slh_xattn_map(const slh_xattn_map_desc* d, slh_stream_t stream);
+
 /* guidance loss (prompt_util.py:108-148): loss = mean((target - (neutral +- gs*(positive-uncond)))^2);
  * writes loss (fp32 scalar, atomically accumulated: zero it first) and d(loss)/d(target) (bf16). */
 typedef struct slh_loss_desc {
@@ -739,7 +760,8 @@ enum {
     SLH_OP_VAE_CONV_IN = 27, SLH_OP_VAE_MOMENTS = 28, SLH_OP_VAE_SAMPLE = 29, SLH_OP_VAE_POST_QUANT = 30, SLH_OP_LION = 31,
     SLH_OP_WGRAD_BATCH = 32, SLH_OP_TRANSPOSE_BATCH = 33, SLH_OP_GATHER16 = 34, SLH_OP_GN_FUSED = 35,
     SLH_OP_LORA_LN_FOLD = 36,     /* 37 was SLH_OP_PREFETCH (side-stream weight touch: measured slower, removed in round 5) */
-    SLH_OP_LORA_MERGE = 38, SLH_OP_DDPM_EDIT = 39, SLH_OP_DDPM_EDIT_BLEND = 40, SLH_OP_EPS_ABSDIFF = 41
+    SLH_OP_LORA_MERGE = 38, SLH_OP_DDPM_EDIT = 39, SLH_OP_DDPM_EDIT_BLEND = 40, SLH_OP_EPS_ABSDIFF = 41,
+    SLH_OP_XATTN_MAP = 42
 };
 /* SLH_OP_MEMSET: byte fill by a kernel of this library (not hipMemsetAsync: a captured memset node is a runtime blit whose
  * replays were observed to go wrong on the legacy default stream - see the executor's comment) */

@@ -81,6 +81,7 @@ extern "C" int slh_run_program(const void* program, int64_t nbytes, slh_stream_t
             case SLH_OP_DDPM_EDIT_BLEND:
                 rc = run_desc<slh_ddpm_edit_blend_desc>(p, sz, slh_ddpm_edit_blend, stream, "ddpm_edit_blend"); break;
             case SLH_OP_EPS_ABSDIFF: rc = run_desc<slh_eps_absdiff_desc>(p, sz, slh_eps_absdiff, stream, "eps_absdiff"); break;
+            case SLH_OP_XATTN_MAP: rc = run_desc<slh_xattn_map_desc>(p, sz, slh_xattn_map, stream, "xattn_map"); break;
             case SLH_OP_LOSS: rc = run_desc<slh_loss_desc>(p, sz, slh_guidance_loss, stream, "loss"); break;
             case SLH_OP_WGRAD: rc = run_desc<slh_wgrad_desc>(p, sz, slh_lora_wgrad, stream, "wgrad"); break;
             case SLH_OP_ADAMW: rc = run_desc<slh_adamw_desc>(p, sz, slh_adamw, stream, "adamw"); break;
@@ -196,7 +197,7 @@ extern "C" int slh_desc_sizes(int32_t* out, int32_t cap) {
         (int32_t)sizeof(slh_vae_conv_desc), (int32_t)sizeof(slh_vae_sample_desc), (int32_t)sizeof(slh_lion_desc),
         (int32_t)sizeof(slh_batch_desc),    (int32_t)sizeof(slh_gather16_desc), (int32_t)sizeof(slh_lora_lnfold_desc),
         (int32_t)sizeof(slh_lora_merge_desc), (int32_t)sizeof(slh_ddpm_edit_desc),
-        (int32_t)sizeof(slh_ddpm_edit_blend_desc), (int32_t)sizeof(slh_eps_absdiff_desc)};
+        (int32_t)sizeof(slh_ddpm_edit_blend_desc), (int32_t)sizeof(slh_eps_absdiff_desc), (int32_t)sizeof(slh_xattn_map_desc)};
     const int n = (int)(sizeof(sizes) / sizeof(sizes[0]));
     for (int i = 0; i < n && i < cap; ++i) out[i] = sizes[i];
     return n;

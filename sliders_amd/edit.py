@@ -25,7 +25,9 @@ bf16 rounding.
 Localised edits (mask=, --mask / --auto_mask): every step of an edit is blended against the latent the inversion itself had after
 that step (NoiseSpace.visited, slh_ddpm_edit_blend), so outside the mask the result is the reconstruction bit for bit.  The mask
 comes from a file (`load_mask`, `feather_mask`) or from where the slider changes the predicted noise on this image
-(`SliderEditor.footprint`, slh_eps_absdiff; `footprint_mask`).  `blend_reference` restates the blend as the other references do.
+(`SliderEditor.footprint`, slh_eps_absdiff; `footprint_mask`), or from where a word of the prompt lives in the UNet's cross-attention
+(`SliderEditor.word_map`, slh_xattn_map; `word_mask`, `word_token_indices`).  `blend_reference` restates the blend as the other
+references do.
 """
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ import argparse
 import math
 import os
 from dataclasses import dataclass, fields
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -296,7 +298,6 @@ def footprint_mean(A: torch.Tensor) -> torch.Tensor:
 def footprint_mask(F: torch.Tensor, quantile: float = 0.98, threshold: float = 0.5, dilate: int = 1, feather: float = 1.0) -> torch.Tensor:
     """A footprint [bs][h][w] (or [h][w]) -> a mask of its shape, DiffEdit's procedure: scale by the `quantile` value of each sample
     and clamp to [0, 1], binarise at `threshold`, dilate by `dilate` pixels, feather with a Gaussian of sigma `feather`."""
-    import torch.nn.functional as nnf
     if F.dim() not in (2, 3):
         raise ValueError(f"footprint_mask: F of shape {tuple(F.shape)}: expected [bs][h][w] or [h][w]")
     if not 0.0 < quantile <= 1.0 or not 0.0 < threshold <= 1.0 or int(dilate) != dilate or dilate < 0:
@@ -308,10 +309,103 @@ def footprint_mask(F: torch.Tensor, quantile: float = 0.98, threshold: float = 0
     if not bool((q > 0).all()):
         raise ValueError("footprint_mask: the slider has no footprint at this scale")
     m = (f / q[:, None, None]).clamp(0.0, 1.0)
-    m = (m >= threshold).to(torch.float32)
+    return _binary_tail(m >= threshold, dilate, feather).reshape(F.shape)
+
+
+def _binary_tail(inside: torch.Tensor, dilate: int, feather: float) -> torch.Tensor:
+    """What footprint_mask and word_mask end with: a boolean [n][h][w] -> fp32, grown by `dilate` pixels, feathered with sigma `feather`"""
+    import torch.nn.functional as nnf
+    m = inside.to(torch.float32)
     if dilate > 0:
         m = nnf.max_pool2d(m[:, None], 2 * int(dilate) + 1, stride=1, padding=int(dilate))[:, 0]
-    return feather_mask(m, feather).reshape(F.shape)
+    return feather_mask(m, feather)
+
+
+def word_mask(F: torch.Tensor, threshold: float = 0.3, dilate: int = 1, feather: float = 1.0) -> torch.Tensor:
+    """A word map [bs][h][w] (or [h][w]) -> a mask of its shape: F divided by its maximum over the pixels of each sample, binarised
+    at `threshold` (a pixel exactly at it is in), then footprint_mask's dilation and feathering.  0.3 is the default of
+    prompt-to-prompt's local blend; a default, not a tuned value.  A map whose maximum is not positive raises."""
+    if F.dim() not in (2, 3):
+        raise ValueError(f"word_mask: F of shape {tuple(F.shape)}: expected [bs][h][w] or [h][w]")
+    if not 0.0 < threshold <= 1.0 or int(dilate) != dilate or dilate < 0:
+        raise ValueError(f"word_mask: threshold = {threshold}, dilate = {dilate}: expected 0 < threshold <= 1, an integer dilate >= 0")
+    f = F.to(torch.float32).reshape((-1,) + tuple(F.shape[-2:]))
+    top = f.amax(dim=(1, 2))
+    if not bool((top > 0).all()):
+        raise ValueError("word_mask: the map is zero everywhere (no attention on the chosen tokens)")
+    return _binary_tail(f / top[:, None, None] >= threshold, dilate, feather).reshape(F.shape)
+
+
+def word_token_indices(prompt: str, word: str, tokenizer, ctx_len: int = 77) -> List[int]:
+    """Key positions (BOS = 0) of the sub-word tokens that spell every whitespace-separated word of `prompt` equal to `word`
+    (case-insensitive).  The prompt's tokens are decoded one by one and walked along its words: a word owns tokens until their pieces
+    are as long as it is.  tokenizer: encode(prompt) -> ids with BOS first and EOS last, decode([id]) -> the piece.  Raises if the
+    word is absent or one of its tokens falls past position ctx_len - 2 (the last key before the EOS of a truncated prompt)."""
+    words = prompt.split()
+    want = {n for n, w in enumerate(words) if w.lower() == word.lower()}
+    if not want:
+        raise ValueError(f"word_token_indices: {word!r} is not a word of {prompt!r}")
+    ids = list(tokenizer.encode(prompt))[1:-1]
+    out, at, have = [], 0, 0
+    for pos, tid in enumerate(ids, start=1):
+        if at >= len(words):
+            break
+        if at in want:
+            out.append(pos)
+        have += len(tokenizer.decode([tid]).strip().lstrip("#"))
+        if have >= len(words[at]):
+            at, have = at + 1, 0
+    if not out or at <= max(want):
+        raise ValueError(f"word_token_indices: the tokens of {prompt!r} end before {word!r} is spelled")
+    if max(out) > ctx_len - 2:
+        raise ValueError(f"word_token_indices: {word!r} reaches key position {max(out)}, past the last text key {ctx_len - 2} of a {ctx_len}-key context")
+    return out
+
+
+def key_weights(bs: int, ctx_len: int, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The [bs][ctx_len] fp32 key weights of a word map: 1 at `tokens` (key positions, BOS = 0), or `weights` as given"""
+    if (tokens is None) == (weights is None):
+        raise ValueError("word_map: give either tokens= or weights=")
+    if weights is not None:
+        w = torch.as_tensor(weights, dtype=torch.float32)
+        if tuple(w.shape) != (bs, ctx_len) or not bool(torch.isfinite(w).all()):
+            raise ValueError(f"word_map: weights of shape {tuple(w.shape)}: expected finite values of shape ({bs}, {ctx_len})")
+        return w.contiguous()
+    tokens = [int(t) for t in tokens]
+    if not tokens or min(tokens) < 0 or max(tokens) >= ctx_len:
+        raise ValueError(f"word_map: tokens = {tokens}: expected key positions in 0 .. {ctx_len - 1}")
+    w = torch.zeros(bs, ctx_len, dtype=torch.float32)
+    w[:, tokens] = 1.0
+    return w
+
+
+def level_mean(maps: Dict[int, torch.Tensor], h: int, w: int) -> torch.Tensor:
+    """{factor: [bs][(h / factor) (w / factor)]} -> [bs][h][w]: every level replicated factor x factor to the latent grid
+    (repeat_interleave: exact), then the mean over the levels in ascending factor"""
+    if not maps:
+        raise ValueError("level_mean: no level")
+    total = None
+    for f in sorted(maps):
+        if h % f or w % f:
+            raise ValueError(f"level_mean: a {h} x {w} grid is not divisible by {f}")
+        m = maps[f].to(torch.float32).reshape(-1, h // f, w // f).repeat_interleave(f, dim=1).repeat_interleave(f, dim=2)
+        total = m if total is None else total + m
+    return total / float(len(maps))
+
+
+def word_map_reference(collect: Callable[[torch.Tensor, int], Dict[int, torch.Tensor]], space: NoiseSpace, draws: int = 8) -> torch.Tensor:
+    """SliderEditor.word_map over a callable collect(x_bf16, t) -> {factor: [bs][T_level]}: the inversion's own latents at `draws` evenly
+    spaced steps of the whole grid, level_mean per draw, then the mean over the draws in grid order"""
+    if space.visited is None:
+        raise ValueError("word_map_reference: the NoiseSpace carries no visited latents")
+    idx = footprint_draws(space.timesteps, space.timesteps[0], draws, 0)
+    h, w = space.x_start.shape[-2:]
+    total = None
+    for i in idx:
+        x = space.x_start if i == 0 else space.visited[i - 1]
+        m = level_mean(collect(x.to(torch.bfloat16), space.timesteps[i]), h, w)
+        total = m if total is None else total + m
+    return total / float(len(idx))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -328,10 +422,11 @@ class SliderEditor(SliderSampler):
             raise ValueError(f"SliderEditor: scheduler {scheduler!r}: the DDPM noise space is defined on the DDIM grid")
         super().__init__(engine, store, decoder, prediction_type, "ddim", scheduler_seed, sliders)
 
-    def _load_inputs(self, bs: int, h: int, w: int, ctx, pooled, time_ids):
-        """the plan of this shape with its conditioning inputs written (the lines SliderSampler.sample_latents starts with)"""
+    def _load_inputs(self, bs: int, h: int, w: int, ctx, pooled, time_ids, attn_maps=None):
+        """the plan of this shape with its conditioning inputs written (the lines SliderSampler.sample_latents starts with);
+        attn_maps: the plan of the shape that also records attention maps (UNetEngine.plan)"""
         eng = self.eng
-        p = eng.plan(2 * bs, h, w, "on" if self.store is not None else "off")
+        p = eng.plan(2 * bs, h, w, "on" if self.store is not None else "off", attn_maps=attn_maps)
         io = p.io
         io["ctx"].tensor.copy_(ctx.to(torch.bfloat16))
         if eng.cfg.is_xl:
@@ -520,6 +615,47 @@ class SliderEditor(SliderSampler):
         return footprint_mean(A)
 
     @torch.no_grad()
+    def word_map(self, space: NoiseSpace, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None, draws: int = 8,
+                 max_factor: int = 4) -> torch.Tensor:
+        """Where words of the inversion's prompt live on this image: F [bs][h][w] fp32 = the mean over `draws` evenly spaced steps of
+        the whole grid of the mean over the collected levels of the UNet's cross-attention probabilities on the chosen keys
+        (slh_xattn_map behind every attn2 whose tokens are the latent grid divided by <= max_factor; heads and layers of a level
+        averaged, a level replicated to the latent grid).  tokens: key positions (BOS = 0, `word_token_indices`), or weights
+        [bs][ctx_len].  Inputs, conditioning and guidance are the footprint's - the inversion's own - and the slider is off
+        (multiplier 0, or the base weights with sliders=): len(draws) UNet passes of the maps plan, half of the footprint's, and
+        none of them depends on a slider.  The edit's own plans are not touched; the next chain starts with its full program."""
+        self._check_prediction(space)
+        self._check_conditioning(space, "word_map")
+        idx = footprint_draws(space.timesteps, space.timesteps[0], draws, 0)
+        eng, dev = self.eng, self.eng.device
+        visited = self.trajectory(space).visited.to(dev, torch.float32)
+        x_start = space.x_start.to(dev, torch.float32)
+        bs, _, h, w = x_start.shape
+        wt = key_weights(bs, eng.ctx_len, tokens, weights)
+        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids, attn_maps={"max_factor": int(max_factor)})
+        io = p.io
+        io["xattn_wt"].tensor.copy_(wt)
+        levels = {int(k.split(".")[1]): b for k, b in io.items() if k.startswith("xattn_map.")}
+        smp = io["sample"]
+        s = torch.cuda.current_stream().cuda_stream
+        total = torch.zeros((bs, h, w), dtype=torch.float32, device=dev)
+        try:
+            for n, i in enumerate(idx):
+                xb = (x_start if i == 0 else visited[i - 1]).to(torch.bfloat16)
+                smp.tensor[:bs].copy_(xb)
+                smp.tensor[bs:].copy_(xb)
+                if self.store is not None:
+                    eng.set_lora(True, 0.0)
+                io["t"].tensor.fill_(float(space.timesteps[i]))
+                self._edit_program(p, n, space.timesteps[i], 0.0, -1).run(s)
+                total += level_mean({f: b.tensor for f, b in levels.items()}, h, w)
+        finally:
+            self._restore()
+            if self.store is not None:
+                eng.set_lora(False)
+        return total / float(len(idx))
+
+    @torch.no_grad()
     def edit(self, space: NoiseSpace, **kw) -> torch.Tensor:
         """-> uint8 images [bs][H][W][3] (needs a VaeDecoder); the arguments of edit_latents, mask= included."""
         if self.decoder is None:
@@ -564,6 +700,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--auto_mask_draws", type=int, default=None, help="noise levels the footprint averages over (default 8)")
     p.add_argument("--auto_mask_threshold", type=float, default=None, help="binarisation threshold of the footprint (default 0.5)")
     p.add_argument("--auto_mask_dilate", type=int, default=None, help="latent pixels the binary footprint is grown by (default 1)")
+    p.add_argument("--mask_word", action="append", default=[], metavar="WORD",
+                   help="localise the edits to where this word of --prompt lives in the cross-attention; repeatable (needs the model's tokenizer)")
+    p.add_argument("--mask_tokens", default=None, metavar="I,J,...", help="the same from key positions of the prompt (BOS = 0)")
+    p.add_argument("--mask_word_threshold", type=float, default=None, help="binarisation threshold of the word map / its maximum (default 0.3)")
+    p.add_argument("--mask_word_draws", type=int, default=None, help="steps of the grid the word map averages over (default 8)")
+    p.add_argument("--save_attention", default=None, help="write the word map / its maximum here (8-bit PNG at latent resolution)")
     p.add_argument("--save_mask", default=None, help="write the latent-resolution mask here (8-bit PNG)")
     return p
 
@@ -587,14 +729,30 @@ def check_args(a):
         scales = [float(v) for v in a.scales.split(",")]
     except ValueError:
         raise SystemExit(f"--scales {a.scales!r}: expected comma-separated numbers")
-    if a.mask and a.auto_mask:
-        raise SystemExit("--mask reads a mask, --auto_mask derives one from the slider: give one of them")
+    word = bool(a.mask_word) or a.mask_tokens is not None
+    if sum([bool(a.mask), bool(a.auto_mask), bool(a.mask_word), a.mask_tokens is not None]) > 1:
+        raise SystemExit("--mask reads a mask, --auto_mask derives one from the slider, --mask_word / --mask_tokens from the prompt: give one of them")
+    if a.mask_word and a.synthetic:
+        raise SystemExit("--mask_word needs the model's tokenizer: with --synthetic give key positions (--mask_tokens)")
+    if a.mask_tokens is not None:
+        try:
+            a.mask_token_list = [int(v) for v in a.mask_tokens.split(",")]
+        except ValueError:
+            raise SystemExit(f"--mask_tokens {a.mask_tokens!r}: expected comma-separated key positions")
+        if not a.mask_token_list or min(a.mask_token_list) < 0 or max(a.mask_token_list) > 76:
+            raise SystemExit(f"--mask_tokens {a.mask_tokens!r}: expected key positions in 0 .. 76")
+    if not word and (a.mask_word_threshold is not None or a.mask_word_draws is not None or a.save_attention):
+        raise SystemExit("--mask_word_threshold / --mask_word_draws / --save_attention need --mask_word or --mask_tokens")
+    if a.mask_word_threshold is not None and not 0.0 < a.mask_word_threshold <= 1.0:
+        raise SystemExit(f"--mask_word_threshold {a.mask_word_threshold}: expected 0 < threshold <= 1")
+    if a.mask_word_draws is not None and a.mask_word_draws < 1:
+        raise SystemExit(f"--mask_word_draws {a.mask_word_draws}: expected at least 1")
     if a.mask and not os.path.isfile(a.mask):
         raise SystemExit(f"--mask {a.mask}: no such file")
-    if a.mask_invert and not a.mask:
-        raise SystemExit("--mask_invert needs --mask")
-    if not (a.mask or a.auto_mask) and (a.mask_feather is not None or a.save_mask):
-        raise SystemExit("--mask_feather / --save_mask need --mask or --auto_mask")
+    if a.mask_invert and not (a.mask or a.mask_word or a.mask_tokens is not None):
+        raise SystemExit("--mask_invert needs --mask (or --mask_word / --mask_tokens)")
+    if not (a.mask or a.auto_mask or word) and (a.mask_feather is not None or a.save_mask):
+        raise SystemExit("--mask_feather / --save_mask need --mask, --auto_mask, --mask_word or --mask_tokens")
     if a.mask_feather is not None and not 0.0 <= a.mask_feather < float("inf"):
         raise SystemExit(f"--mask_feather {a.mask_feather}: expected a finite sigma >= 0")
     given = [n for n in ("scale", "draws", "threshold", "dilate") if getattr(a, "auto_mask_" + n) is not None]
@@ -650,11 +808,13 @@ def main(argv=None):
         cond = []
         if xl:
             toks, encs = model_util.load_text_encoders_xl(a.model_path, dev, torch.bfloat16)
+            tokenizer = toks[0]
             for pr in prompts:
                 (e_u, p_u), (e_t, p_t) = (model_util.encode_prompts_xl(toks, encs, [s]) for s in ("", pr))
                 cond.append((torch.cat([e_u, e_t]), torch.cat([p_u, p_t])))
         else:
             tok, enc = model_util.load_text_encoder(a.model_path, dev, torch.bfloat16)
+            tokenizer = tok
             for pr in prompts:
                 cond.append((torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in ("", pr)]), None))
     dec = VaeDecoder(vae_sd, dev, VAE_SCALING[a.model])
@@ -698,6 +858,22 @@ def main(argv=None):
                                         feather=1.0 if a.mask_feather is None else a.mask_feather)
         except ValueError as e:
             raise SystemExit(f"--auto_mask: {e}")
+    elif a.mask_word or a.mask_tokens is not None:
+        try:
+            tokens = sorted({i for wd in a.mask_word for i in word_token_indices(a.prompt, wd, tokenizer, eng.ctx_len)}) if a.mask_word \
+                else a.mask_token_list
+            F = ed.word_map(space, tokens=tokens, draws=a.mask_word_draws or 8).cpu()
+            kw["mask"] = word_mask(F, threshold=0.3 if a.mask_word_threshold is None else a.mask_word_threshold,
+                                   feather=1.0 if a.mask_feather is None else a.mask_feather)
+        except ValueError as e:
+            raise SystemExit(f"--mask_word / --mask_tokens: {e}")
+        if a.mask_invert:
+            kw["mask"] = 1.0 - kw["mask"]
+        print(f"word map over key positions {tokens}: maximum {float(F.max()):.4f}")
+        if a.save_attention:
+            a8 = (F[0] / F[0].max() * 255.0).round().to(torch.uint8)
+            Image.fromarray(a8.numpy()).save(a.save_attention)
+            print(f"attention saved to {a.save_attention}")
     if a.save_mask:
         m8 = (kw["mask"].reshape(kw["mask"].shape[-2:]) * 255.0).round().to(torch.uint8)
         Image.fromarray(m8.cpu().numpy()).save(a.save_mask)

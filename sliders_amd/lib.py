@@ -79,6 +79,8 @@ DdpmEditBlendDesc = _struct("DdpmEditBlendDesc", _ptrs("eps", "eps_text", "x", "
                             + _ints("v_prediction"))
 EpsAbsdiffDesc = _struct("EpsAbsdiffDesc", _ptrs("eps_a", "eps_a_text", "eps_b", "eps_b_text", "out") + _ints("nb", "chw", "hw")
                          + [("guidance", c_f32)])
+XattnMapDesc = _struct("XattnMapDesc", _ptrs("q", "k", "wt", "out") + _ints("B", "b0", "nb", "H", "D", "Tq", "Tk", "ldq", "ldk")
+                       + [("scale", c_f32), ("coef", c_f32)] + _ints("accumulate"))
 LossDesc = _struct("LossDesc", _ptrs("target", "positive", "neutral", "uncond", "loss", "dtarget", "dtarget_pix")
                    + _ints("n") + [("guidance", c_f32)] + _ints("erase", "hw", "nch"))
 WgradDesc = _struct("WgradDesc", _ptrs("z0", "z1", "v", "out", "scale")
@@ -128,6 +130,8 @@ _SIZE_ORDER = [GemmDesc, SkinnyDesc, GemvDesc, GnDesc, GnBwdDesc, LnDesc, LnBwdD
                AttnBwdDesc, TembedDesc, ConvInDesc, EwDesc, CfgDdimDesc, LossDesc, WgradDesc, AdamwDesc, MemsetDesc,
                LoraCdgradDesc, TembLoraBwdDesc, SgemmDesc, Gn32Desc, Softmax32Desc, VaeConvDesc, VaeSampleDesc, LionDesc,
                BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc, DdpmEditDesc, DdpmEditBlendDesc, EpsAbsdiffDesc]
+# ... and the descriptors slh_desc_sizes() lists behind those (tests pin the tail of _SIZE_ORDER: new ones are appended here)
+_SIZE_ORDER_APPENDED = [XattnMapDesc]
 
 # opcodes (enum in sliders_hip.h)
 OP_GEMM, OP_SKINNY, OP_GEMV, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTN_FWD, OP_TRANSPOSE_HEADS = range(1, 9)
@@ -141,6 +145,7 @@ OP_LORA_LN_FOLD = 36
 OP_LORA_MERGE = 38
 OP_DDPM_EDIT = 39
 OP_DDPM_EDIT_BLEND, OP_EPS_ABSDIFF = 40, 41
+OP_XATTN_MAP = 42
 
 EW_COPY, EW_ADD, EW_GEGLU_FWD, EW_GEGLU_BWD, EW_UPSAMPLE_BWD, EW_COLSUM = range(6)
 
@@ -165,6 +170,7 @@ _ENTRY = {
     OP_LORA_LN_FOLD: ("slh_lora_ln_fold", LoraLnFoldDesc), OP_LORA_MERGE: ("slh_lora_merge", LoraMergeDesc),
     OP_DDPM_EDIT: ("slh_ddpm_edit_step", DdpmEditDesc),
     OP_DDPM_EDIT_BLEND: ("slh_ddpm_edit_blend", DdpmEditBlendDesc), OP_EPS_ABSDIFF: ("slh_eps_absdiff", EpsAbsdiffDesc),
+    OP_XATTN_MAP: ("slh_xattn_map", XattnMapDesc),
 }
 
 EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
@@ -209,9 +215,10 @@ def load() -> C.CDLL:
         fn.restype = c_i32
     sizes = (c_i32 * 64)()
     n = lib.slh_desc_sizes(sizes, 64)
-    if n != len(_SIZE_ORDER):
-        raise SlidersHipError(f"binding/library mismatch: library reports {n} descriptors, binding has {len(_SIZE_ORDER)}")
-    for i, d in enumerate(_SIZE_ORDER):
+    order = _SIZE_ORDER + _SIZE_ORDER_APPENDED
+    if n != len(order):
+        raise SlidersHipError(f"binding/library mismatch: library reports {n} descriptors, binding has {len(order)}")
+    for i, d in enumerate(order):
         if C.sizeof(d) != sizes[i]:
             raise SlidersHipError(f"binding/library mismatch: sizeof({d.__name__}) = {C.sizeof(d)} vs {sizes[i]}")
     _lib = lib

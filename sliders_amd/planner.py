@@ -187,6 +187,24 @@ def attach_weight_touch(ops: List[tuple], sw: Switches):
                 break
 
 
+@dataclass(frozen=True)
+class AttnMapSpec:
+    """Which cross-attention layers of a no-grad plan record a per-token attention map (slh_xattn_map): every attn2 whose query grid
+    is the latent grid divided by a factor <= max_factor.  4 gives SDXL both of its attention levels, SD-1.x its 1x / 2x / 4x levels
+    without the 8x level and the mid block."""
+    max_factor: int = 4
+
+    @classmethod
+    def of(cls, spec) -> Optional["AttnMapSpec"]:
+        """None, an AttnMapSpec, a dict of its fields or a bare max_factor"""
+        if spec is None or isinstance(spec, cls):
+            return spec
+        s = cls(**spec) if isinstance(spec, dict) else cls(int(spec))
+        if int(s.max_factor) != s.max_factor or s.max_factor < 1:
+            raise ValueError(f"attn_maps: max_factor = {s.max_factor}: expected an integer >= 1")
+        return s
+
+
 def _program(ops) -> "lib.Program":
     prog = lib.Program()
     for o, d, nm in ops:
@@ -203,9 +221,13 @@ def _src_parts(x: Src):
 class UNetPlan:
     def __init__(self, cfg: UNetConfig, weights: WeightStore, arena: Arena, zarena: Arena, B: int, H: int, W: int,
                  ctx_len: int = 77, lora: Optional[LoraStore] = None, mode: str = "off",
-                 lora_scale_ptr: int = 0, io: Optional[dict] = None):
+                 lora_scale_ptr: int = 0, io: Optional[dict] = None, attn_maps=None):
         assert mode in ("off", "on", "train")
         assert mode == "off" or lora is not None
+        self.attn_maps = AttnMapSpec.of(attn_maps)
+        if self.attn_maps is not None and mode == "train":
+            raise ValueError("attn_maps: attention maps are collected in the no-grad plans (mode 'off' / 'on'), not in 'train'")
+        self.map_ops: Dict[int, list] = {}        # factor -> the slh_xattn_map descriptors of that level, in plan order
         self.cfg, self.w, self.arena, self.zarena = cfg, weights, arena, zarena
         self.B, self.H, self.W, self.ctx_len = B, H, W, ctx_len
         self.lora = lora if mode != "off" else None
@@ -220,6 +242,7 @@ class UNetPlan:
         self.zmark = zarena.mark()
         self._build_io(io)
         self._forward()
+        self._finish_maps()
         self.zend = zarena.mark()
         # zero the fp32 accumulators (GroupNorm statistics ...) used by this program first
         head = []
@@ -250,10 +273,11 @@ class UNetPlan:
     # ------------------------------------------------------------------------------------------------
     def _build_io(self, io):
         cfg, B = self.cfg, self.B
+        a = self.arena
         if io is not None:
             self.io = io
+            self._build_map_io()
             return
-        a = self.arena
         self.io = {
             "sample": a.alloc((B, cfg.in_channels, self.H, self.W), torch.bfloat16, "in.sample"),
             "t": a.alloc((B, 1), torch.float32, "in.t"),
@@ -263,6 +287,52 @@ class UNetPlan:
         if cfg.is_xl:
             self.io["time_ids"] = a.alloc((B, 6), torch.float32, "in.time_ids")
             self.io["add_in"] = a.alloc((B, cfg.projection_class_embeddings_input_dim), torch.bfloat16, "in.add_in")
+        self._build_map_io()
+
+    def _map_factor(self, h: Act) -> Optional[int]:
+        """The level of a transformer block's tokens (latent grid / query grid) where this plan collects its map, else None"""
+        if self.attn_maps is None or self.H % h.H or self.W % h.W or self.H // h.H != self.W // h.W:
+            return None
+        f = self.H // h.H
+        return f if f <= self.attn_maps.max_factor else None
+
+    def _build_map_io(self):
+        """xattn_wt [B/2][ctx_len] and one xattn_map.<factor> [B/2][T_level] per collected level (fp32): the key weights the caller
+        writes and the maps it reads, for the text half of the CFG pair"""
+        if self.attn_maps is None:
+            return
+        cfg, B = self.cfg, self.B
+        if B % 2:
+            raise ValueError(f"attn_maps: B = {B}: the maps are those of the text half of a CFG pair (an even batch)")
+        # the levels with a transformer: the attention down blocks (the up blocks mirror them) and the mid block, at the last level
+        levels = {i for i, t in enumerate(cfg.down_block_types) if t != "DownBlock2D"} | {len(cfg.down_block_types) - 1}
+        levels = sorted(i for i in levels if 2 ** i <= self.attn_maps.max_factor)
+        if not levels:
+            raise ValueError(f"attn_maps: no cross-attention level of this model has a factor <= {self.attn_maps.max_factor}")
+        fmax = 2 ** max(levels)
+        if self.H % fmax or self.W % fmax:
+            raise ValueError(f"attn_maps: a {self.H} x {self.W} latent is not divisible by {fmax}, the coarsest collected level")
+        self.io.setdefault("xattn_wt", self.arena.alloc((B // 2, self.ctx_len), torch.float32, "in.xattn_wt"))
+        for i in levels:
+            f = 2 ** i
+            self.io.setdefault(f"xattn_map.{f}", self.arena.alloc((B // 2, (self.H // f) * (self.W // f)), torch.float32, f"out.xattn_map.{f}"))
+
+    def _record_map(self, q: Act, k: Act, heads: int, factor: int, name: str):
+        """One slh_xattn_map behind a collected cross-attention, while its q and k are live; coef and accumulate are set once the
+        level's layers are counted (_finish_maps)"""
+        B = self.B
+        d = lib.XattnMapDesc(q=q.ptr, k=k.ptr, wt=self.io["xattn_wt"].ptr, out=self.io[f"xattn_map.{factor}"].ptr, B=B, b0=B // 2,
+                             nb=B // 2, H=heads, D=q.C // heads, Tq=q.HW, Tk=self.ctx_len, ldq=q.ld, ldk=k.ld,
+                             scale=(q.C // heads) ** -0.5)
+        self.map_ops.setdefault(factor, []).append(d)
+        self.add(lib.OP_XATTN_MAP, d, name)
+
+    def _finish_maps(self):
+        """The first map op of a level writes, the others add; coef = 1 / (heads * layers of the level): the last one leaves the mean"""
+        for descs in self.map_ops.values():
+            for n, d in enumerate(descs):
+                d.accumulate = 1 if n else 0
+                d.coef = 1.0 / (d.H * len(descs))
 
     def act(self, B, H, W, C, name="") -> Act:
         buf = self.arena.alloc((B * H * W, C), torch.bfloat16, name)
@@ -650,10 +720,11 @@ class UNetPlan:
         # no-grad passes, head dim 64, text keys, no adapter on to_q: the attention runs in the epilogue of the query projection
         xa = None
         D2 = C // heads
+        map_factor = self._map_factor(h)          # a collected layer keeps q2 in memory: its attention is a launch of its own
         # (the gate restates slh_gemm's own checks for xa_*: head dim 64 with whole 64-column heads, 65..96 keys - two 64-key V^T
         # tiles are always staged, so xa_ldvt = roundup(ctx_len, 64) must reach 128 - and whole 128-row query tiles per sample)
         if not self.train and vt_pre is not None and D2 == 64 and C % 64 == 0 and 64 < self.ctx_len <= 96 and h.HW % 128 == 0 and \
-                self._lora_group([a2 + ".to_q"]) is None and not self.sw.no_fused_xattn:
+                self._lora_group([a2 + ".to_q"]) is None and not self.sw.no_fused_xattn and map_factor is None:
             xa = dict(k=k2, vt_ptr=vt_pre[0], vt_heads=vt_pre[1], Tk=self.ctx_len, Tq=h.HW, scale=D2 ** -0.5,
                       ldvt=(self.ctx_len + 63) // 64 * 64)
         q2 = self.ln_gemm(h1, path + ".norm2", a2 + ".q", C, bias=False, lora_paths=[a2 + ".to_q"], xattn=xa)
@@ -661,6 +732,8 @@ class UNetPlan:
             o2 = q2
         else:
             o2 = self.attention(q2, k2, v2, self.ctx_len, heads, a2 + ".sdpa", vt_pre=vt_pre)
+            if map_factor is not None:
+                self._record_map(q2, k2, heads, map_factor, a2 + ".map")
         h2 = self.gemm(o2, a2 + ".out", C, a2 + ".out", residual=h1, lora_paths=[a2 + ".to_out.0"], ln_stats=True)
         if self.train and (self._lora_group([path + ".ff.net.0.proj"]) is not None or
                            self.sw.train_unfused_geglu):

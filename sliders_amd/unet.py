@@ -18,7 +18,7 @@ from . import lib
 from .arena import Arena
 from .config import UNetConfig
 from .lora_store import LoraStore
-from .planner import BackwardPlan, UNetPlan
+from .planner import AttnMapSpec, BackwardPlan, UNetPlan
 from .weights import WeightStore
 
 
@@ -98,13 +98,13 @@ class UNetEngine:
             self.lora_scale.fill_(self.lora_scale_host)
 
     # ---- planning ---------------------------------------------------------------------------------
-    def _virtual_size(self, B, H, W, mode) -> int:
+    def _virtual_size(self, B, H, W, mode, attn_maps=None) -> int:
         va = Arena(1 << 50, None, "virtual")
         vz = Arena(1 << 40, None, "virtualz")
         # (placeholder pointers where the real plan has some: slh_gemm_tile_ok refuses an adapter without its scale, and the dry run
         # must choose the tiles - and split-K workspaces - the real plan will)
         p = UNetPlan(self.cfg, _VirtualWeights(self.weights), va, vz, B, H, W, self.ctx_len,
-                     _VirtualLora(self.lora) if mode != "off" else None, mode, 0x4000)
+                     _VirtualLora(self.lora) if mode != "off" else None, mode, 0x4000, attn_maps=attn_maps)
         if mode == "train":
             b0, nb = self._grad_samples(B)
             BackwardPlan(p, b0, nb, 0x4000)
@@ -132,8 +132,13 @@ class UNetEngine:
             self.arena = None
             self.arena = Arena(max(need, self._arena_bytes or 0) + (1 << 20), self.device, "activations")
 
-    def plan(self, B: int, H: int, W: int, mode: str) -> UNetPlan:
-        key = (B, H, W, mode)
+    def plan(self, B: int, H: int, W: int, mode: str, attn_maps=None) -> UNetPlan:
+        """attn_maps (planner.AttnMapSpec, a dict of its fields, or None): a no-grad plan that also records per-token cross-attention
+        maps (io["xattn_wt"], io["xattn_map.<factor>"]); a plan of its own next to the ordinary one of the shape, in the same arena"""
+        spec = AttnMapSpec.of(attn_maps)
+        if spec is not None and mode == "train":
+            raise ValueError("attn_maps: attention maps are collected in the no-grad plans (mode 'off' / 'on'), not in 'train'")
+        key = (B, H, W, mode) if spec is None else (B, H, W, mode, spec)
         p = self._plans.get(key)
         if p is not None:
             return p
@@ -144,7 +149,7 @@ class UNetEngine:
         # size the shared arena for the requested plan and, once adapters are attached, for the training plan
         # of the same shape (so 'on' -> 'train' does not trigger a regrow that invalidates cached plans)
         modes = {mode} | ({"train"} if (self.lora is not None and mode != "off") else set())
-        need = max(self._virtual_size(B, H, W, m) for m in modes)
+        need = max(self._virtual_size(B, H, W, m, spec if m == mode else None) for m in modes)
         off = mode == "off"
         self._ensure_arena(need, off)
         if mode == "train":
@@ -154,7 +159,7 @@ class UNetEngine:
         arena = self.arena_off if off else self.arena
         arena.reset(0)
         p = UNetPlan(self.cfg, self.weights, arena, self.zarena, B, H, W, self.ctx_len,
-                     self.lora if mode != "off" else None, mode, self.lora_scale.data_ptr())
+                     self.lora if mode != "off" else None, mode, self.lora_scale.data_ptr(), attn_maps=spec)
         if mode == "train":
             b0, nb = self._grad_samples(B)
             p.backward = BackwardPlan(p, b0, nb, self.one.data_ptr())
