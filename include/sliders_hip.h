@@ -32,7 +32,7 @@ extern "C" {
 
 typedef void* slh_stream_t; /* hipStream_t */
 
-int slh_version(void);
+int slh_version(void);   /* 2: slh_op_info (keyed by opcode) replaced the positional list of descriptor sizes; SLH_OP_MEMSET has an entry point, slh_memset */
 const char* slh_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -766,6 +766,7 @@ enum {
 /* SLH_OP_MEMSET: byte fill by a kernel of this library (not hipMemsetAsync: a captured memset node is a runtime blit whose
  * replays were observed to go wrong on the legacy default stream - see the executor's comment) */
 typedef struct slh_memset_desc { void* ptr; int64_t nbytes; int32_t value; int32_t pad; } slh_memset_desc;
+int slh_memset(const slh_memset_desc* d, slh_stream_t stream);   /* nbytes <= 0: nothing is launched, 0 */
 int slh_run_program(const void* program, int64_t nbytes, slh_stream_t stream);
 /* hipGraph replay of a command buffer: capture records the launches slh_run_program would issue (on a private stream;
  * nothing executes), launch re-submits them as one graph.  The buffer must be static between replays (descriptors are baked
@@ -775,8 +776,10 @@ int slh_run_program(const void* program, int64_t nbytes, slh_stream_t stream);
 int slh_graph_capture(const void* program, int64_t nbytes, void** out_graph);
 int slh_graph_launch(void* graph, slh_stream_t stream);
 int slh_graph_destroy(void* graph);
-/* sizeof() of every descriptor, in declaration order above, for binding self-checks */
-int slh_desc_sizes(int32_t* out, int32_t cap);
+/* The executor's op table, one row per SLH_OP_*, for binding self-checks: row `index` gives the opcode, the name of its entry point
+ * and the sizeof() of the descriptor that entry point takes (any out pointer may be NULL).  Returns the number of rows; an index
+ * outside [0, rows) writes nothing.  The order of the rows carries no meaning: a binding keys its check by opcode. */
+int slh_op_info(int index, int32_t* opcode, const char** entry, int32_t* desc_size);
 
 #ifdef __cplusplus
 }

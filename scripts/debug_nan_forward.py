@@ -53,11 +53,7 @@ for attempt in range(N):
                     print("   vt_all non-finite count", idx.shape[0], "max |v|", float(t.abs().max()), flush=True)
                     s_ = torch.cuda.current_stream().cuda_stream
                     for j in range(0, i + 1):
-                        o2, d2 = p.prog.ops[j]
-                        if o2 in lib._ENTRY:
-                            lib.call(o2, d2, s_)
-                        else:
-                            one = lib.Program(); one.add(o2, d2); one.run(s_)
+                        lib.call(*p.prog.ops[j], s_)
                     torch.cuda.synchronize()
                     t2 = view(d.dst, d.B * d.H * Dp, d.ldt, d.ldt).float()
                     print("   after re-running ops 0..%d: non-finite in vt_all: %d" % (i, int((~torch.isfinite(t2)).sum())), flush=True)

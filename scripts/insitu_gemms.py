@@ -37,20 +37,13 @@ stream = torch.cuda.current_stream()
 s = stream.cuda_stream
 
 
-def launch(op, d):
-    if op in lib._ENTRY:
-        lib.call(op, d, s)
-    else:
-        one = lib.Program(); one.add(op, d); one.run(s)
-
-
 for _ in range(2):
     p.prog.run(s)
 torch.cuda.synchronize()
 recs = []
 for (op, d), nm in zip(p.prog.ops, p.prog.op_names):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream); launch(op, d); e1.record(stream)
+    e0.record(stream); lib.call(op, d, s); e1.record(stream)
     recs.append((op, d, nm, e0, e1))
 torch.cuda.synchronize()
 agg = defaultdict(lambda: [0, 0.0, 0.0, ""])
@@ -58,7 +51,7 @@ other = defaultdict(lambda: [0, 0.0])
 for op, d, nm, e0, e1 in recs:
     us = e0.elapsed_time(e1) * 1e3
     if op != lib.OP_GEMM:
-        k = lib._ENTRY[op][0] if op in lib._ENTRY else "memset"
+        k = lib._ENTRY[op][0]
         if args.attn and op == lib.OP_ATTN_FWD:
             k = f"slh_attn_fwd B{d.B} H{d.H} Tq{d.Tq} Tk{d.Tk} D{d.D}"
         other[k][0] += 1; other[k][1] += us

@@ -64,16 +64,13 @@ def breakdown(prog, title):
     for op, d in prog.ops:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
-        if op in lib._ENTRY:
-            lib.call(op, d, s)
-        else:
-            one = lib.Program(); one.add(op, d); one.run(s)
+        lib.call(op, d, s)
         e1.record(stream)
         recs.append((op, e0, e1))
     torch.cuda.synchronize()
     agg = defaultdict(lambda: [0, 0.0])
     for op, e0, e1 in recs:
-        k = lib._ENTRY[op][0] if op in lib._ENTRY else "memset"
+        k = lib._ENTRY[op][0]
         agg[k][0] += 1
         agg[k][1] += e0.elapsed_time(e1)
     print(f"-- {title}: {sum(v[1] for v in agg.values()):.2f} ms summed over {len(recs)} ops")

@@ -51,15 +51,6 @@ def inputs(B):
     return x, ctx, kw
 
 
-def launch(op, d):
-    if op in lib._ENTRY:
-        lib.call(op, d, s)
-    else:
-        one = lib.Program()
-        one.add(op, d)
-        one.run(s)
-
-
 def valid(d, tile):
     f = tile_fields(tile)
     ni, wm = f.ni, f.family
@@ -120,11 +111,11 @@ for pname, prog in programs:
                 if op == lib.OP_GEMM:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
-                    launch(op, d)
+                    lib.call(op, d, s)
                     e1.record(stream)
                     recs.append((d, e0, e1))
                 else:
-                    launch(op, d)
+                    lib.call(op, d, s)
             torch.cuda.synchronize()
             if rep == 0:
                 continue                        # first replay with a new tile set: warm-up

@@ -14,7 +14,7 @@ void slh_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* slh_last_error(void) { return g_err; }
-extern "C" int slh_version(void) { return 1; }
+extern "C" int slh_version(void) { return 2; }
 
 // ---- launch query (slh_gemm_kernel_name, slh_gemm_launch_query) ----------------------------------------------------------------
 // While a sink is set on this thread the launchers (common.h: slh_launch<Kern>) record the instantiation they WOULD launch instead of

@@ -23,35 +23,120 @@ __global__ void fill_kernel(unsigned char* p, unsigned v4, long n, int head) {
         for (long j = head + ((n - head) & ~15L); j < n; ++j) p[j] = (unsigned char)v4;
     }
 }
-inline int fill_bytes(void* ptr, int value, long n, hipStream_t s) {
+}  // namespace
+
+extern "C" int slh_memset(const slh_memset_desc* d, slh_stream_t stream) {
+    if (!d) { slh_set_error("slh_memset: null descriptor"); return -3; }
+    const long n = (long)d->nbytes;
     if (n <= 0) return 0;
-    long head = (long)((16 - ((uintptr_t)ptr & 15)) & 15);
+    if (!d->ptr) { slh_set_error("slh_memset: null ptr with nbytes = %ld", n); return -3; }
+    long head = (long)((16 - ((uintptr_t)d->ptr & 15)) & 15);
     if (head > n) head = n;
-    const unsigned b = (unsigned)value & 0xffu, v4 = b * 0x01010101u;
+    const unsigned b = (unsigned)d->value & 0xffu, v4 = b * 0x01010101u;
     const long threads = (n - head) / 16 + 1;
-    fill_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>((unsigned char*)ptr, v4, n, (int)head);
-    if (hipGetLastError() != hipSuccess) { slh_set_error("slh_run_program: memset launch failed"); return -2; }
+    hipStream_t s = (hipStream_t)stream;
+    fill_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>((unsigned char*)d->ptr, v4, n, (int)head);
+    if (hipGetLastError() != hipSuccess) { slh_set_error("slh_memset: launch failed"); return -2; }
     return 0;
 }
 
-template <typename T>
-inline int run_desc(const unsigned char* p, int32_t nbytes, int (*fn)(const T*, slh_stream_t), slh_stream_t s,
-                    const char* name) {
+namespace {
+// The op table: THE association of an opcode with its entry point and its descriptor.  The executor dispatches through it and
+// slh_op_info reports it, so a binding checks itself against the rows the executor runs.  A new op is one row here (plus its
+// enumerator, struct and prototype in sliders_hip.h).
+struct OpRow {
+    int32_t opcode;
+    const char* entry;
+    int32_t desc_size;
+    int (*run)(const unsigned char* rec, int32_t nbytes, slh_stream_t s, const char* entry);
+};
+
+template <typename T, int (*Fn)(const T*, slh_stream_t)>
+int run_desc(const unsigned char* rec, int32_t nbytes, slh_stream_t s, const char* entry) {
     if (nbytes != (int32_t)sizeof(T)) {
-        slh_set_error("slh_run_program: %s descriptor is %d bytes, library expects %d", name, nbytes, (int)sizeof(T));
+        slh_set_error("slh_run_program: %s descriptor is %d bytes, library expects %d", entry, nbytes, (int)sizeof(T));
         return -3;
     }
     T d;
-    memcpy(&d, p, sizeof(T));
-    return fn(&d, s);
+    memcpy(&d, rec, sizeof(T));
+    return Fn(&d, s);
 }
+
+#define SLH_OP_ROW(op, fn, desc) {op, #fn, (int32_t)sizeof(desc), run_desc<desc, fn>}
+constexpr OpRow kOps[] = {
+    SLH_OP_ROW(SLH_OP_GEMM, slh_gemm, slh_gemm_desc),
+    SLH_OP_ROW(SLH_OP_SKINNY, slh_skinny, slh_skinny_desc),
+    SLH_OP_ROW(SLH_OP_GEMV, slh_gemv, slh_gemv_desc),
+    SLH_OP_ROW(SLH_OP_GN_STATS, slh_gn_stats, slh_gn_desc),
+    SLH_OP_ROW(SLH_OP_GN_APPLY, slh_gn_apply, slh_gn_desc),
+    SLH_OP_ROW(SLH_OP_LAYERNORM, slh_layernorm, slh_ln_desc),
+    SLH_OP_ROW(SLH_OP_ATTN_FWD, slh_attn_fwd, slh_attn_desc),
+    SLH_OP_ROW(SLH_OP_TRANSPOSE_HEADS, slh_transpose_heads, slh_transpose_desc),
+    SLH_OP_ROW(SLH_OP_TEMBED, slh_timestep_embed, slh_tembed_desc),
+    SLH_OP_ROW(SLH_OP_CONV_IN, slh_conv_in, slh_convin_desc),
+    SLH_OP_ROW(SLH_OP_ELEMENTWISE, slh_elementwise, slh_ew_desc),
+    SLH_OP_ROW(SLH_OP_CFG_DDIM, slh_cfg_ddim, slh_cfg_ddim_desc),
+    SLH_OP_ROW(SLH_OP_LOSS, slh_guidance_loss, slh_loss_desc),
+    SLH_OP_ROW(SLH_OP_WGRAD, slh_lora_wgrad, slh_wgrad_desc),
+    SLH_OP_ROW(SLH_OP_ADAMW, slh_adamw, slh_adamw_desc),
+    SLH_OP_ROW(SLH_OP_GN_BWD_STATS, slh_gn_bwd_stats, slh_gn_bwd_desc),
+    SLH_OP_ROW(SLH_OP_GN_BWD_APPLY, slh_gn_bwd_apply, slh_gn_bwd_desc),
+    SLH_OP_ROW(SLH_OP_LAYERNORM_BWD, slh_layernorm_bwd, slh_ln_bwd_desc),
+    SLH_OP_ROW(SLH_OP_ATTN_BWD, slh_attn_bwd, slh_attn_bwd_desc),
+    SLH_OP_ROW(SLH_OP_MEMSET, slh_memset, slh_memset_desc),
+    SLH_OP_ROW(SLH_OP_LORA_CONV_DGRAD, slh_lora_conv_dgrad, slh_lora_cdgrad_desc),
+    SLH_OP_ROW(SLH_OP_TEMB_LORA_BWD, slh_temb_lora_bwd, slh_temb_lora_bwd_desc),
+    SLH_OP_ROW(SLH_OP_SGEMM, slh_sgemm, slh_sgemm_desc),
+    SLH_OP_ROW(SLH_OP_GN32_STATS, slh_gn32_stats, slh_gn32_desc),
+    SLH_OP_ROW(SLH_OP_GN32_APPLY, slh_gn32_apply, slh_gn32_desc),
+    SLH_OP_ROW(SLH_OP_SOFTMAX32, slh_softmax32, slh_softmax32_desc),
+    SLH_OP_ROW(SLH_OP_VAE_CONV_IN, slh_vae_conv_in, slh_vae_conv_desc),
+    SLH_OP_ROW(SLH_OP_VAE_MOMENTS, slh_vae_moments, slh_vae_conv_desc),
+    SLH_OP_ROW(SLH_OP_VAE_SAMPLE, slh_vae_sample, slh_vae_sample_desc),
+    SLH_OP_ROW(SLH_OP_VAE_POST_QUANT, slh_vae_post_quant, slh_vae_conv_desc),
+    SLH_OP_ROW(SLH_OP_LION, slh_lion, slh_lion_desc),
+    SLH_OP_ROW(SLH_OP_WGRAD_BATCH, slh_lora_wgrad_batch, slh_batch_desc),
+    SLH_OP_ROW(SLH_OP_TRANSPOSE_BATCH, slh_transpose_heads_batch, slh_batch_desc),
+    SLH_OP_ROW(SLH_OP_GATHER16, slh_gather16, slh_gather16_desc),
+    SLH_OP_ROW(SLH_OP_GN_FUSED, slh_gn_fused, slh_gn_desc),
+    SLH_OP_ROW(SLH_OP_LORA_LN_FOLD, slh_lora_ln_fold, slh_lora_lnfold_desc),
+    SLH_OP_ROW(SLH_OP_LORA_MERGE, slh_lora_merge, slh_lora_merge_desc),
+    SLH_OP_ROW(SLH_OP_DDPM_EDIT, slh_ddpm_edit_step, slh_ddpm_edit_desc),
+    SLH_OP_ROW(SLH_OP_DDPM_EDIT_BLEND, slh_ddpm_edit_blend, slh_ddpm_edit_blend_desc),
+    SLH_OP_ROW(SLH_OP_EPS_ABSDIFF, slh_eps_absdiff, slh_eps_absdiff_desc),
+    SLH_OP_ROW(SLH_OP_XATTN_MAP, slh_xattn_map, slh_xattn_map_desc),
+};
+#undef SLH_OP_ROW
+constexpr int kNumOps = (int)(sizeof(kOps) / sizeof(kOps[0]));
+
+// opcode -> row, filled once: the executor pays one indexed load per record
+constexpr int kOpSlots = 64;
+constexpr bool opcodes_fit() {
+    for (const OpRow& r : kOps)
+        if (r.opcode <= 0 || r.opcode >= kOpSlots) return false;
+    return true;
+}
+static_assert(opcodes_fit(), "an SLH_OP_* value outside (0, kOpSlots): widen kOpSlots");
+struct OpIndex {
+    const OpRow* at[kOpSlots] = {};
+    OpIndex() { for (const OpRow& r : kOps) at[r.opcode] = &r; }
+};
 }  // namespace
 
+extern "C" int slh_op_info(int index, int32_t* opcode, const char** entry, int32_t* desc_size) {
+    if (index >= 0 && index < kNumOps) {
+        if (opcode) *opcode = kOps[index].opcode;
+        if (entry) *entry = kOps[index].entry;
+        if (desc_size) *desc_size = kOps[index].desc_size;
+    }
+    return kNumOps;
+}
+
 extern "C" int slh_run_program(const void* program, int64_t nbytes, slh_stream_t stream) {
+    static const OpIndex index;
     const unsigned char* p = (const unsigned char*)program;
     const unsigned char* end = p + nbytes;
     int idx = 0;
-    int rc_all = 0;
     while (p < end) {
         if (end - p < 8) { slh_set_error("slh_run_program: truncated record header at op %d", idx); return -3; }
         int32_t hdr[2];
@@ -59,71 +144,14 @@ extern "C" int slh_run_program(const void* program, int64_t nbytes, slh_stream_t
         p += 8;
         const int32_t op = hdr[0], sz = hdr[1];
         if (sz < 0 || end - p < sz) { slh_set_error("slh_run_program: truncated record at op %d", idx); return -3; }
-        int rc = 0;
-        switch (op) {
-            case SLH_OP_GEMM: rc = run_desc<slh_gemm_desc>(p, sz, slh_gemm, stream, "gemm"); break;
-            case SLH_OP_SKINNY: rc = run_desc<slh_skinny_desc>(p, sz, slh_skinny, stream, "skinny"); break;
-            case SLH_OP_GEMV: rc = run_desc<slh_gemv_desc>(p, sz, slh_gemv, stream, "gemv"); break;
-            case SLH_OP_GN_STATS: rc = run_desc<slh_gn_desc>(p, sz, slh_gn_stats, stream, "gn_stats"); break;
-            case SLH_OP_GN_APPLY: rc = run_desc<slh_gn_desc>(p, sz, slh_gn_apply, stream, "gn_apply"); break;
-            case SLH_OP_GN_FUSED: rc = run_desc<slh_gn_desc>(p, sz, slh_gn_fused, stream, "gn_fused"); break;
-            case SLH_OP_LORA_LN_FOLD: rc = run_desc<slh_lora_lnfold_desc>(p, sz, slh_lora_ln_fold, stream, "lora_ln_fold"); break;
-            case SLH_OP_LORA_MERGE: rc = run_desc<slh_lora_merge_desc>(p, sz, slh_lora_merge, stream, "lora_merge"); break;
-            case SLH_OP_LAYERNORM: rc = run_desc<slh_ln_desc>(p, sz, slh_layernorm, stream, "layernorm"); break;
-            case SLH_OP_ATTN_FWD: rc = run_desc<slh_attn_desc>(p, sz, slh_attn_fwd, stream, "attn_fwd"); break;
-            case SLH_OP_TRANSPOSE_HEADS:
-                rc = run_desc<slh_transpose_desc>(p, sz, slh_transpose_heads, stream, "transpose_heads"); break;
-            case SLH_OP_TEMBED: rc = run_desc<slh_tembed_desc>(p, sz, slh_timestep_embed, stream, "tembed"); break;
-            case SLH_OP_CONV_IN: rc = run_desc<slh_convin_desc>(p, sz, slh_conv_in, stream, "conv_in"); break;
-            case SLH_OP_ELEMENTWISE: rc = run_desc<slh_ew_desc>(p, sz, slh_elementwise, stream, "elementwise"); break;
-            case SLH_OP_CFG_DDIM: rc = run_desc<slh_cfg_ddim_desc>(p, sz, slh_cfg_ddim, stream, "cfg_ddim"); break;
-            case SLH_OP_DDPM_EDIT: rc = run_desc<slh_ddpm_edit_desc>(p, sz, slh_ddpm_edit_step, stream, "ddpm_edit"); break;
-            case SLH_OP_DDPM_EDIT_BLEND:
-                rc = run_desc<slh_ddpm_edit_blend_desc>(p, sz, slh_ddpm_edit_blend, stream, "ddpm_edit_blend"); break;
-            case SLH_OP_EPS_ABSDIFF: rc = run_desc<slh_eps_absdiff_desc>(p, sz, slh_eps_absdiff, stream, "eps_absdiff"); break;
-            case SLH_OP_XATTN_MAP: rc = run_desc<slh_xattn_map_desc>(p, sz, slh_xattn_map, stream, "xattn_map"); break;
-            case SLH_OP_LOSS: rc = run_desc<slh_loss_desc>(p, sz, slh_guidance_loss, stream, "loss"); break;
-            case SLH_OP_WGRAD: rc = run_desc<slh_wgrad_desc>(p, sz, slh_lora_wgrad, stream, "wgrad"); break;
-            case SLH_OP_ADAMW: rc = run_desc<slh_adamw_desc>(p, sz, slh_adamw, stream, "adamw"); break;
-            case SLH_OP_LION: rc = run_desc<slh_lion_desc>(p, sz, slh_lion, stream, "lion"); break;
-            case SLH_OP_GN_BWD_STATS:
-                rc = run_desc<slh_gn_bwd_desc>(p, sz, slh_gn_bwd_stats, stream, "gn_bwd_stats"); break;
-            case SLH_OP_GN_BWD_APPLY:
-                rc = run_desc<slh_gn_bwd_desc>(p, sz, slh_gn_bwd_apply, stream, "gn_bwd_apply"); break;
-            case SLH_OP_LAYERNORM_BWD:
-                rc = run_desc<slh_ln_bwd_desc>(p, sz, slh_layernorm_bwd, stream, "layernorm_bwd"); break;
-            case SLH_OP_ATTN_BWD: rc = run_desc<slh_attn_bwd_desc>(p, sz, slh_attn_bwd, stream, "attn_bwd"); break;
-            case SLH_OP_LORA_CONV_DGRAD:
-                rc = run_desc<slh_lora_cdgrad_desc>(p, sz, slh_lora_conv_dgrad, stream, "lora_conv_dgrad"); break;
-            case SLH_OP_TEMB_LORA_BWD:
-                rc = run_desc<slh_temb_lora_bwd_desc>(p, sz, slh_temb_lora_bwd, stream, "temb_lora_bwd"); break;
-            case SLH_OP_SGEMM: rc = run_desc<slh_sgemm_desc>(p, sz, slh_sgemm, stream, "sgemm"); break;
-            case SLH_OP_GN32_STATS: rc = run_desc<slh_gn32_desc>(p, sz, slh_gn32_stats, stream, "gn32_stats"); break;
-            case SLH_OP_GN32_APPLY: rc = run_desc<slh_gn32_desc>(p, sz, slh_gn32_apply, stream, "gn32_apply"); break;
-            case SLH_OP_SOFTMAX32: rc = run_desc<slh_softmax32_desc>(p, sz, slh_softmax32, stream, "softmax32"); break;
-            case SLH_OP_VAE_CONV_IN: rc = run_desc<slh_vae_conv_desc>(p, sz, slh_vae_conv_in, stream, "vae_conv_in"); break;
-            case SLH_OP_VAE_MOMENTS: rc = run_desc<slh_vae_conv_desc>(p, sz, slh_vae_moments, stream, "vae_moments"); break;
-            case SLH_OP_VAE_POST_QUANT: rc = run_desc<slh_vae_conv_desc>(p, sz, slh_vae_post_quant, stream, "vae_post_quant"); break;
-            case SLH_OP_VAE_SAMPLE: rc = run_desc<slh_vae_sample_desc>(p, sz, slh_vae_sample, stream, "vae_sample"); break;
-            case SLH_OP_WGRAD_BATCH: rc = run_desc<slh_batch_desc>(p, sz, slh_lora_wgrad_batch, stream, "wgrad_batch"); break;
-            case SLH_OP_TRANSPOSE_BATCH: rc = run_desc<slh_batch_desc>(p, sz, slh_transpose_heads_batch, stream, "transpose_batch"); break;
-            case SLH_OP_GATHER16: rc = run_desc<slh_gather16_desc>(p, sz, slh_gather16, stream, "gather16"); break;
-            case SLH_OP_MEMSET: {
-                if (sz != (int32_t)sizeof(slh_memset_desc)) { slh_set_error("slh_run_program: memset desc size"); return -3; }
-                slh_memset_desc d;
-                memcpy(&d, p, sizeof(d));
-                rc = fill_bytes(d.ptr, d.value, (long)d.nbytes, (hipStream_t)stream);
-                break;
-            }
-            default:
-                slh_set_error("slh_run_program: unknown opcode %d at op %d", op, idx);
-                return -3;
-        }
-        if (rc != 0) { rc_all = rc; break; }
+        const OpRow* row = op > 0 && op < kOpSlots ? index.at[op] : nullptr;
+        if (!row) { slh_set_error("slh_run_program: unknown opcode %d at op %d", op, idx); return -3; }
+        const int rc = row->run(p, sz, stream, row->entry);
+        if (rc != 0) return rc;          // stop at the first failing op
         p += (sz + 7) & ~7;
         ++idx;
     }
-    return rc_all;
+    return 0;
 }
 
 // ---- hipGraph replay ------------------------------------------------------------------------------------------------
@@ -182,23 +210,4 @@ extern "C" int slh_graph_destroy(void* graph) {
     (void)hipGraphDestroy(h->graph);
     delete h;
     return 0;
-}
-
-extern "C" int slh_desc_sizes(int32_t* out, int32_t cap) {
-    const int32_t sizes[] = {
-        (int32_t)sizeof(slh_gemm_desc),     (int32_t)sizeof(slh_skinny_desc),   (int32_t)sizeof(slh_gemv_desc),
-        (int32_t)sizeof(slh_gn_desc),       (int32_t)sizeof(slh_gn_bwd_desc),   (int32_t)sizeof(slh_ln_desc),
-        (int32_t)sizeof(slh_ln_bwd_desc),   (int32_t)sizeof(slh_attn_desc),     (int32_t)sizeof(slh_transpose_desc),
-        (int32_t)sizeof(slh_attn_bwd_desc), (int32_t)sizeof(slh_tembed_desc),   (int32_t)sizeof(slh_convin_desc),
-        (int32_t)sizeof(slh_ew_desc),       (int32_t)sizeof(slh_cfg_ddim_desc), (int32_t)sizeof(slh_loss_desc),
-        (int32_t)sizeof(slh_wgrad_desc),    (int32_t)sizeof(slh_adamw_desc),    (int32_t)sizeof(slh_memset_desc),
-        (int32_t)sizeof(slh_lora_cdgrad_desc), (int32_t)sizeof(slh_temb_lora_bwd_desc),
-        (int32_t)sizeof(slh_sgemm_desc),    (int32_t)sizeof(slh_gn32_desc),     (int32_t)sizeof(slh_softmax32_desc),
-        (int32_t)sizeof(slh_vae_conv_desc), (int32_t)sizeof(slh_vae_sample_desc), (int32_t)sizeof(slh_lion_desc),
-        (int32_t)sizeof(slh_batch_desc),    (int32_t)sizeof(slh_gather16_desc), (int32_t)sizeof(slh_lora_lnfold_desc),
-        (int32_t)sizeof(slh_lora_merge_desc), (int32_t)sizeof(slh_ddpm_edit_desc),
-        (int32_t)sizeof(slh_ddpm_edit_blend_desc), (int32_t)sizeof(slh_eps_absdiff_desc), (int32_t)sizeof(slh_xattn_map_desc)};
-    const int n = (int)(sizeof(sizes) / sizeof(sizes[0]));
-    for (int i = 0; i < n && i < cap; ++i) out[i] = sizes[i];
-    return n;
 }

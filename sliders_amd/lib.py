@@ -1,7 +1,7 @@
 """ctypes binding of libsliders_hip.so (include/sliders_hip.h).
 
-The product path has NO fallback: if the shared library is missing or a descriptor size disagrees
-with the header the import of this module raises, and every op raises RuntimeError with the
+The product path has NO fallback: if the shared library is missing, or an opcode's entry point or descriptor
+size disagrees with the library's own op table (slh_op_info), load() raises, and every op raises RuntimeError with the
 library's slh_last_error() text on a non-zero status.
 """
 from __future__ import annotations
@@ -125,14 +125,6 @@ VaeSampleDesc = _struct("VaeSampleDesc", _ptrs("moments", "post_noise", "noise",
                         + _ints("batch", "hw") + [("scaling", c_f32), ("sqrt_alpha", c_f32), ("sqrt_one_minus_alpha", c_f32)]
                         + _ints("pad_"))
 
-# order of slh_desc_sizes()
-_SIZE_ORDER = [GemmDesc, SkinnyDesc, GemvDesc, GnDesc, GnBwdDesc, LnDesc, LnBwdDesc, AttnDesc, TransposeDesc,
-               AttnBwdDesc, TembedDesc, ConvInDesc, EwDesc, CfgDdimDesc, LossDesc, WgradDesc, AdamwDesc, MemsetDesc,
-               LoraCdgradDesc, TembLoraBwdDesc, SgemmDesc, Gn32Desc, Softmax32Desc, VaeConvDesc, VaeSampleDesc, LionDesc,
-               BatchDesc, Gather16Desc, LoraLnFoldDesc, LoraMergeDesc, DdpmEditDesc, DdpmEditBlendDesc, EpsAbsdiffDesc]
-# ... and the descriptors slh_desc_sizes() lists behind those (tests pin the tail of _SIZE_ORDER: new ones are appended here)
-_SIZE_ORDER_APPENDED = [XattnMapDesc]
-
 # opcodes (enum in sliders_hip.h)
 OP_GEMM, OP_SKINNY, OP_GEMV, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTN_FWD, OP_TRANSPOSE_HEADS = range(1, 9)
 OP_TEMBED, OP_CONV_IN, OP_ELEMENTWISE, OP_CFG_DDIM, OP_LOSS, OP_WGRAD, OP_ADAMW = range(9, 16)
@@ -149,7 +141,7 @@ OP_XATTN_MAP = 42
 
 EW_COPY, EW_ADD, EW_GEGLU_FWD, EW_GEGLU_BWD, EW_UPSAMPLE_BWD, EW_COLSUM = range(6)
 
-# C entry point per opcode, for direct (non-program) calls
+# C entry point and descriptor per opcode: what call() launches and what load() holds against the library's own op table (slh_op_info)
 _ENTRY = {
     OP_GEMM: ("slh_gemm", GemmDesc), OP_SKINNY: ("slh_skinny", SkinnyDesc), OP_GEMV: ("slh_gemv", GemvDesc),
     OP_GN_STATS: ("slh_gn_stats", GnDesc), OP_GN_APPLY: ("slh_gn_apply", GnDesc),
@@ -159,7 +151,7 @@ _ENTRY = {
     OP_CFG_DDIM: ("slh_cfg_ddim", CfgDdimDesc), OP_LOSS: ("slh_guidance_loss", LossDesc),
     OP_WGRAD: ("slh_lora_wgrad", WgradDesc), OP_ADAMW: ("slh_adamw", AdamwDesc),
     OP_GN_BWD_STATS: ("slh_gn_bwd_stats", GnBwdDesc), OP_GN_BWD_APPLY: ("slh_gn_bwd_apply", GnBwdDesc),
-    OP_LAYERNORM_BWD: ("slh_layernorm_bwd", LnBwdDesc), OP_ATTN_BWD: ("slh_attn_bwd", AttnBwdDesc),
+    OP_LAYERNORM_BWD: ("slh_layernorm_bwd", LnBwdDesc), OP_ATTN_BWD: ("slh_attn_bwd", AttnBwdDesc), OP_MEMSET: ("slh_memset", MemsetDesc),
     OP_LORA_CONV_DGRAD: ("slh_lora_conv_dgrad", LoraCdgradDesc), OP_TEMB_LORA_BWD: ("slh_temb_lora_bwd", TembLoraBwdDesc),
     OP_SGEMM: ("slh_sgemm", SgemmDesc), OP_GN32_STATS: ("slh_gn32_stats", Gn32Desc), OP_GN32_APPLY: ("slh_gn32_apply", Gn32Desc),
     OP_SOFTMAX32: ("slh_softmax32", Softmax32Desc), OP_VAE_CONV_IN: ("slh_vae_conv_in", VaeConvDesc),
@@ -173,9 +165,26 @@ _ENTRY = {
     OP_XATTN_MAP: ("slh_xattn_map", XattnMapDesc),
 }
 
-EXPORTS = ["slh_version", "slh_last_error", "slh_run_program", "slh_desc_sizes", "slh_graph_capture", "slh_graph_launch",
-           "slh_graph_destroy", "slh_gemm_kernel_name", "slh_gemm_launch_query", "slh_gemm_tile_ok", "slh_gemm_ln_chunk_cols", "slh_attn_fwd_carries_touch", "slh_attn_fwd_kernel_name", "slh_attn_bwd_kernel_names", "slh_gn_row_blocks", "slh_gn_clusters", "slh_gn32_row_blocks",
-           "slh_lora_wgrad_blocks", "slh_lora_wgrad_single_blocks", "slh_lora_wgrad_geometry", "slh_skinny_kernel_name", "slh_transpose_heads_blocks", "slh_gn_fused_ok", "slh_lora_merge_blocks"] + [v[0] for v in _ENTRY.values()]
+# every other export: name -> (restype, argtypes), applied once by load()
+_P, _str = C.POINTER, C.c_char_p
+_HOST_FNS = {
+    "slh_version": (c_i32, []), "slh_last_error": (_str, []),
+    "slh_run_program": (c_i32, [c_vp, c_i64, c_vp]), "slh_op_info": (c_i32, [c_i32, _P(c_i32), _P(_str), _P(c_i32)]),
+    "slh_graph_capture": (c_i32, [c_vp, c_i64, _P(c_vp)]), "slh_graph_launch": (c_i32, [c_vp, c_vp]), "slh_graph_destroy": (c_i32, [c_vp]),
+    "slh_gemm_kernel_name": (c_i32, [_P(GemmDesc), _str, c_i32]),
+    "slh_gemm_launch_query": (c_i32, [_P(GemmDesc), _str, c_i32, _P(c_i32), _P(c_i32), _P(C.c_uint64)]),
+    "slh_gemm_tile_ok": (c_i32, [_P(GemmDesc)]), "slh_gemm_ln_chunk_cols": (c_i32, [_P(GemmDesc)]),
+    "slh_skinny_kernel_name": (c_i32, [_P(SkinnyDesc), _str, c_i32]),
+    "slh_attn_fwd_carries_touch": (c_i32, [_P(AttnDesc)]), "slh_attn_fwd_kernel_name": (c_i32, [_P(AttnDesc), _str, c_i32]),
+    "slh_attn_bwd_kernel_names": (c_i32, [_P(AttnBwdDesc), _str, _str, c_i32]),
+    "slh_gn_row_blocks": (c_i32, [c_i32, c_i32, c_i32]), "slh_gn_clusters": (c_i32, [c_i32]), "slh_gn32_row_blocks": (c_i32, [c_i32]),
+    "slh_gn_fused_ok": (c_i32, [c_i32, c_i32, c_i32]),
+    "slh_lora_wgrad_blocks": (c_i32, [_P(WgradDesc)]), "slh_lora_wgrad_single_blocks": (c_i32, [_P(WgradDesc)]),
+    "slh_lora_wgrad_geometry": (c_i32, [_P(WgradDesc), c_i32, _P(c_i32)]),
+    "slh_transpose_heads_blocks": (c_i32, [_P(TransposeDesc)]), "slh_lora_merge_blocks": (c_i32, [_P(LoraMergeItem)]),
+}
+
+EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
 
 
 class SlidersHipError(RuntimeError):
@@ -199,28 +208,24 @@ def load() -> C.CDLL:
     # leaves two runtimes in the process and every launch fails with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    lib.slh_last_error.restype = C.c_char_p
-    lib.slh_run_program.argtypes = [c_vp, c_i64, c_vp]
-    lib.slh_run_program.restype = c_i32
-    lib.slh_desc_sizes.argtypes = [C.POINTER(c_i32), c_i32]
-    lib.slh_graph_capture.argtypes = [c_vp, c_i64, C.POINTER(c_vp)]
-    lib.slh_graph_capture.restype = c_i32
-    lib.slh_graph_launch.argtypes = [c_vp, c_vp]
-    lib.slh_graph_launch.restype = c_i32
-    lib.slh_graph_destroy.argtypes = [c_vp]
-    lib.slh_graph_destroy.restype = c_i32
-    for name, desc in _ENTRY.values():
+    signatures = dict(_HOST_FNS)
+    signatures.update((name, (c_i32, [_P(desc), c_vp])) for name, desc in _ENTRY.values())
+    for name, (restype, argtypes) in signatures.items():
         fn = getattr(lib, name)
-        fn.argtypes = [C.POINTER(desc), c_vp]
-        fn.restype = c_i32
-    sizes = (c_i32 * 64)()
-    n = lib.slh_desc_sizes(sizes, 64)
-    order = _SIZE_ORDER + _SIZE_ORDER_APPENDED
-    if n != len(order):
-        raise SlidersHipError(f"binding/library mismatch: library reports {n} descriptors, binding has {len(order)}")
-    for i, d in enumerate(order):
-        if C.sizeof(d) != sizes[i]:
-            raise SlidersHipError(f"binding/library mismatch: sizeof({d.__name__}) = {C.sizeof(d)} vs {sizes[i]}")
+        fn.restype, fn.argtypes = restype, argtypes
+    # the library's op table, keyed by opcode, against this binding's
+    theirs = {}
+    op, entry, size = c_i32(), _str(), c_i32()
+    for i in range(lib.slh_op_info(-1, None, None, None)):
+        lib.slh_op_info(i, C.byref(op), C.byref(entry), C.byref(size))
+        theirs[op.value] = (entry.value.decode(), size.value)
+    if set(theirs) != set(_ENTRY):
+        raise SlidersHipError(f"binding/library mismatch: opcodes only in the library {sorted(set(theirs) - set(_ENTRY))}, "
+                              f"only in the binding {sorted(set(_ENTRY) - set(theirs))}")
+    for opcode, (name, desc) in _ENTRY.items():
+        if (name, C.sizeof(desc)) != theirs[opcode]:
+            field = "entry" if name != theirs[opcode][0] else f"sizeof({desc.__name__})"
+            raise SlidersHipError(f"binding/library mismatch: opcode {opcode} {field}: binding {(name, C.sizeof(desc))}, library {theirs[opcode]}")
     _lib = lib
     return lib
 
@@ -254,10 +259,7 @@ TILE_256x320 = 0x748A     # eight compute waves (gemm7w_kernel): GEGLU.proj as o
 def gemm_tile_ok(desc) -> bool:
     """slh_gemm_tile_ok: the tile named by desc.tile (0: the library's heuristic) can run this descriptor - every check of slh_gemm
     but the split-K workspace and ln_lora_s / ln_lora_c, which a caller provisions after choosing the tile"""
-    lib = load()
-    lib.slh_gemm_tile_ok.argtypes = [C.POINTER(GemmDesc)]
-    lib.slh_gemm_tile_ok.restype = c_i32
-    return bool(lib.slh_gemm_tile_ok(C.byref(desc)))
+    return bool(load().slh_gemm_tile_ok(C.byref(desc)))
 
 
 def gemm5_ok(desc) -> bool:
@@ -274,10 +276,7 @@ def gemm7_ok(desc) -> bool:
 
 def gemm_ln_chunk_cols(desc) -> int:
     """slh_gemm_ln_chunk_cols: width of the LayerNorm chunks desc's tile writes to desc.ln_out (80 or 64), 0 where it cannot"""
-    lib = load()
-    lib.slh_gemm_ln_chunk_cols.argtypes = [C.POINTER(GemmDesc)]
-    lib.slh_gemm_ln_chunk_cols.restype = c_i32
-    return lib.slh_gemm_ln_chunk_cols(C.byref(desc))
+    return load().slh_gemm_ln_chunk_cols(C.byref(desc))
 
 
 def gn_fused_ok(channels: int, hw: int, groups: int) -> int:
@@ -302,10 +301,7 @@ def batch_table(opcode: int, descs, device, arg: int = 0):
     the library here, at plan time (slh_*_blocks); device = None builds a pointer-less descriptor for dry-run planning."""
     import torch
     fn_name, dtype = _BATCH_KINDS[opcode]
-    l = load()
-    fn = getattr(l, fn_name)
-    fn.argtypes = [C.POINTER(dtype)]
-    fn.restype = c_i32
+    fn = getattr(load(), fn_name)
     prefix = [0]
     slab_geom = 0
     if opcode == OP_WGRAD_BATCH:
@@ -350,8 +346,6 @@ def merge_table(items, device):
     (slh_lora_merge_blocks); the device table and the running sum of workgroups are built once and reused by every launch."""
     import torch
     l = load()
-    l.slh_lora_merge_blocks.argtypes = [C.POINTER(LoraMergeItem)]
-    l.slh_lora_merge_blocks.restype = c_i32
     prefix = [0]
     for it in items:
         nb = l.slh_lora_merge_blocks(C.byref(it))
@@ -365,10 +359,7 @@ def merge_table(items, device):
 
 def wgrad_single_blocks(desc) -> int:
     """Workgroups (= slabs = tickets) of a stand-alone slh_lora_wgrad launch with the fixed-order reduction."""
-    lib = load()
-    lib.slh_lora_wgrad_single_blocks.argtypes = [C.POINTER(WgradDesc)]
-    lib.slh_lora_wgrad_single_blocks.restype = c_i32
-    nb = lib.slh_lora_wgrad_single_blocks(C.byref(desc))
+    nb = load().slh_lora_wgrad_single_blocks(C.byref(desc))
     if nb <= 0:
         raise SlidersHipError(f"slh_lora_wgrad_single_blocks: {last_error()}")
     return nb
@@ -377,83 +368,57 @@ def wgrad_single_blocks(desc) -> int:
 def wgrad_geometry(desc, kind: int):
     """slh_lora_wgrad_geometry: (gx, splits, taps, rows_per_block) of desc's problem for kind 0 (fp32 atomics), 1 (single launch with
     slabs) or 2 (inside a batch with slabs), from the library's one geometry function; shape fields only, no device needed."""
-    lib = load()
-    lib.slh_lora_wgrad_geometry.argtypes = [C.POINTER(WgradDesc), c_i32, C.POINTER(c_i32)]
-    lib.slh_lora_wgrad_geometry.restype = c_i32
     out = (c_i32 * 4)()
-    if lib.slh_lora_wgrad_geometry(C.byref(desc), kind, out) != 0:
+    if load().slh_lora_wgrad_geometry(C.byref(desc), kind, out) != 0:
         raise SlidersHipError(f"slh_lora_wgrad_geometry: {last_error()}")
     return tuple(out)
+
+
+def _kernel_names(query: str, desc, cap: int, bufs: int = 1) -> tuple:
+    """One of the library's name queries: `bufs` kernel names of at most cap bytes each for desc, or the library's refusal raised."""
+    lib = load()
+    out = [C.create_string_buffer(cap) for _ in range(bufs)]
+    rc = getattr(lib, query)(C.byref(desc), *out, cap)
+    if rc != 0:
+        raise SlidersHipError(f"{query} failed ({rc}): {lib.slh_last_error().decode()}")
+    return tuple(b.value.decode() for b in out)
 
 
 def skinny_kernel_name(desc) -> str:
     """slh_skinny_kernel_name: the instantiation slh_skinny would launch for this descriptor ('skinny<12,16>': accumulator rows, lanes
     per output row), named by the selection function slh_skinny launches through; raises for a descriptor slh_skinny refuses."""
-    lib = load()
-    lib.slh_skinny_kernel_name.argtypes = [C.POINTER(SkinnyDesc), C.c_char_p, c_i32]
-    lib.slh_skinny_kernel_name.restype = c_i32
-    buf = C.create_string_buffer(64)
-    rc = lib.slh_skinny_kernel_name(C.byref(desc), buf, 64)
-    if rc != 0:
-        raise SlidersHipError(f"slh_skinny_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
-    return buf.value.decode()
+    return _kernel_names("slh_skinny_kernel_name", desc, 64)[0]
 
 
 def attn_carries_touch(desc) -> bool:
     """slh_attn_fwd_carries_touch: this attention launch runs the key-split form, whose idle workgroup slots can stream weights for a
     later product (slh_attn_desc.pf_*)"""
-    lib = load()
-    lib.slh_attn_fwd_carries_touch.argtypes = [C.POINTER(AttnDesc)]
-    lib.slh_attn_fwd_carries_touch.restype = c_i32
-    return bool(lib.slh_attn_fwd_carries_touch(C.byref(desc)))
+    return bool(load().slh_attn_fwd_carries_touch(C.byref(desc)))
 
 
 def attn_fwd_kernel_name(desc) -> str:
     """slh_attn_fwd_kernel_name: the instantiation slh_attn_fwd would launch for this descriptor ('attn_fwd_kernel<4, 1, true>',
     'attn_fwd_ks_kernel'), named by the dispatch code itself; raises for a descriptor slh_attn_fwd refuses."""
-    lib = load()
-    lib.slh_attn_fwd_kernel_name.argtypes = [C.POINTER(AttnDesc), C.c_char_p, c_i32]
-    lib.slh_attn_fwd_kernel_name.restype = c_i32
-    buf = C.create_string_buffer(96)
-    rc = lib.slh_attn_fwd_kernel_name(C.byref(desc), buf, 96)
-    if rc != 0:
-        raise SlidersHipError(f"slh_attn_fwd_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
-    return buf.value.decode()
+    return _kernel_names("slh_attn_fwd_kernel_name", desc, 96)[0]
 
 
 def attn_bwd_kernel_names(desc):
     """slh_attn_bwd_kernel_names: (dq, dkv) instantiations slh_attn_bwd would launch ('attn_bwd_dq_kernel<2>',
     'attn_bwd_dkv_kernel<2, 2>'; dkv is '' with need_dkv = 0); raises for a descriptor slh_attn_bwd refuses."""
-    lib = load()
-    lib.slh_attn_bwd_kernel_names.argtypes = [C.POINTER(AttnBwdDesc), C.c_char_p, C.c_char_p, c_i32]
-    lib.slh_attn_bwd_kernel_names.restype = c_i32
-    a, b = C.create_string_buffer(96), C.create_string_buffer(96)
-    rc = lib.slh_attn_bwd_kernel_names(C.byref(desc), a, b, 96)
-    if rc != 0:
-        raise SlidersHipError(f"slh_attn_bwd_kernel_names failed ({rc}): {lib.slh_last_error().decode()}")
-    return a.value.decode(), b.value.decode()
+    return _kernel_names("slh_attn_bwd_kernel_names", desc, 96, bufs=2)
 
 
 def gemm_kernel_name(desc) -> str:
     """slh_gemm_kernel_name: the kernel instantiation slh_gemm would launch for this descriptor, spelled as rocprofv3 prints it
     (e.g. 'gemm8pb_kernel<1, 5, 0, false>').  The library runs its whole dispatch with the launch replaced by a record of the template
     it selected, so a new tile can never be mis-named here; raises (with the library's message) for a descriptor slh_gemm refuses."""
-    lib = load()
-    lib.slh_gemm_kernel_name.argtypes = [C.POINTER(GemmDesc), C.c_char_p, c_i32]
-    lib.slh_gemm_kernel_name.restype = c_i32
-    buf = C.create_string_buffer(160)
-    rc = lib.slh_gemm_kernel_name(C.byref(desc), buf, 160)
-    if rc != 0:
-        raise SlidersHipError(f"slh_gemm_kernel_name failed ({rc}): {lib.slh_last_error().decode()}")
-    return buf.value.decode()
+    return _kernel_names("slh_gemm_kernel_name", desc, 160)[0]
 
 
 def gemm_launch_query(desc):
     """slh_gemm_launch_query: (kernel name, grid, block size, FNV-1a hash of the kernel's argument bytes) of the launch slh_gemm would
     make for this descriptor - a function of the descriptor alone, no device needed; raises for a descriptor slh_gemm refuses."""
     lib = load()
-    lib.slh_gemm_launch_query.argtypes = [C.POINTER(GemmDesc), C.c_char_p, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(C.c_uint64)]
-    lib.slh_gemm_launch_query.restype = c_i32
     buf, grid, block, h = C.create_string_buffer(160), c_i32(), c_i32(), C.c_uint64()
     rc = lib.slh_gemm_launch_query(C.byref(desc), buf, 160, C.byref(grid), C.byref(block), C.byref(h))
     if rc != 0:

@@ -19,6 +19,7 @@ from sliders_amd.ddim import DDIMSchedule
 from sliders_amd.edit import (NoiseSpace, blend_reference, ddpm_mu_reference, ddpm_step_coefficients, edit_reference, feather_mask,
                               footprint_mask, invert_reference, load_mask)
 from tests.test_edit_host import toy_predict
+from tests.test_host import library_ops
 
 U = 2.0 ** -24
 SHAPE = (2, 4, 9, 7)
@@ -361,7 +362,8 @@ def test_ddpm_edit_blend_refuses_bad_descriptors_before_any_launch():
     assert lib._ENTRY[lib.OP_DDPM_EDIT_BLEND] == ("slh_ddpm_edit_blend", lib.DdpmEditBlendDesc)
     assert ctypes.sizeof(lib.DdpmEditBlendDesc) == 9 * 8 + 3 * 4 + 6 * 4 + 4 == 112
     assert ctypes.sizeof(lib.DdpmEditDesc) == 104, "slh_ddpm_edit_desc is what it was"
-    assert lib._SIZE_ORDER[-3:] == [lib.DdpmEditDesc, lib.DdpmEditBlendDesc, lib.EpsAbsdiffDesc], "appended, not reordered"
+    ops = library_ops()                             # the library's own table lists the three ops of the edit under their opcodes
+    assert (ops[39], ops[40], ops[41]) == (("slh_ddpm_edit_step", 104), ("slh_ddpm_edit_blend", 112), ("slh_eps_absdiff", 56))
     # never dereferenced: every case is refused on the host.  nb * chw * 4 = 256 bytes per fp32 buffer, the buffers 0x1000 apart
     full = dict(eps=0x1000, x=0x2000, resid=0x3000, keep=0x4000, mask=0x5000, out=0x6000, out_bf16=0x7000, out2_bf16=0x8000, nb=1, chw=64, hw=16,
                 guidance=7.5, c_sqrt_beta_t=0.5, c_inv_sqrt_alpha_t=1.2, c_sqrt_alpha_t=0.8, c_sqrt_alpha_prev=0.9, c_dir=0.3)

@@ -55,11 +55,132 @@ def test_c_abi_exports_exactly_the_declared_symbols():
     for sym in sorted(declared):
         assert hasattr(l, sym), f"{sym} declared in sliders_hip.h but not exported"
     assert declared == set(lib.EXPORTS)
-    assert l.slh_version() >= 1
-    # descriptor sizes were cross-checked inside lib.load(); a bad descriptor is rejected with a message
+    assert l.slh_version() >= 2, "2: slh_op_info and slh_memset exist"
+    # entry names and descriptor sizes were cross-checked per opcode inside lib.load(); a bad descriptor is rejected with a message
     d = lib.GemmDesc()
     assert l.slh_gemm(ctypes.byref(d), None) != 0
     assert b"slh_gemm" in l.slh_last_error()
+
+
+def library_ops():
+    """opcode -> (entry point, sizeof(descriptor)) as the library's own op table has it (slh_op_info)"""
+    l = lib.load()
+    n = l.slh_op_info(-1, None, None, None)
+    op, entry, size = ctypes.c_int32(-7), ctypes.c_char_p(), ctypes.c_int32(-7)
+    assert l.slh_op_info(n, ctypes.byref(op), ctypes.byref(entry), ctypes.byref(size)) == n
+    assert (op.value, entry.value, size.value) == (-7, None, -7), "an index out of range writes nothing"
+    rows = {}
+    for i in range(n):
+        assert l.slh_op_info(i, ctypes.byref(op), ctypes.byref(entry), ctypes.byref(size)) == n
+        assert op.value not in rows, f"opcode {op.value} listed twice"
+        rows[op.value] = (entry.value.decode(), size.value)
+    return rows
+
+
+def test_library_op_table_is_the_bindings():
+    rows = library_ops()
+    assert len(rows) == 41 and rows == {op: (name, ctypes.sizeof(desc)) for op, (name, desc) in lib._ENTRY.items()}
+    assert rows[lib.OP_MEMSET] == ("slh_memset", 24) and lib.OP_MEMSET == 20
+    # slh_memset on the host: nothing to fill is a success that launches nothing, through either route; bad descriptors are refused
+    lib.call(lib.OP_MEMSET, lib.MemsetDesc(ptr=0, nbytes=0, value=1), 0)
+    lib.call(lib.OP_MEMSET, lib.MemsetDesc(ptr=0x1000, nbytes=-5), 0)
+    prog = lib.Program()
+    prog.memset(0x1000, 0)
+    prog.run(0)
+    with pytest.raises(lib.SlidersHipError, match="slh_memset: null ptr"):
+        lib.call(lib.OP_MEMSET, lib.MemsetDesc(ptr=0, nbytes=16), 0)
+    assert lib.load().slh_memset(None, None) != 0 and b"slh_memset" in lib.load().slh_last_error()
+    # the executor's own refusals keep their texts and status
+    prog = lib.Program()
+    prog.add(lib.OP_MEMSET, lib.Gather16Desc(), "wrong descriptor")
+    with pytest.raises(lib.SlidersHipError, match=r"rc=-3.*slh_memset descriptor is 32 bytes, library expects 24"):
+        prog.run(0)
+    prog = lib.Program()
+    prog.add(37, lib.MemsetDesc(), "retired opcode")
+    with pytest.raises(lib.SlidersHipError, match=r"rc=-3.*unknown opcode 37 at op 0"):
+        prog.run(0)
+    l, raw = lib.load(), bytes(prog.finalize())
+    for cut, what in ((4, b"truncated record header at op 0"), (16, b"truncated record at op 0")):
+        assert l.slh_run_program(raw[:cut], cut, None) == -3 and what in l.slh_last_error()
+
+
+# ---- the binding equals the header -------------------------------------------------------------------------------------------------
+_KIND = {lib.c_vp: "pointer", lib.c_i32: "int32_t", lib.c_i64: "int64_t", lib.c_f32: "float", lib.c_f64: "double"}
+
+
+def _parse_header():
+    """include/sliders_hip.h -> (struct -> [(field, kind)], entry point -> descriptor struct, SLH_OP_ name -> value); kind is 'pointer' or
+    the scalar's C type.  A declaration this small parser does not understand raises."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sliders_hip.h")).read(), flags=re.S)
+    structs = {}
+    for name, body in re.findall(r"typedef struct (slh_\w+) \{(.*?)\} \1;", hdr, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(r"(?:const )?(\w+)(\*?) ([\w, ]+)", decl)
+            assert m, f"{name}: cannot parse '{decl}'"
+            ctype, star, names = m.groups()
+            names = [n.strip() for n in names.split(",")]
+            assert (len(names) == 1 and ctype in ("void", "float", "int32_t", "uint32_t", "uint64_t") or ctype.startswith("slh_")) if star \
+                else ctype in ("int32_t", "int64_t", "float", "double"), f"{name}: '{decl}'"
+            fields += [(n, "pointer" if star else ctype) for n in names]
+        structs[name] = fields
+    entries = dict(re.findall(r"^int (slh_\w+)\(const (slh_\w+_desc)\* d, slh_stream_t stream\);", hdr, flags=re.M))
+    ops = {n: int(v) for n, v in re.findall(r"\bSLH_OP_(\w+) = (\d+)", hdr)}
+    return structs, entries, ops
+
+
+def _binding_ops(module=lib):
+    return {n[3:]: v for n, v in vars(module).items() if n.startswith("OP_") and isinstance(v, int)}
+
+
+def _abi_mismatches(header, entry_table, ops):
+    """every disagreement between the parsed header and a binding's (opcode -> (entry, ctypes struct), OP_ name -> value), as text"""
+    structs, entries, hdr_ops = header
+    out = [f"SLH_OP_{n}: header {hdr_ops.get(n)}, binding {ops.get(n)}" for n in sorted(set(hdr_ops) | set(ops)) if hdr_ops.get(n) != ops.get(n)]
+    out += [f"opcode {op} has no OP_ constant" for op in entry_table if op not in ops.values()]
+    for op, (entry, desc) in sorted(entry_table.items()):
+        if entry not in entries:
+            out.append(f"opcode {op}: {entry} is not declared as int {entry}(const slh_*_desc* d, slh_stream_t stream)")
+            continue
+        out += _struct_mismatches(structs[entries[entry]], desc, f"opcode {op} {entry}: {entries[entry]} / {desc.__name__}")
+    return out
+
+
+def _struct_mismatches(fields, ctype, what):
+    mine = [(n, _KIND[t]) for n, t in ctype._fields_]
+    if mine == fields:
+        return []
+    at = next((i for i, (a, b) in enumerate(zip(fields, mine)) if a != b), min(len(fields), len(mine)))
+    return [f"{what}: field {at}: header {fields[at] if at < len(fields) else None}, binding {mine[at] if at < len(mine) else None}"]
+
+
+def test_binding_equals_header():
+    """Every SLH_OP_* value, and every field of every descriptor by name, order and kind (pointer / int32_t / int64_t / float / double),
+    is the same in include/sliders_hip.h and in sliders_amd/lib.py - what the load-time check (entry name and sizeof per opcode)
+    cannot see: two same-sized fields swapped load cleanly and compute garbage."""
+    header = _parse_header()
+    structs, entries, hdr_ops = header
+    assert len(structs) >= 36 and len(hdr_ops) == 41 and len(set(hdr_ops.values())) == 41
+    assert set(hdr_ops.values()) == set(lib._ENTRY), "every opcode of the header has a row of lib._ENTRY and the other way round"
+    assert _abi_mismatches(header, lib._ENTRY, _binding_ops()) == []
+    assert {entries[e] for e, _ in lib._ENTRY.values()} | {"slh_lora_merge_item", "slh_lora_lnfold_item"} == set(structs), \
+        "a struct of the header that no check above looked at"
+    assert _struct_mismatches(structs["slh_lora_merge_item"], lib.LoraMergeItem, "slh_lora_merge_item") == []
+    # slh_lora_lnfold_item has no ctypes struct: lib.lnfold_item writes it as int64 words
+    item = structs["slh_lora_lnfold_item"]
+    assert [k for _, k in item] == ["pointer"] * 6 + ["int32_t"] * 2 and [n for n, _ in item[6:]] == ["rows", "K"]
+    assert 8 * lib.LORA_LNFOLD_ITEM_I64 == 6 * 8 + 2 * 4
+    # the comparison can fail: two same-kind neighbours swapped in one struct, one opcode value changed
+    f = list(lib.AttnDesc._fields_)
+    i = [n for n, _ in f].index("ldq")
+    assert f[i + 1][0] == "ldk" and f[i][1] is f[i + 1][1]
+    f[i], f[i + 1] = f[i + 1], f[i]
+    swapped = type("AttnDesc", (ctypes.Structure,), {"_fields_": f})
+    assert ctypes.sizeof(swapped) == ctypes.sizeof(lib.AttnDesc), "the load-time check would pass this one"
+    got = _abi_mismatches(header, {**lib._ENTRY, lib.OP_ATTN_FWD: ("slh_attn_fwd", swapped)}, _binding_ops())
+    assert len(got) == 1 and "slh_attn_fwd" in got[0] and "('ldq', 'int32_t')" in got[0] and "('ldk', 'int32_t')" in got[0], got
+    got = _abi_mismatches(header, lib._ENTRY, {**_binding_ops(), "LION": 30})
+    assert got == ["SLH_OP_LION: header 31, binding 30", "opcode 31 has no OP_ constant"], got
 
 
 class _FakeWeights:

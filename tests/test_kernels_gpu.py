@@ -1678,3 +1678,27 @@ def test_gemm_splitk(dev, tile):
     torch.cuda.synchronize()
     report(f"splitk conv 2src tile{tile:x}", cc, ref, TOL)
     assert int(tickets.abs().sum()) == 0
+
+
+def test_memset_every_byte(dev):
+    """slh_memset (fill_kernel: thread 0 writes the bytes up to the first 16-byte boundary and the tail, every thread one aligned uint4 of
+    the middle) against buf[o:o+n] = v in torch, exactly, launched directly and as a one-op program: start offsets around the 16-byte
+    alignment x lengths that are head only, tail only, one aligned vector, and one and two 256-thread blocks (4096 bytes each) with a tail.
+    One comparison of the whole buffer: the 64-byte fences and every byte outside the range keep their 0xAB."""
+    FENCE, BODY = 64, 8704
+    buf = torch.empty(FENCE + BODY + FENCE, dtype=torch.uint8, device=dev)
+    assert p(buf) % 16 == 0
+    for o in (0, 1, 15, 16):
+        for n in (0, 1, 15, 16, 17, 31, 4096, 4096 + 17, 8192 + 5):
+            for v in (0, 0x5A):
+                exp = torch.full_like(buf, 0xAB)
+                exp[FENCE + o:FENCE + o + n] = v
+                d = lib.MemsetDesc(ptr=p(buf) + FENCE + o, nbytes=n, value=v, pad=0)
+                one = lib.Program()
+                one.add(lib.OP_MEMSET, d, "memset")
+                for how, launch in (("call", lambda: lib.call(lib.OP_MEMSET, d, stream())), ("program", lambda: one.run(stream()))):
+                    buf.fill_(0xAB)
+                    launch()
+                    bad = (buf != exp).nonzero().flatten()
+                    assert bad.numel() == 0, (f"memset offset {o} length {n} value {v:#x} through {how}: {bad.numel()} wrong bytes, first at "
+                                              f"{int(bad[0]) - FENCE - o} from the start of the range (got {int(buf[bad[0]]):#x})")

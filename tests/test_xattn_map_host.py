@@ -13,7 +13,7 @@ from sliders_amd.config import CONFIGS
 from sliders_amd.modules import build_tree
 from sliders_amd.planner import AttnMapSpec, UNetPlan
 from tests import xattn_map_matrix as xm
-from tests.test_host import _FakeWeights
+from tests.test_host import _FakeWeights, library_ops
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -23,12 +23,8 @@ def test_opcode_entry_and_descriptor_size():
     assert lib.OP_XATTN_MAP == 42
     assert lib._ENTRY[lib.OP_XATTN_MAP] == ("slh_xattn_map", lib.XattnMapDesc)
     assert "slh_xattn_map" in lib.EXPORTS
-    l = lib.load()
-    sizes = (C.c_int32 * 64)()
-    n = l.slh_desc_sizes(sizes, 64)
-    order = lib._SIZE_ORDER + lib._SIZE_ORDER_APPENDED
-    assert n == len(order) and order[-1] is lib.XattnMapDesc
-    assert sizes[n - 1] == C.sizeof(lib.XattnMapDesc) == 4 * 8 + 9 * 4 + 2 * 4 + 4
+    assert library_ops()[42] == ("slh_xattn_map", C.sizeof(lib.XattnMapDesc)), "the library's own table lists opcode 42 so"
+    assert C.sizeof(lib.XattnMapDesc) == 4 * 8 + 9 * 4 + 2 * 4 + 4
 
 
 def _good(**kw):
