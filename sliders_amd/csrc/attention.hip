@@ -16,10 +16,6 @@
 
 namespace {
 
-__device__ __forceinline__ int lds_off(int row, int slot) {
-    return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
-}
-
 // NW waves per workgroup: 4 (128 queries) or 2 (64 queries, used when the grid would not fill the chip)
 // TAIL: Tk is not a multiple of 64 (cross-attention, Tk = 77): the key columns past Tk of the last tile are masked.  A
 // template flag because hipcc if-converts the mask into ~50 selects per tile that every tile of every launch would execute.
@@ -445,12 +441,7 @@ __global__ __launch_bounds__(256) void transpose_heads_kernel(const slh_transpos
 // n problems in one launch (slh_batch_desc): workgroup -> problem by bisection of the prefix sums
 __global__ __launch_bounds__(256) void transpose_heads_batch_kernel(const slh_transpose_desc* table, const int* prefix, int n) {
     const int bid = blockIdx.x;
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= bid) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
+    const int lo = __builtin_amdgcn_readfirstlane(batch_find(prefix, n, bid));
     const slh_transpose_desc d = table[lo];
     const int D = d.D > 0 ? d.D : 64;
     const int DT = (D + 63) / 64;

@@ -18,9 +18,6 @@
 
 namespace {
 
-__device__ __forceinline__ int lds_off(int row, int slot) {
-    return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
-}
 __device__ __forceinline__ int perm_row(int r) {  // swap bits 2 and 3
     return (r & 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 3) | (r & 16);
 }

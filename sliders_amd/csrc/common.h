@@ -91,6 +91,21 @@ __device__ __forceinline__ void glds16_hidden(const void* gsrc, unsigned lds_byt
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
+// swizzled byte offset of (row, 16-byte slot) inside a [rows][64] bf16 LDS tile
+__device__ __forceinline__ int lds_off(int row, int slot) {
+    return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
+}
+
+// batched launches (slh_batch_desc): problem of workgroup `bid` = the last index with prefix[index] <= bid (prefix[0] = 0,
+// prefix[n] = total > bid)
+__device__ __forceinline__ int batch_find(const int* prefix, int n, int bid) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= bid) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // ---- weight touch (slh_gemm_desc.pf_* / slh_attn_desc.pf_*) --------------------------------------------------------------------
 // Workgroup `idx` of `count` touch workgroups - dispatched behind every workgroup that does the launch's own work - streams its

@@ -96,11 +96,8 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
             xrow_off0[i] = (long)m * p.lda0;
             xrow_off1[i] = (long)m * p.lda1;
         } else {
-            const int hw = p.ho * p.wo;
-            const int b = m / hw;
-            const int rem = m - b * hw;
-            const int oy = rem / p.wo;
-            xb[i] = b; xoy[i] = oy; xox[i] = rem - oy * p.wo;
+            const RowPixel px = pixel_of_row(m, p.ho, p.wo);
+            xb[i] = px.b; xoy[i] = px.oy; xox[i] = px.ox;
         }
     }
     const __bf16* wptr[WI];
@@ -109,8 +106,7 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
         const int row = (wave + NW * i) * 8 + frow;
         int n = n0 + row;
         n = n < p.N ? n : p.N - 1;
-        wptr[i] = p.w_packed ? p.w + ((long)(n >> 6) * (p.K >> 6)) * 4096 + ((n & 63) << 6) + (fslot << 3)
-                             : p.w + (long)n * p.ldw + ((fslot ^ ((row >> 1) & 7)) << 3);
+        wptr[i] = w_row_src(p, n, row, fslot);
     }
     const int wkstep = p.w_packed ? 4096 : BK;   // elements between consecutive K tiles of one W row group
 
@@ -125,34 +121,22 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
         char* dX = sX + buf * (BM * 128);
         char* dW = sW + buf * (BN * 128);
         if (MODE == 0) {
-            const bool s1 = k0 >= p.ca0;
-            const __bf16* base = s1 ? p.a1 : p.a0;
-            const int kk = s1 ? k0 - p.ca0 : k0;
+            const SrcSel s = src_select(p, k0);
 #pragma unroll
             for (int i = 0; i < XI; ++i) {
-                const __bf16* src = base + (s1 ? xrow_off1[i] : xrow_off0[i]) + kk + (xks[i] << 3);
+                const __bf16* src = s.base + (s.second ? xrow_off1[i] : xrow_off0[i]) + s.cc + (xks[i] << 3);
                 stage_copy(src, dX + (wave + NW * i) * 1024);
             }
         } else {
             const int tap = k0 / cin;
             const int c0 = k0 - tap * cin;
             const int ky = tap / 3, kx = tap - ky * 3;
-            const bool s1 = c0 >= p.ca0;
-            const __bf16* base = s1 ? p.a1 : p.a0;
-            const int ld = s1 ? p.lda1 : p.lda0;
-            const int cc = s1 ? c0 - p.ca0 : c0;
-            const int sh = p.src_xform ? 1 : 0;
-            const int HL = p.hs << sh, WL = p.ws << sh;
+            const SrcSel s = src_select(p, c0);
 #pragma unroll
             for (int i = 0; i < XI; ++i) {
-                const int iy = xoy[i] * p.stride + ky - 1;
-                const int ix = xox[i] * p.stride + kx - 1;
-                bool ok = (iy >= 0) & (iy < HL) & (ix >= 0) & (ix < WL);
-                if (p.src_xform == 2) ok = ok & (((iy | ix) & 1) == 0);
-                const int sy = iy >> sh, sx = ix >> sh;
-                const long pix = ((long)xb[i] * p.hs + sy) * p.ws + sx;
-                const __bf16* src = ok ? base + pix * ld + cc + (xks[i] << 3)
-                                       : (const __bf16*)slh_zero_page;
+                const ConvTap t = conv_tap(p, xb[i], xoy[i], xox[i], ky, kx);
+                const __bf16* src = t.ok ? s.base + t.pix * s.ld + s.cc + (xks[i] << 3)
+                                         : (const __bf16*)slh_zero_page;
                 stage_copy(src, dX + (wave + NW * i) * 1024);
             }
         }
@@ -162,10 +146,7 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
         }
         if (LORA) {
             const int row = (wave & 3) * 8 + frow;   // with 8 waves the upper four re-issue the same rows (benign)
-            const __bf16* src = row < p.lora_rank
-                                    ? p.lora_down + (long)row * p.K + k0 + ((fslot ^ ((row >> 1) & 7)) << 3)
-                                    : (const __bf16*)slh_zero_page;
-            stage_copy(src, sL + buf * (32 * 128) + (wave & 3) * 1024);
+            stage_copy(lora_down_src(p, row, k0, fslot), sL + buf * (32 * 128) + (wave & 3) * 1024);
         }
     };
 
@@ -264,10 +245,8 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
         for (int i = 0; i < WI; ++i) wsrc[i] = (const char*)(wptr[i] + (long)kt_begin * wkstep);
         if (LORA) {
             const int row = (wave & 3) * 8 + frow;
-            const bool ok = row < p.lora_rank;
-            lsrc = ok ? (const char*)(p.lora_down + (long)row * p.K + kt_begin * BK + ((fslot ^ ((row >> 1) & 7)) << 3))
-                      : (const char*)slh_zero_page;
-            ladv = ok ? 128 : 0;
+            lsrc = (const char*)lora_down_src(p, row, kt_begin * BK, fslot);
+            ladv = row < p.lora_rank ? 128 : 0;
         }
         // K tile the next issue belongs to (relative to this workgroup's K slice); its channel offset / filter tap
         int i_kt = 0, i_c0 = kt_begin * BK, i_tap = 0;
@@ -278,30 +257,20 @@ __global__ __launch_bounds__(128 * WM, gemm_waves_per_simd(MI, NI, STAGES, LORA,
 
         // (re)base the X pointers of the tile at (i_tap, i_c0); called when a tap or a concat source begins
         auto rebase_x = [&]() {
-            const bool s1 = i_c0 >= p.ca0;
-            const __bf16* base = s1 ? p.a1 : p.a0;
-            const int cc = s1 ? i_c0 - p.ca0 : i_c0;
+            const SrcSel s = src_select(p, i_c0);
             if (MODE == 0) {
 #pragma unroll
                 for (int i = 0; i < XI; ++i) {
-                    xsrc[i] = (const char*)(base + (s1 ? xrow_off1[i] : xrow_off0[i]) + cc + (xks[i] << 3));
+                    xsrc[i] = (const char*)(s.base + (s.second ? xrow_off1[i] : xrow_off0[i]) + s.cc + (xks[i] << 3));
                     xadv[i] = 128;
                 }
             } else {
-                const int ld = s1 ? p.lda1 : p.lda0;
                 const int ky = i_tap / 3, kx = i_tap - ky * 3;
-                const int sh = p.src_xform ? 1 : 0;
-                const int HL = p.hs << sh, WL = p.ws << sh;
 #pragma unroll
                 for (int i = 0; i < XI; ++i) {
-                    const int iy = xoy[i] * p.stride + ky - 1;
-                    const int ix = xox[i] * p.stride + kx - 1;
-                    bool ok = (iy >= 0) & (iy < HL) & (ix >= 0) & (ix < WL);
-                    if (p.src_xform == 2) ok = ok & (((iy | ix) & 1) == 0);
-                    const int sy = iy >> sh, sx = ix >> sh;
-                    const long pix = ((long)xb[i] * p.hs + sy) * p.ws + sx;
-                    xsrc[i] = ok ? (const char*)(base + pix * ld + cc + (xks[i] << 3)) : (const char*)slh_zero_page;
-                    xadv[i] = ok ? 128 : 0;
+                    const ConvTap t = conv_tap(p, xb[i], xoy[i], xox[i], ky, kx);
+                    xsrc[i] = t.ok ? (const char*)(s.base + t.pix * s.ld + s.cc + (xks[i] << 3)) : (const char*)slh_zero_page;
+                    xadv[i] = t.ok ? 128 : 0;
                 }
             }
         };

@@ -89,9 +89,9 @@ __global__ __launch_bounds__(256) void gemm5_kernel(const G5Args p) {
     for (int i = 0; i < G5_WI; ++i) {
         int pc = wave + 4 * i + wrot;
         pc = pc >= 20 ? pc - 20 : pc;
-        const int n = n0 + pc * 8 + frow;       // (the swizzle key of a packed row has period 16: a tile may start at row 0 / 32 of a block)
+        const int n = n0 + pc * 8 + frow;
         wdst[i] = pc * 1024;
-        wsrc[i] = (const char*)(p.w + ((long)(n >> 6) * (p.K >> 6)) * 4096 + ((n & 63) << 6) + (fslot << 3));
+        wsrc[i] = (const char*)w_row_src_packed(p, n, fslot);
     }
     // fused adapter: wave 3 stages one more piece per K tile, rows 160-167 of the W tile = lora_down[0..3][k tile] + 4 zero rows (its
     // counted waits are one piece deeper: `extra`, wave-uniform)

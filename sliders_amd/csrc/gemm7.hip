@@ -112,7 +112,7 @@ __global__ __launch_bounds__(512) void gemm7_kernel(const G7Args p) {
             int pc = lw + 4 * i;
             pc = pc < 2 * WB ? pc : 2 * WB - 1;      // (the slot past the end belongs to loaders < WREM only; the others never issue it)
             const int n = n0 + pc * 16 + frow;
-            wsrc[i] = (const char*)(p.w + ((long)(n >> 6) * (p.K >> 6)) * 4096 + ((n & 63) << 6) + ((fsl ^ ((n >> 1) & 7)) << 3));
+            wsrc[i] = (const char*)w_row_src_packed(p, n, fsl ^ ((n >> 1) & 7));
         }
         // second half of a packed 128-byte row: 64 bytes up or down, by bit 2 of the row's key = bit 3 of the row (tiles start at
         // multiples of 16); from the second half to the first half of the next 64-deep block: 8192 minus that

@@ -31,20 +31,6 @@
 
 using namespace slh_gemm_detail;
 
-// ablation switches for scripts/build_variant.sh builds (-DSLH8P_ABL=<bits>): 1 no LDS-DMA inside the K loop, 2 no MFMA,
-// 4 no fragment reads, 8 no stagger between the wave groups, 16 no priority raise around the MFMAs.  0 in the product build.
-#ifndef SLH8P_ABL
-#define SLH8P_ABL 0
-#endif
-// schedule variants: 1 = half of the waves issue the phase's LDS-DMA ahead of its fragment reads (LDS and the load path busy
-// at the same time), 2 = the LDS-DMA pieces ride in the shadow of the MFMAs, 4 = linear X source (timing only, wrong results)
-#ifndef SLH8P_VAR
-#define SLH8P_VAR 0
-#endif
-#ifndef SLH8P_VM
-#define SLH8P_VM ((SLH8P_VAR & 2) ? 6 : 8)   /* VAR 8 implies 2 */
-#endif
-
 namespace {
 
 template <int MODE, bool LORA>
@@ -90,9 +76,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
         const int row = wrow0 + WOFF[a] + frow;
         int n = n0 + row;
         n = n < p.N ? n : p.N - 1;
-        const __bf16* wp = p.w_packed ? p.w + ((long)(n >> 6) * (p.K >> 6)) * 4096 + ((n & 63) << 6) + (fslot << 3)
-                                      : p.w + (long)n * p.ldw + ((fslot ^ ((row >> 1) & 7)) << 3);
-        wsrc[a] = (const char*)(wp + (long)kt_begin * wkstep);
+        wsrc[a] = (const char*)(w_row_src(p, n, row, fslot) + (long)kt_begin * wkstep);
     }
     int wkbytes = wkstep * 2;
 
@@ -108,23 +92,18 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
     bool i_first = true;
     int x_left = nk, w_left = nk;          // K tiles whose X / W units have not been issued yet
     auto rebase_x = [&]() {
-        const bool s1 = i_c0 >= p.ca0;
-        const __bf16* base = s1 ? p.a1 : p.a0;
-        const int cc = s1 ? i_c0 - p.ca0 : i_c0;
+        const SrcSel s = src_select(p, i_c0);
         if (MODE == 0) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const int row = xrow0 + XOFF[a] + frow;
                 int m = m0 + row;
                 m = m < p.M ? m : p.M - 1;
-                xsrc[a] = (const char*)(base + (long)m * (s1 ? p.lda1 : p.lda0) + cc + (((SLH8P_VAR & 4) ? fslot : (fslot ^ ((row >> 1) & 7))) << 3));
+                xsrc[a] = (const char*)(s.base + (long)m * s.ld + s.cc + ((fslot ^ ((row >> 1) & 7)) << 3));
             }
             xmove = 15;
         } else {
-            const int ld = s1 ? p.lda1 : p.lda0;
             const int ky = i_tap / 3, kx = i_tap - ky * 3;
-            const int sh = p.src_xform ? 1 : 0;
-            const int HL = p.hs << sh, WL = p.ws << sh;
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const int row = xrow0 + XOFF[a] + frow;
@@ -132,27 +111,14 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
                 // registers through the K loop
                 int m = m0 + row;
                 m = m < p.M ? m : p.M - 1;
-                const int hw = p.ho * p.wo;
-                const int xb_a = m / hw;
-                const int rem = m - xb_a * hw;
-                const int xoy_a = rem / p.wo, xox_a = rem - xoy_a * p.wo;
-                const int iy = xoy_a * p.stride + ky - 1;
-                const int ix = xox_a * p.stride + kx - 1;
-                bool ok = (iy >= 0) & (iy < HL) & (ix >= 0) & (ix < WL);
-                if (p.src_xform == 2) ok = ok & (((iy | ix) & 1) == 0);
-                const int sy = iy >> sh, sx = ix >> sh;
-                const long pix = ((long)xb_a * p.hs + sy) * p.ws + sx;
-                xsrc[a] = ok ? (const char*)(base + pix * ld + cc + ((fslot ^ ((row >> 1) & 7)) << 3)) : zero_page;
-                xmove = ok ? (xmove | (1u << a)) : (xmove & ~(1u << a));
+                const RowPixel px = pixel_of_row(m, p.ho, p.wo);
+                const ConvTap t = conv_tap(p, px.b, px.oy, px.ox, ky, kx);
+                xsrc[a] = t.ok ? (const char*)(s.base + t.pix * s.ld + s.cc + ((fslot ^ ((row >> 1) & 7)) << 3)) : zero_page;
+                xmove = t.ok ? (xmove | (1u << a)) : (xmove & ~(1u << a));
             }
         }
     };
     const unsigned lds0 = lds_addr_of(smem);
-    bool in_loop = false;
-    auto dma = [&](const void* src, const unsigned dst) {
-        if ((SLH8P_ABL & 1) && in_loop) return;
-        glds16_hidden(src, dst);
-    };
     // LDS byte address (wave-uniform) of this wave's 8-row group `a` of operand X / W in the buffer at byte offset `bo`
     auto x_dst = [&](const unsigned bo, const int a) { return lds0 + bo + (xrow0 + XOFF[a]) * 128; };
     auto w_dst = [&](const unsigned bo, const int a) { return lds0 + bo + XB + (wrow0 + WOFF[a]) * 128; };
@@ -180,21 +146,21 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
         }
     };
     auto unit_piece = [&](const int u, const int k, const unsigned bo) {
-        if (u == 1) dma(xsrc[k], x_dst(bo, k));
-        else if (u == 4) dma(xsrc[2 + k], x_dst(bo, 2 + k));
-        else if (u == 2) dma(wsrc[k], w_dst(bo, k));
-        else dma(wsrc[2 + k], w_dst(bo, 2 + k));
+        if (u == 1) glds16_hidden(xsrc[k], x_dst(bo, k));
+        else if (u == 4) glds16_hidden(xsrc[2 + k], x_dst(bo, 2 + k));
+        else if (u == 2) glds16_hidden(wsrc[k], w_dst(bo, k));
+        else glds16_hidden(wsrc[2 + k], w_dst(bo, 2 + k));
     };
     auto unit_end = [&](const int u) {
         if (u == 4) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) xsrc[a] += (SLH8P_ABL & 32) ? 0 : (int)((xmove >> a) & 1) << 7;     // ABL 32: every K tile re-reads the first one (L2-hit rate of the DMA path)
+            for (int a = 0; a < 4; ++a) xsrc[a] += (int)((xmove >> a) & 1) << 7;
             i_c0 += BK;
             if (MODE == 1 && i_c0 == cin) { i_c0 = 0; ++i_tap; }
             --x_left;
         } else if (u == 3) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) wsrc[a] += (SLH8P_ABL & 32) ? 0 : wkbytes;
+            for (int a = 0; a < 4; ++a) wsrc[a] += wkbytes;
             --w_left;
         }
     };
@@ -242,7 +208,6 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
 
     bf16x8 xf[2][4], wf[2][4];      // X: the two row blocks of the current half x 4 k-steps; W: both column blocks x 4 k-steps
     auto read_x = [&](const unsigned bo, const int half) {
-        if (SLH8P_ABL & 4) return;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -250,41 +215,18 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
                 xf[b][ks] = *(const bf16x8*)(xbase + bo + (half * 2 + b) * 4096 + lds_off(lrow, ks * 2 + lhi));
     };
     auto read_w = [&](const unsigned bo, const int j) {
-        if (SLH8P_ABL & 4) return;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) wf[j][ks] = *(const bf16x8*)(wbase + bo + j * 4096 + lds_off(lrow, ks * 2 + lhi));
     };
-    // the 8 MFMAs of a quadrant; with SLH8P_VAR & 2 the two LDS-DMA pieces of unit `u` go out in their shadow
-    auto mfmas = [&](const int half, const int j, const int u, const unsigned ubo) {
-        if (!(SLH8P_ABL & 16)) __builtin_amdgcn_s_setprio(1);
-        if (SLH8P_VAR & 2) unit_begin(u);
+    // the 8 MFMAs of a quadrant
+    auto mfmas = [&](const int half, const int j) {
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                if (SLH8P_ABL & 2) asm volatile("" ::"v"(wf[j][ks]), "v"(xf[b][ks]));
-                else if (SLH8P_VAR & 16) {
-                    // timing experiment (wrong numbers): the same operand registers and FLOPs as two 16x16x32 MFMAs, whose
-                    // accumulator traffic per FLOP is half that of 32x32x16
-                    f32x16& A = acc[half * 2 + b][j];
-                    f32x4 q0 = {A[ks * 4], A[ks * 4 + 1], A[ks * 4 + 2], A[ks * 4 + 3]};
-                    f32x4 q1 = {A[(ks ^ 2) * 4], A[(ks ^ 2) * 4 + 1], A[(ks ^ 2) * 4 + 2], A[(ks ^ 2) * 4 + 3]};
-                    q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][ks], xf[b][ks], q0, 0, 0, 0);
-                    q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][ks], xf[b][ks], q1, 0, 0, 0);
-                    A[ks * 4] = q0[0]; A[ks * 4 + 1] = q0[1]; A[ks * 4 + 2] = q0[2]; A[ks * 4 + 3] = q0[3];
-                    A[(ks ^ 2) * 4] = q1[0]; A[(ks ^ 2) * 4 + 1] = q1[1]; A[(ks ^ 2) * 4 + 2] = q1[2]; A[(ks ^ 2) * 4 + 3] = q1[3];
-                }
-                else acc[half * 2 + b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][ks], xf[b][ks], acc[half * 2 + b][j], 0, 0, 0);
-                if ((SLH8P_VAR & 8) ? (wc == ((ks * 2 + b) & 3)) : ((SLH8P_VAR & 2) && b == 1 && (ks == 0 || ks == 2))) {
-                    // (VAR 8: wave wc issues behind MFMA wc and wc + 4 - the four waves of the group, which run in lockstep on
-                    // four SIMDs, hand the load path one piece per 32-cycle MFMA slot instead of a burst of four)
-                    __builtin_amdgcn_sched_barrier(0);
-                    unit_piece(u, (SLH8P_VAR & 8) ? ks >> 1 : ks >> 1, ubo);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        if (SLH8P_VAR & 2) unit_end(u);
-        if (!(SLH8P_ABL & 16)) __builtin_amdgcn_s_setprio(0);
+            for (int b = 0; b < 2; ++b)
+                acc[half * 2 + b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][ks], xf[b][ks], acc[half * 2 + b][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
     };
     // the barrier pair of a phase: [reads / DMA issued above] -> barrier -> fragments landed -> MFMAs -> barrier
 #define SLH_PHASE_MID()                              \
@@ -296,28 +238,16 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
     __builtin_amdgcn_sched_barrier(0);               \
     __builtin_amdgcn_s_barrier();                    \
     __builtin_amdgcn_sched_barrier(0)
-#define SLH_VMWAIT() asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SLH8P_VM) : "memory")
+#define SLH_VMWAIT() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
 
     __builtin_amdgcn_s_barrier();                 // every wave's share of U1(0), U2(0) has landed
-    if (!(SLH8P_ABL & 8) && grp == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0 from here on
+    if (grp == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0 from here on
 
-    in_loop = true;
-    const bool dma_first = (SLH8P_VAR & 1) && wc >= 2;   // half of the waves issue their LDS-DMA ahead of the fragment reads
-    // read half of a phase: the fragment reads `rd` and (unless it rides in the MFMA shadow) unit u into the buffer at ubo
+    // read half of a phase: the fragment reads `rd`, then unit u into the buffer at ubo
     auto read_half = [&](auto rd, const int u, const unsigned ubo, const bool wait) {
-        if (SLH8P_VAR & 2) {
-            rd();
-            __builtin_amdgcn_sched_barrier(0);
-        } else if (dma_first) {
-            issue_unit(u, ubo);
-            __builtin_amdgcn_sched_barrier(0);
-            rd();
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            rd();
-            __builtin_amdgcn_sched_barrier(0);
-            issue_unit(u, ubo);
-        }
+        rd();
+        __builtin_amdgcn_sched_barrier(0);
+        issue_unit(u, ubo);
         if (wait) SLH_VMWAIT();
     };
     unsigned bo = 0;                              // byte offset of the current K tile's buffer
@@ -326,27 +256,27 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs p) {
         // phase 1: quadrant (row blocks 0-1, column block 0); U3(s+1); wait: U3(s) landed (read in phase 2)
         read_half([&]() { read_x(bo, 0); read_w(bo, 0); }, 3, nb, true);
         SLH_PHASE_MID();
-        mfmas(0, 0, 3, nb);
+        mfmas(0, 0);
         SLH_PHASE_END();
         // phase 2: (row blocks 0-1, column block 1); U4(s+1); wait: U4(s) landed (read in phase 3)
         read_half([&]() { read_w(bo, 1); }, 4, nb, true);
         SLH_PHASE_MID();
-        mfmas(0, 1, 4, nb);
+        mfmas(0, 1);
         SLH_PHASE_END();
         // phase 3: (row blocks 2-3, column block 1); U1(s+2) into the rows last read in phase 1
         read_half([&]() { read_x(bo, 1); }, 1, bo, false);
         SLH_PHASE_MID();
-        mfmas(1, 1, 1, bo);
+        mfmas(1, 1);
         SLH_PHASE_END();
         // phase 4: (row blocks 2-3, column block 0); U2(s+2); wait: U1(s+1), U2(s+1) landed (read in phase 1 of the next tile)
         read_half([&]() {}, 2, bo, true);
         SLH_PHASE_MID();
-        mfmas(1, 0, 2, bo);
+        mfmas(1, 0);
         SLH_PHASE_END();
         bo = nb;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-page units of the two tiles past the end: landed before the epilogue recycles the buffers
-    if (!(SLH8P_ABL & 8) && grp == 0) __builtin_amdgcn_s_barrier();        // re-align the groups
+    if (grp == 0) __builtin_amdgcn_s_barrier();        // re-align the groups
     __builtin_amdgcn_s_barrier();
 #undef SLH_PHASE_MID
 #undef SLH_PHASE_END
@@ -410,11 +340,8 @@ __global__ __launch_bounds__(512, 2) void gemm8pb_kernel(const GemmArgs p) {
         for (int a = 0; a < XG; ++a) {
             int m = m0 + xrow0 + a * 64 + frow;
             m = m < p.M ? m : p.M - 1;
-            const int hw = p.ho * p.wo;
-            const int b = m / hw;
-            const int rem = m - b * hw;
-            const int oy = rem / p.wo;
-            xb[a] = b; xoy[a] = oy; xox[a] = rem - oy * p.wo;
+            const RowPixel px = pixel_of_row(m, p.ho, p.wo);
+            xb[a] = px.b; xoy[a] = px.oy; xox[a] = px.ox;
         }
     }
     const int wkstep = p.w_packed ? 4096 : BK;
@@ -424,9 +351,7 @@ __global__ __launch_bounds__(512, 2) void gemm8pb_kernel(const GemmArgs p) {
         const int row = wrow0 + j * 32 + frow;
         int n = n0 + row;
         n = n < p.N ? n : p.N - 1;
-        const __bf16* wp = p.w_packed ? p.w + ((long)(n >> 6) * (p.K >> 6)) * 4096 + ((n & 63) << 6) + (fslot << 3)
-                                      : p.w + (long)n * p.ldw + ((fslot ^ ((row >> 1) & 7)) << 3);
-        wsrc[j] = (const char*)(wp + (long)kt_begin * wkstep);
+        wsrc[j] = (const char*)(w_row_src(p, n, row, fslot) + (long)kt_begin * wkstep);
     }
     int wkbytes = wkstep * 2;
     const char* lsrc = nullptr;
@@ -438,42 +363,31 @@ __global__ __launch_bounds__(512, 2) void gemm8pb_kernel(const GemmArgs p) {
     int i_c0 = kt_begin * BK, i_tap = 0;
     if (LORA) {
         const int row = (wave & 3) * 8 + frow;       // waves 4-7 re-issue the rows of waves 0-3 (same bytes, same place: benign)
-        const bool ok = row < p.lora_rank;
-        lsrc = ok ? (const char*)(p.lora_down + (long)row * p.K + kt_begin * BK + ((fslot ^ ((row >> 1) & 7)) << 3)) : zero_page;
-        ladv = ok ? 128 : 0;
+        lsrc = (const char*)lora_down_src(p, row, kt_begin * BK, fslot);
+        ladv = row < p.lora_rank ? 128 : 0;
     }
     if (MODE == 1) { i_tap = i_c0 / cin; i_c0 -= i_tap * cin; }
     bool i_first = true;
     int x_left = nk, w_left = nk;
     auto rebase_x = [&]() {
-        const bool s1 = i_c0 >= p.ca0;
-        const __bf16* base = s1 ? p.a1 : p.a0;
-        const int cc = s1 ? i_c0 - p.ca0 : i_c0;
+        const SrcSel s = src_select(p, i_c0);
         if (MODE == 0) {
 #pragma unroll
             for (int a = 0; a < XG; ++a) {
                 const int row = xrow0 + a * 64 + frow;
                 int m = m0 + row;
                 m = m < p.M ? m : p.M - 1;
-                xsrc[a] = (const char*)(base + (long)m * (s1 ? p.lda1 : p.lda0) + cc + ((fslot ^ ((row >> 1) & 7)) << 3));
+                xsrc[a] = (const char*)(s.base + (long)m * s.ld + s.cc + ((fslot ^ ((row >> 1) & 7)) << 3));
                 xadv[a] = 128;
             }
         } else {
-            const int ld = s1 ? p.lda1 : p.lda0;
             const int ky = i_tap / 3, kx = i_tap - ky * 3;
-            const int sh = p.src_xform ? 1 : 0;
-            const int HL = p.hs << sh, WL = p.ws << sh;
 #pragma unroll
             for (int a = 0; a < XG; ++a) {
                 const int row = xrow0 + a * 64 + frow;
-                const int iy = xoy[a] * p.stride + ky - 1;
-                const int ix = xox[a] * p.stride + kx - 1;
-                bool ok = (iy >= 0) & (iy < HL) & (ix >= 0) & (ix < WL);
-                if (p.src_xform == 2) ok = ok & (((iy | ix) & 1) == 0);
-                const int sy = iy >> sh, sx = ix >> sh;
-                const long pix = ((long)xb[a] * p.hs + sy) * p.ws + sx;
-                xsrc[a] = ok ? (const char*)(base + pix * ld + cc + ((fslot ^ ((row >> 1) & 7)) << 3)) : zero_page;
-                xadv[a] = ok ? 128 : 0;
+                const ConvTap t = conv_tap(p, xb[a], xoy[a], xox[a], ky, kx);
+                xsrc[a] = t.ok ? (const char*)(s.base + t.pix * s.ld + s.cc + ((fslot ^ ((row >> 1) & 7)) << 3)) : zero_page;
+                xadv[a] = t.ok ? 128 : 0;
             }
         }
     };

@@ -1,7 +1,7 @@
 // Shared device code of the bf16 MFMA GEMM kernels (gemm.hip: 2-slot / ring K loops; gemm8p.hip: 256 x 256 ping-pong K loop):
 // argument block, LDS swizzle, XCD-aware tile mapping, the folded-LayerNorm prologue and the fused epilogue.  gfx950 only.
 #pragma once
-#include "common.h"
+#include "addressing.h"
 #include <cstdint>
 #include <type_traits>
 #include "../../include/sliders_hip.h"
@@ -40,11 +40,6 @@ struct GemmArgs {
 };
 
 constexpr int BK = 64;
-
-// swizzled byte offset of (row, 16-byte slot) inside a [rows][64] bf16 LDS tile
-__device__ __forceinline__ int lds_off(int row, int slot) {
-    return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
-}
 
 // ---- XCD-aware tile mapping: block b runs on XCD b%8 (own 4 MB L2); give each XCD a contiguous chunk of a
 // grouped tile sequence: groups of group_m consecutive m-tiles, inside a group m fastest, then n.  The host

@@ -5,7 +5,7 @@
 //   slh_skinny : T[M][R]   = A[M][K] . Wd[R][K]^T          (lora_down(x); also conv_out 320->4)
 //   slh_gemv   : y[nb][N]  = x[nb][K] . W[N][K]^T + ...     (TimestepEmbedding, time_emb_proj batch)
 //   slh_lora_wgrad : dW[C][R] += s * sum_m Z[m][c] V[m][r]  (LoRA up / down weight gradients)
-#include "common.h"
+#include "addressing.h"
 #include "../../include/sliders_hip.h"
 
 namespace {
@@ -79,6 +79,8 @@ __global__ __launch_bounds__(256) void skinny_kernel(AddrArgs A, const __bf16* _
             cur = nxt;
         }
     } else {
+        // (the one site that keeps its own statement of addressing.h's pixel_of_row / conv_tap / src_select: through the helpers
+        // the conv_out launch of an SDXL pass measured 56.2 us against 53.5)
         const int hw = A.ho * A.wo;
         const int b = mm / hw;
         const int rem = mm - b * hw;
@@ -224,27 +226,18 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p, const int bx, con
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[e][r] = 0.f;
     const int voff = p.vgroup_cols > 0 ? 4 * (c / p.vgroup_cols) : 0;
-    const int sh = p.A.src_xform ? 1 : 0;
-    const int HL = p.A.hs << sh, WL = p.A.ws << sh;
     const int ky = tap / 3, kx = tap - ky * 3;
-    const int hw = p.A.ho * p.A.wo;
+    const SrcSel zs = src_select(p.A, c);      // the source that holds this thread's 8 channels
     if (cvalid) {
         for (int m = m_begin + ry; m < m_end; m += 8) {
-            const __bf16* src;
-            if (p.A.mode == 0) {
-                src = c < p.A.ca0 ? p.A.a0 + (long)m * p.A.lda0 + c : p.A.a1 + (long)m * p.A.lda1 + (c - p.A.ca0);
-            } else {
-                const int b = m / hw;
-                const int rem = m - b * hw;
-                const int oy = rem / p.A.wo, ox = rem - oy * p.A.wo;
-                const int iy = oy * p.A.stride + ky - 1, ix = ox * p.A.stride + kx - 1;
-                bool ok = (iy >= 0) & (iy < HL) & (ix >= 0) & (ix < WL);
-                if (p.A.src_xform == 2) ok = ok & (((iy | ix) & 1) == 0);
-                if (!ok) continue;
-                const long pix = ((long)b * p.A.hs + (iy >> sh)) * p.A.ws + (ix >> sh);
-                src = c < p.A.ca0 ? p.A.a0 + pix * p.A.lda0 + c : p.A.a1 + pix * p.A.lda1 + (c - p.A.ca0);
+            long pix = m;
+            if (p.A.mode != 0) {
+                const RowPixel px = pixel_of_row(m, p.A.ho, p.A.wo);
+                const ConvTap t = conv_tap(p.A, px.b, px.oy, px.ox, ky, kx);
+                if (!t.ok) continue;
+                pix = t.pix;
             }
-            const bf16x8 z = *(const bf16x8*)src;
+            const bf16x8 z = *(const bf16x8*)(zs.base + pix * zs.ld + zs.cc);
             float vv[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) vv[r] = p.v[(long)m * p.ldv + voff + r];
@@ -357,26 +350,21 @@ __host__ __device__ inline WgradGeom wgrad_geom(int C, int M, int mode, int kind
     return g;
 }
 
+__host__ __device__ inline void fill_addr(AddrArgs& A, const void* a0, const void* a1, int lda0, int lda1, int ca0, int ca1, int mode,
+                                         int hs, int ws, int src_xform, int stride, int ho, int wo) {
+    A.a0 = (const __bf16*)a0; A.a1 = (const __bf16*)a1;
+    A.lda0 = lda0; A.lda1 = lda1; A.ca0 = ca0; A.ca1 = ca1; A.mode = mode;
+    A.hs = hs; A.ws = ws; A.src_xform = src_xform; A.stride = stride; A.ho = ho; A.wo = wo;
+}
+
 __host__ __device__ inline void wgrad_args(WgradArgs& p, const slh_wgrad_desc& d) {
-    p.A.a0 = (const __bf16*)d.z0; p.A.a1 = (const __bf16*)d.z1;
-    p.A.lda0 = d.ldz0; p.A.lda1 = d.ldz1; p.A.ca0 = d.c0; p.A.ca1 = d.c1; p.A.mode = d.mode;
-    p.A.hs = d.hs; p.A.ws = d.ws; p.A.src_xform = d.src_xform; p.A.stride = d.stride; p.A.ho = d.ho; p.A.wo = d.wo;
+    fill_addr(p.A, d.z0, d.z1, d.ldz0, d.ldz1, d.c0, d.c1, d.mode, d.hs, d.ws, d.src_xform, d.stride, d.ho, d.wo);
     p.v = d.v; p.out = d.out; p.scale = d.scale;
     p.M = d.M; p.R = d.R; p.ldv = d.ldv; p.ldo = d.ldo;
     p.rmajor = d.out_rmajor;
     p.vgroup_cols = d.vgroup_cols;
     p.ws = d.slabs; p.ticket = (unsigned*)d.tickets;
     p.rows_per_block = wgrad_geom(d.c0 + d.c1, d.M, d.mode, d.slabs ? 1 : 0).rows_per_block;
-}
-
-// problem of workgroup `bid`: the last index with prefix[index] <= bid (prefix[0] = 0, prefix[n] = total > bid)
-__device__ __forceinline__ int batch_find(const int* prefix, int n, int bid) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= bid) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // ws / ticket: the batch's workspace (one slab per workgroup, one ticket per workgroup id - a column block uses the ticket at
@@ -398,14 +386,6 @@ __global__ __launch_bounds__(256) void wgrad_batch_kernel(const slh_wgrad_desc* 
 }
 
 }  // namespace
-
-static int fill_addr(AddrArgs& A, const void* a0, const void* a1, int lda0, int lda1, int ca0, int ca1, int mode,
-                     int hs, int ws, int src_xform, int stride, int ho, int wo) {
-    A.a0 = (const __bf16*)a0; A.a1 = (const __bf16*)a1;
-    A.lda0 = lda0; A.lda1 = lda1; A.ca0 = ca0; A.ca1 = ca1; A.mode = mode;
-    A.hs = hs; A.ws = ws; A.src_xform = src_xform; A.stride = stride; A.ho = ho; A.wo = wo;
-    return 0;
-}
 
 // The one place that decides which skinny_kernel<RMAX, LPR> runs a descriptor: slh_skinny launches what this returns and
 // slh_skinny_kernel_name names it through the same launch statements.  RMAX: accumulator rows compiled in (rows past R are masked);

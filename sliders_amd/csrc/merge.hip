@@ -24,11 +24,7 @@ __device__ __forceinline__ long merge_slot_off(const slh_lora_merge_item& it, in
 
 __global__ __launch_bounds__(256) void lora_merge_kernel(const slh_lora_merge_item* items, const int32_t* prefix, int n_items) {
     const int bid = blockIdx.x;
-    int lo = 0, hi = n_items;                   // prefix[lo] <= bid < prefix[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= bid) lo = mid; else hi = mid;
-    }
+    const int lo = batch_find(prefix, n_items, bid);
     const slh_lora_merge_item it = items[lo];
     const int row0 = (bid - prefix[lo]) * 64;   // first row of this workgroup, relative to the item
     const int tid = threadIdx.x;
