@@ -74,7 +74,7 @@ eng.set_lora(True, 1.0)
 sp = tr._step_programs(p)
 sp.capture_all()
 for n in (33, 33):
-    tr._load_latents(p, noise.to(torch.bfloat16))
+    sp.drv.load_latents(noise)
     torch.cuda.synchronize()
     t0 = time.time()
     for i in range(n):

@@ -39,7 +39,9 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import lib
 from .ddim import DDIMSchedule
+from .passes import Pass
 from .sampler import SliderSampler
 from .vae import VaeDecoder
 
@@ -422,32 +424,17 @@ class SliderEditor(SliderSampler):
             raise ValueError(f"SliderEditor: scheduler {scheduler!r}: the DDPM noise space is defined on the DDIM grid")
         super().__init__(engine, store, decoder, prediction_type, "ddim", scheduler_seed, sliders)
 
-    def _load_inputs(self, bs: int, h: int, w: int, ctx, pooled, time_ids, attn_maps=None):
-        """the plan of this shape with its conditioning inputs written (the lines SliderSampler.sample_latents starts with);
-        attn_maps: the plan of the shape that also records attention maps (UNetEngine.plan)"""
-        eng = self.eng
-        p = eng.plan(2 * bs, h, w, "on" if self.store is not None else "off", attn_maps=attn_maps)
-        io = p.io
-        io["ctx"].tensor.copy_(ctx.to(torch.bfloat16))
-        if eng.cfg.is_xl:
-            if time_ids is None:
-                time_ids = torch.tensor([[h * 8.0, w * 8.0, 0.0, 0.0, h * 8.0, w * 8.0]] * (2 * bs))
-            io["time_ids"].tensor.copy_(time_ids.to(device=eng.device, dtype=torch.float32).reshape(2 * bs, 6))
-            io["add_in"].tensor[:, : eng.cfg.pooled_dim].copy_(pooled.to(torch.bfloat16))
-        return p
-
-    def _edit_program(self, p, i: int, t: int, scale: float, start_noise: float):
-        """SliderSampler._program, except that a multiplier of 0 means the inversion's program: at scale 0 nothing is merged, sliders
-        held at a fixed scale included (they belong to the edit, and scale 0 is the reconstruction)."""
-        if float(scale) == 0.0:
-            return p.prog if i == 0 or p.prog_text_cached is None else p.prog_text_cached
-        return self._program(p, i, t, scale, start_noise)
+    def _pass(self, bs: int, h: int, w: int, ctx, pooled, time_ids, attn_maps=None) -> Pass:
+        """the CFG-pair plan of this shape with its conditioning written; attn_maps: the plan of the shape that also records attention
+        maps (UNetEngine.plan)"""
+        drv = Pass(self.eng, self.eng.plan(2 * bs, h, w, "on" if self.store is not None else "off", attn_maps=attn_maps))
+        drv.load_cond(ctx, pooled, time_ids)
+        return drv
 
     def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None):
         """The step's one element-wise launch after the UNet pass, src -> dst (fp32, may be one tensor) and the bf16 halves of `sample`:
         slh_ddpm_edit_step - mode 0 with a target (resid_i written), else mode 1 (resid_i read) - or, with a mask, slh_ddpm_edit_blend
         against keep"""
-        from . import lib
         io, bs, chw = p.io, src.shape[0], src[0].numel()
         smp = io["sample"]
         common = dict(eps=io["eps"].ptr, x=src.data_ptr(), resid=resid_i.data_ptr(), out=dst.data_ptr(), out_bf16=smp.ptr,
@@ -462,31 +449,22 @@ class SliderEditor(SliderSampler):
             d = lib.DdpmEditBlendDesc(keep=keep.data_ptr(), mask=mask.data_ptr(), hw=chw // src.shape[1], **common)
             lib.call(lib.OP_DDPM_EDIT_BLEND, d, s)
 
-    def _chain(self, p, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None, record=None, keep=None, mask=None):
+    def _chain(self, drv: Pass, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None, record=None, keep=None,
+               mask=None):
         """x (fp32) through the grid; returns the final latent.  path given = invert (resid written), else edit (resid read).
         record None: x is updated in place.  record [len(ts)][bs][4][h][w]: the same launches, but step i reads record[i - 1] (x for
         i = 0) and writes record[i], so the chain's latents are kept (the inversion, `trajectory`).
-        mask [bs][1][h][w] with keep = the inversion's latents: every step is blended against keep[i] (in place)."""
-        eng, io = self.eng, p.io
-        bs = x.shape[0]
-        smp = io["sample"]
-        xb = x.to(torch.bfloat16)
-        smp.tensor[:bs].copy_(xb)
-        smp.tensor[bs:].copy_(xb)
+        mask [bs][1][h][w] with keep = the inversion's latents: every step is blended against keep[i] (in place).
+        The slider is the sampler's (slider_session), except that a multiplier of 0 means the inversion's pass: at scale 0 nothing is
+        merged, sliders held at a fixed scale included (they belong to the edit, and scale 0 is the reconstruction)."""
+        drv.load_latents(x)
         s = torch.cuda.current_stream().cuda_stream
-        try:
+        with self.slider_session(scale, start_noise, zero_merges=False) as gate:
             for i, t in enumerate(ts):
-                if self.store is not None:
-                    eng.set_lora(True, 0.0 if t > start_noise else float(scale))
-                io["t"].tensor.fill_(float(t))
-                self._edit_program(p, i, t, scale, start_noise).run(s)
+                drv.run(t, gate(t, i == 0), s)
                 src, dst = (x, x) if record is None else (x if i == 0 else record[i - 1], record[i])
                 target = None if path is None else (path[i + 1] if i + 1 < len(ts) else x0)
-                self._launch_step(p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask)
-        finally:
-            self._restore()
-            if self.store is not None:
-                eng.set_lora(False)
+                self._launch_step(drv.p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask)
         return x if record is None else record[-1].clone()
 
     @torch.no_grad()
@@ -500,10 +478,10 @@ class SliderEditor(SliderSampler):
         dev = self.eng.device
         x0 = x0_latents.detach().to(dev, torch.float32).contiguous()
         bs, _, h, w = x0.shape
-        p = self._load_inputs(bs, h, w, ctx, pooled, time_ids)
+        drv = self._pass(bs, h, w, ctx, pooled, time_ids)
         path = build_path(self.sched, x0, ts, seed)
         resid, visited = torch.empty_like(path), torch.empty_like(path)
-        x = self._chain(p, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0, record=visited)
+        x = self._chain(drv, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0, record=visited)
         return NoiseSpace(x0=x0, x_start=path[0].clone(), resid=resid, recon=x, timesteps=list(ts), steps=int(steps),
                           skip=steps - len(ts), eta=float(eta), guidance=float(guidance_scale),
                           prediction_type=self.sched.prediction_type, seed=int(seed), ctx=ctx.detach().clone(),
@@ -532,9 +510,9 @@ class SliderEditor(SliderSampler):
         x = space.x_start.to(dev, torch.float32).clone().contiguous()
         resid = space.resid.to(dev, torch.float32).contiguous()
         bs, _, h, w = x.shape
-        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids)
+        drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids)
         visited = torch.empty_like(resid)
-        end = self._chain(p, x, space.timesteps, space.steps, space.eta, space.guidance, 0.0, -1, resid, record=visited)
+        end = self._chain(drv, x, space.timesteps, space.steps, space.eta, space.guidance, 0.0, -1, resid, record=visited)
         if not torch.equal(end, space.recon.to(dev)):
             raise RuntimeError("trajectory: the scale-0 replay does not end on space.recon bit for bit: this NoiseSpace was not inverted "
                                "with these weights and this conditioning")
@@ -563,9 +541,9 @@ class SliderEditor(SliderSampler):
         if mask is not None:
             mask = as_mask(mask, bs, h, w).to(dev)
             visited = self.trajectory(space).visited.to(dev, torch.float32).contiguous()
-        p = self._load_inputs(bs, h, w, ctx, pooled, time_ids)
+        drv = self._pass(bs, h, w, ctx, pooled, time_ids)
         g = space.guidance if guidance_scale is None else guidance_scale
-        return self._chain(p, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask)
+        return self._chain(drv, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask)
 
     @torch.no_grad()
     def footprint(self, space: NoiseSpace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200) -> torch.Tensor:
@@ -575,31 +553,24 @@ class SliderEditor(SliderSampler):
         those levels (x_start / visited[i - 1]: the image under independent noise draws), conditioning and guidance the inversion's.
         All slider-off passes run first, then the slider is switched on once (store=: the multiplier; sliders=: one merge, full
         program on the first pass after it) for the slider-on passes: 2 * len(draws) UNet passes."""
-        from . import lib
         self._check_prediction(space)
         self._check_conditioning(space, "footprint")
         idx = footprint_draws(space.timesteps, start_noise, draws, t_min)
-        eng, dev = self.eng, self.eng.device
+        dev = self.eng.device
         visited = self.trajectory(space).visited.to(dev, torch.float32)
         x_start = space.x_start.to(dev, torch.float32)
         bs, ch, h, w = x_start.shape
-        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids)
-        io = p.io
-        smp = io["sample"]
+        drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids)
+        io = drv.io
         off = torch.empty((len(idx),) + tuple(io["eps"].tensor.shape), dtype=torch.bfloat16, device=dev)
         A = torch.empty((len(idx), bs, h, w), dtype=torch.float32, device=dev)
         s = torch.cuda.current_stream().cuda_stream
+        with self.slider_session(scale, start_noise, zero_merges=False) as gate:
+            def unet(n, i, multiplier):
+                """pass n of this call at step i of the grid; n and the multiplier choose the program as in the edit's chain"""
+                drv.load_latents(x_start if i == 0 else visited[i - 1])
+                drv.run(space.timesteps[i], gate(space.timesteps[i], n == 0, multiplier), s)
 
-        def unet(n, i, multiplier):
-            """pass n of this call at step i of the grid; n and the multiplier choose the program as in the edit's chain"""
-            xb = (x_start if i == 0 else visited[i - 1]).to(torch.bfloat16)
-            smp.tensor[:bs].copy_(xb)
-            smp.tensor[bs:].copy_(xb)
-            if self.store is not None:
-                eng.set_lora(True, float(multiplier))
-            io["t"].tensor.fill_(float(space.timesteps[i]))
-            self._edit_program(p, n, space.timesteps[i], multiplier, start_noise).run(s)
-        try:
             for j, i in enumerate(idx):
                 unet(j, i, 0.0)
                 off[j].copy_(io["eps"].tensor)
@@ -608,10 +579,6 @@ class SliderEditor(SliderSampler):
                 d = lib.EpsAbsdiffDesc(eps_a=io["eps"].ptr, eps_b=off[j].data_ptr(), out=A[j].data_ptr(), nb=bs, chw=ch * h * w, hw=h * w,
                                        guidance=float(space.guidance))
                 lib.call(lib.OP_EPS_ABSDIFF, d, s)
-        finally:
-            self._restore()
-            if self.store is not None:
-                eng.set_lora(False)
         return footprint_mean(A)
 
     @torch.no_grad()
@@ -632,27 +599,17 @@ class SliderEditor(SliderSampler):
         x_start = space.x_start.to(dev, torch.float32)
         bs, _, h, w = x_start.shape
         wt = key_weights(bs, eng.ctx_len, tokens, weights)
-        p = self._load_inputs(bs, h, w, space.ctx, space.pooled, space.time_ids, attn_maps={"max_factor": int(max_factor)})
-        io = p.io
+        drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids, attn_maps={"max_factor": int(max_factor)})
+        io = drv.io
         io["xattn_wt"].tensor.copy_(wt)
         levels = {int(k.split(".")[1]): b for k, b in io.items() if k.startswith("xattn_map.")}
-        smp = io["sample"]
         s = torch.cuda.current_stream().cuda_stream
         total = torch.zeros((bs, h, w), dtype=torch.float32, device=dev)
-        try:
+        with self.slider_session(0.0, -1, zero_merges=False) as gate:
             for n, i in enumerate(idx):
-                xb = (x_start if i == 0 else visited[i - 1]).to(torch.bfloat16)
-                smp.tensor[:bs].copy_(xb)
-                smp.tensor[bs:].copy_(xb)
-                if self.store is not None:
-                    eng.set_lora(True, 0.0)
-                io["t"].tensor.fill_(float(space.timesteps[i]))
-                self._edit_program(p, n, space.timesteps[i], 0.0, -1).run(s)
+                drv.load_latents(x_start if i == 0 else visited[i - 1])
+                drv.run(space.timesteps[i], gate(space.timesteps[i], n == 0), s)
                 total += level_mean({f: b.tensor for f, b in levels.items()}, h, w)
-        finally:
-            self._restore()
-            if self.store is not None:
-                eng.set_lora(False)
         return total / float(len(idx))
 
     @torch.no_grad()

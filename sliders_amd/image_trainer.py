@@ -55,12 +55,7 @@ class ImageSliderTrainer(SliderTrainer):
                   time_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """img_*: [bs][H*8][W*8][3] float32 in [-1,1] (VaeEncoder.preprocess); post_noise / noise: (bs,4,H,W) float32,
         shared by the two images like the reference's re-seeded generator.  Returns (loss_high, loss_low)."""
-        bs = noise.shape[0]
-        self._use(bs, noise.shape[2], noise.shape[3])
-        if time_ids is not None:
-            self.time_ids = time_ids.to(device=self.eng.device, dtype=torch.float32).reshape(2 * bs, 6)
-        if lr is not None:
-            self.lr = float(lr)
+        self._begin(noise, lr, time_ids)
         st = self.store
         coeff = self.sched.add_noise_coefficients(self.t50[k])               # scheduler.timesteps[timesteps_to], 50 steps
         t_cur = self.t1000[int(k * 1000 / self.nsteps)]

@@ -17,6 +17,8 @@ eval-scripts/clip_score.py) without the diffusers pipelines.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
+from itertools import count
 from typing import Optional
 
 import torch
@@ -26,6 +28,7 @@ from . import schedulers
 from .ddim import DDIMSchedule
 from .lora_store import LoraStore
 from .merge import SliderSet, WeightMerger
+from .passes import Pass
 from .unet import UNetEngine
 from .vae import VaeDecoder
 
@@ -78,93 +81,81 @@ class SliderSampler:
         if ctx.shape[0] not in (bs, 2 * bs):
             raise ValueError(f"sample_latents: ctx has {ctx.shape[0]} rows for {bs} noise rows: expected {2 * bs} (the CFG pair) or {bs}")
         single = ctx.shape[0] == bs
-        rows = bs if single else 2 * bs
-        mode = "on" if self.store is not None else "off"
-        p = eng.plan(rows, h, w, mode)
-        io = p.io
-        io["ctx"].tensor.copy_(ctx.to(torch.bfloat16))
-        if eng.cfg.is_xl:
-            if time_ids is None:
-                time_ids = torch.tensor([[h * 8.0, w * 8.0, 0.0, 0.0, h * 8.0, w * 8.0]] * rows)
-            io["time_ids"].tensor.copy_(time_ids.to(device=eng.device, dtype=torch.float32).reshape(rows, 6))
-            io["add_in"].tensor[:, : eng.cfg.pooled_dim].copy_(pooled.to(torch.bfloat16))
-        smp = io["sample"]
-        if not self.sched.fused:
-            return self._sample_unfused(p, noise, scale, start_noise, ddim_steps, guidance_scale, single)
-        lat = noise.to(eng.device, torch.bfloat16)
-        smp.tensor[:bs].copy_(lat)
-        if not single:
-            smp.tensor[bs:].copy_(lat)
-        s = torch.cuda.current_stream().cuda_stream
-        chw = eng.cfg.out_channels * h * w
-        half = bs * chw * 2
-        # single branch: the text half is read from the one epsilon there is and the guidance passed is 0 (guidance_scale is not
-        # read), so the combine u + 0 * (u - u) hands the step u itself
-        pair = ({"out2": 0, "eps_text": io["eps"].ptr, "guidance": 0.0} if single
-                else {"out2": smp.ptr + half, "guidance": float(guidance_scale)})
-        try:
+        p = eng.plan(ctx.shape[0], h, w, "on" if self.store is not None else "off")
+        drv = Pass(eng, p)
+        drv.load_cond(ctx, pooled, time_ids)
+        with self.slider_session(scale, start_noise) as gate:
+            if not self.sched.fused:
+                return self._sample_unfused(drv, gate, noise, ddim_steps, guidance_scale, single)
+            io, smp = p.io, p.io["sample"]
+            drv.load_latents(noise)
+            s = torch.cuda.current_stream().cuda_stream
+            chw = eng.cfg.out_channels * h * w
+            half = bs * chw * 2
+            # single branch: the text half is read from the one epsilon there is and the guidance passed is 0 (guidance_scale is not
+            # read), so the combine u + 0 * (u - u) hands the step u itself
+            pair = ({"out2": 0, "eps_text": io["eps"].ptr, "guidance": 0.0} if single
+                    else {"out2": smp.ptr + half, "guidance": float(guidance_scale)})
             for i, t in enumerate(self.sched.make_timesteps(ddim_steps)):
-                if self.store is not None:
-                    eng.set_lora(True, 0.0 if t > start_noise else float(scale))
-                io["t"].tensor.fill_(float(t))
-                self._program(p, i, t, scale, start_noise).run(s)
+                drv.run(t, gate(t, i == 0), s)
                 d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, nb=bs, chw=chw, **pair,
                                     **self.sched.step_fields(t, ddim_steps))
                 lib.call(lib.OP_CFG_DDIM, d, s)
+            return smp.tensor[:bs].clone()
+
+    @contextmanager
+    def slider_session(self, scale: float = 0.0, start_noise: float = 750, zero_merges: bool = True):
+        """The slider over the passes of one call.  Yields gate(t, first, multiplier = scale) -> first, to be called in front of every
+        pass: the slider acts at `multiplier` once t <= start_noise.  store=: the adapter multiplier of this pass (0 above start_noise).
+        sliders=: the merge when the loop crosses start_noise (all-zero scales: nothing to merge, the weights stay), which makes this
+        pass a first one - the cross-attention K/V a text-cached program reuses were projected with the weights of the pass before.
+        zero_merges = False (the editor): a multiplier of 0 is the inversion's pass and merges nothing, sliders held at a fixed scale
+        included.  However the body ends, merged weights are restored and the adapter is switched off."""
+        eng, m = self.eng, self.merger
+
+        def gate(t, first: bool, multiplier: Optional[float] = None) -> bool:
+            mult = float(scale if multiplier is None else multiplier)
+            live = not float(t) > start_noise
+            if self.store is not None:
+                eng.set_lora(True, mult if live else 0.0)
+            if m is not None and not m.merged and live and (zero_merges or mult != 0.0):
+                scales = m.sliders.scales(mult)
+                if any(v != 0.0 for v in scales):
+                    m.merge(scales)
+                    return True
+            return first
+
+        try:
+            yield gate
         finally:
-            self._restore()
-        if self.store is not None:
-            eng.set_lora(False)
-        return smp.tensor[:bs].clone()
+            if m is not None and m.merged:
+                m.restore()
+            if self.store is not None:
+                eng.set_lora(False)
 
-    def _program(self, p, i: int, t: float, scale: float, start_noise: float):
-        """The program of step i: the full pass for the first step and for the first step on newly merged weights (the cross-attention
-        K/V that prog_text_cached reuses were projected with the weights of the step before), else the one that skips the text
-        projections.  Merges the sliders when the loop crosses start_noise (all-zero scales: nothing to merge, the weights stay)."""
-        full = i == 0 or p.prog_text_cached is None
-        m = self.merger
-        if m is not None and not m.merged and not float(t) > start_noise:
-            scales = m.sliders.scales(scale)
-            if any(v != 0.0 for v in scales):
-                m.merge(scales)
-                full = True
-        return p.prog if full else p.prog_text_cached
-
-    def _restore(self):
-        if self.merger is not None and self.merger.merged:
-            self.merger.restore()
-
-    def _sample_unfused(self, p, noise, scale, start_noise, steps, guidance_scale, single=False):
-        """generate_images_sd1.py:160-185 with a tensor-op scheduler: scale_model_input -> UNet replay -> guidance combine
-        (slh_cfg_ddim, do_step = 0) -> scheduler.step on the device latents.  single: one epsilon row per sample and nothing to
-        combine; the step reads the plan's epsilon as it is (it returns new tensors, so the next replay may overwrite it)"""
-        eng, sch, io = self.eng, self.sched, p.io
+    def _sample_unfused(self, drv: Pass, gate, noise, steps, guidance_scale, single=False):
+        """generate_images_sd1.py:160-185 with a tensor-op scheduler: schedulers.denoise over the whole grid (scale_model_input ->
+        prediction -> scheduler.step on the device latents), the prediction being slider gate -> UNet replay -> guidance combine
+        (slh_cfg_ddim, do_step = 0).  single: one epsilon row per sample and nothing to combine; the step reads the plan's epsilon as
+        it is (it returns new tensors, so the next replay may overwrite it)"""
+        eng, sch, io = self.eng, self.sched, drv.io
         bs = noise.shape[0]
         s = torch.cuda.current_stream().cuda_stream
-        sch.set_timesteps(steps, device=eng.device)
+        sch.set_timesteps(steps, device=eng.device)        # init_noise_sigma is the grid's
         lat = (noise.to(eng.device, torch.float32) * sch.init_noise_sigma).to(torch.bfloat16)
         eps = io["eps"].tensor.view_as(lat) if single else torch.empty_like(lat)
-        chw = lat[0].numel()
-        try:
-            for i, t in enumerate(sch.timesteps):
-                if self.store is not None:
-                    eng.set_lora(True, 0.0 if float(t) > start_noise else float(scale))
-                x = sch.scale_model_input(lat, t)
-                io["sample"].tensor[:bs].copy_(x)
-                if not single:
-                    io["sample"].tensor[bs:].copy_(x)
-                io["t"].tensor.fill_(float(t))
-                self._program(p, i, float(t), scale, start_noise).run(s)
-                if not single:
-                    d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=0, out=eps.data_ptr(), out2=0, nb=bs, chw=chw,
-                                        guidance=float(guidance_scale), do_step=0)
-                    lib.call(lib.OP_CFG_DDIM, d, s)
-                lat = sch.step(eps, t, lat, generator=self.sched_generator).prev_sample
-        finally:
-            self._restore()
-        if self.store is not None:
-            eng.set_lora(False)
-        return lat
+        combine = lib.CfgDdimDesc(eps=io["eps"].ptr, x=0, out=eps.data_ptr(), out2=0, nb=bs, chw=lat[0].numel(),
+                                  guidance=float(guidance_scale), do_step=0)
+        step = count()
+
+        def predict(x, t):
+            drv.load_latents(x)
+            drv.run(t, gate(t, next(step) == 0), s)
+            if not single:
+                lib.call(lib.OP_CFG_DDIM, combine, s)
+            return eps
+
+        return schedulers.denoise(sch, predict, lat, steps, steps, generator=self.sched_generator, device=eng.device)
 
     @torch.no_grad()
     def generate(self, ctx, noise, **kw) -> torch.Tensor:

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from itertools import count
 from typing import Optional
 
 import os
@@ -31,6 +32,7 @@ from . import schedulers
 from .ddim import DDIMSchedule
 from .lora_store import LoraStore
 from .parallel import allreduce_sum_, world_info
+from .passes import Pass, default_time_ids
 from .unet import UNetEngine
 
 # train.optimizer values that step the flat parameter buffer with tensor ops (sliders_amd/optim.py) instead of one fused kernel
@@ -67,16 +69,15 @@ class _ShapeState:
         self.denoised, self.e_pos, self.e_neu, self.e_unc, self.e_tgt = z(), z(), z(), z(), z()
         self.chw = cfg.out_channels * H * W
         self.time_ids = None
-        if cfg.is_xl:   # [orig_h, orig_w, crop_top, crop_left, target_h, target_w], train_util.py:298-333
-            self.time_ids = torch.tensor([[H * 8.0, W * 8.0, 0.0, 0.0, H * 8.0, W * 8.0]] * (2 * bs),
-                                         dtype=torch.float32, device=dev)
+        if cfg.is_xl:
+            self.time_ids = default_time_ids(H, W, 2 * bs).to(dev)
 
 
 class _StepPrograms:
     """The fused-scheduler denoise loop of one plan, one lib.Program per step index (SliderTrainer._step_programs)."""
 
     def __init__(self, tr: "SliderTrainer", p_on, key):
-        self.key, self.tr, self.p = key, tr, p_on
+        self.key, self.tr, self.drv = key, tr, Pass(tr.eng, p_on)
         B = 2 * tr.bs
         n = len(tr.t50)
         self.t_table = torch.tensor([[float(t)] * B for t in tr.t50], dtype=torch.float32, device=tr.eng.device).reshape(n, B)
@@ -87,9 +88,9 @@ class _StepPrograms:
         pr = self.progs[i]
         if pr is not None:
             return pr
-        tr, p = self.tr, self.p
+        tr, p = self.tr, self.drv.p
         # the prompt embeddings do not change inside the loop: after the first step the text K/V are already there
-        base = p.prog if (i == 0 or p.prog_text_cached is None) else p.prog_text_cached
+        base = self.drv.program(i == 0)
         t_io = p.io["t"].ptr
         pr = lib.Program()
         patched = 0
@@ -185,37 +186,33 @@ class SliderTrainer:
         self.chw, self.time_ids = st.chw, st.time_ids
 
     # ---- helpers ------------------------------------------------------------------------------------
-    def _load_cond(self, p, ctx, pooled):
-        p.io["ctx"].tensor.copy_(ctx)
-        if self.eng.cfg.is_xl:
-            p.io["time_ids"].tensor.copy_(self.time_ids)
-            p.io["add_in"].tensor[:, : self.eng.cfg.pooled_dim].copy_(pooled)
-
-    def _load_latents(self, p, lat):
-        s = p.io["sample"].tensor
-        s[: self.bs].copy_(lat)
-        s[self.bs:].copy_(lat)
+    def _begin(self, noise, lr, time_ids):
+        """What every iteration starts with: the buffers of the noise's shape, this step's learning rate, the SDXL micro-conditioning
+        where it is not the shape's default"""
+        self._use(noise.shape[0], noise.shape[2], noise.shape[3])
+        if time_ids is not None:
+            self.time_ids = time_ids.to(device=self.eng.device, dtype=torch.float32).reshape(2 * self.bs, 6)
+        if lr is not None:
+            self.lr = float(lr)
 
     def _model_input(self, lat, t):
         """scheduler.scale_model_input (train_util.py:156, 234): identity for ddim / ddpm, 1/sqrt(sigma^2+1) for lms / euler_a"""
         return lat if self.sched.fused else self.sched.scale_model_input(lat, t)
 
-    def _denoise_unfused(self, p_on, noise, k: int):
+    def _denoise_unfused(self, drv: Pass, noise, k: int):
         """train_util.diffusion[_xl] (train_util.py:175-196 / 263-294) for the tensor-op schedulers: UNet pass and guidance
         combine are the HIP path, the scheduler step is sliders_amd/schedulers.py on the device latents.  Leaves the
         scheduler on its 1000-step grid like train_lora_xl.py:229 and returns the timestep of the four predictions."""
         sch, s = self.sched, _stream()
         eps = self.e_tgt                    # scratch: the guided prediction of this step (overwritten again in step 3)
-        first = [True]
+        step = count()
 
         def predict(model_input, t):
-            self._load_latents(p_on, model_input)
-            p_on.io["t"].tensor.fill_(float(t))
+            drv.load_latents(model_input)
             # the prompt embeddings do not change inside the loop: after the first step the text K/V are already there
-            (p_on.prog if (first[0] or p_on.prog_text_cached is None) else p_on.prog_text_cached).run(s)
-            first[0] = False
+            drv.run(t, next(step) == 0, s)
             self.unet_passes += 1
-            self._cfg(p_on, eps.data_ptr(), self.denoise_guidance)
+            self._cfg(drv.p, eps.data_ptr(), self.denoise_guidance)
             return eps
 
         lat = schedulers.denoise(sch, predict, noise.to(device=self.eng.device, dtype=torch.bfloat16), k, self.nsteps,
@@ -247,10 +244,10 @@ class SliderTrainer:
         return sp
 
     def _predict(self, p, lat, ctx, pooled, t, out):
-        self._load_latents(p, self._model_input(lat, t))
-        self._load_cond(p, ctx, pooled)
-        p.io["t"].tensor.fill_(float(t))
-        p.prog.run(_stream())
+        drv = Pass(self.eng, p)
+        drv.load_latents(self._model_input(lat, t))
+        drv.load_cond(ctx, pooled, self.time_ids)
+        drv.run(t, True, _stream())
         self.unet_passes += 1
         self._cfg(p, out.data_ptr(), 1.0)
 
@@ -262,10 +259,8 @@ class SliderTrainer:
         rounding.  Still counted as 3 denoise steps (that is what the reference executes)."""
         eng, bs = self.eng, self.bs
         p3 = eng.plan(3 * bs, self.H, self.W, "off")
-        s = p3.io["sample"].tensor
-        lat_in = self._model_input(self.denoised, t_cur)
-        for j in range(3):
-            s[j * bs:(j + 1) * bs].copy_(lat_in)
+        drv = Pass(eng, p3)
+        drv.load_latents(self._model_input(self.denoised, t_cur))
         ctx = p3.io["ctx"].tensor
         ctx[:bs].copy_(pair.ctx_uncond[:bs]); ctx[bs:2 * bs].copy_(pair.ctx_positive[bs:]); ctx[2 * bs:].copy_(pair.ctx_neutral[bs:])
         if eng.cfg.is_xl:
@@ -274,8 +269,7 @@ class SliderTrainer:
             pd = eng.cfg.pooled_dim
             ai[:bs, :pd].copy_(pair.pooled_uncond[:bs]); ai[bs:2 * bs, :pd].copy_(pair.pooled_positive[bs:])
             ai[2 * bs:, :pd].copy_(pair.pooled_neutral[bs:])
-        p3.io["t"].tensor.fill_(float(t_cur))
-        p3.prog.run(_stream())
+        drv.run(t_cur, True, _stream())
         self.unet_passes += 3
         e = p3.io["eps"].ptr
         blk = bs * self.chw * 2
@@ -294,12 +288,8 @@ class SliderTrainer:
         step = False: stop after the backward - no all-reduce, no optimizer step (the caller finishes with `reduce_and_step`;
         this is also how tests run N data-parallel ranks in one process).
         Returns the device loss scalar."""
-        self._use(noise.shape[0], noise.shape[2], noise.shape[3])
         self._mark("start")
-        if time_ids is not None:
-            self.time_ids = time_ids.to(device=self.eng.device, dtype=torch.float32).reshape(2 * self.bs, 6)
-        if lr is not None:
-            self.lr = float(lr)
+        self._begin(noise, lr, time_ids)
         eng, st, bs = self.eng, self.store, self.bs
         B = 2 * bs
         s = _stream()
@@ -307,9 +297,10 @@ class SliderTrainer:
         # 1. partial denoise with the adapters on (train_lora_xl.py:205-227)
         eng.set_lora(True, 1.0)
         p_on = eng.plan(B, self.H, self.W, "on")
-        self._load_cond(p_on, pair.ctx_target, pair.pooled_target)
+        drv = Pass(eng, p_on)
+        drv.load_cond(pair.ctx_target, pair.pooled_target, self.time_ids)
         if self.sched.fused:
-            self._load_latents(p_on, noise.to(torch.bfloat16))
+            drv.load_latents(noise)
             smp = p_on.io["sample"]
             half = bs * self.chw * 2
             sp = self._step_programs(p_on) if self.step_graphs else None
@@ -326,9 +317,7 @@ class SliderTrainer:
                         self._mark(f"step{i}")
                     continue
                 t = self.t50[i]
-                p_on.io["t"].tensor.fill_(float(t))
-                # the prompt embeddings do not change inside the loop: after the first step the text K/V are already there
-                (p_on.prog if (i == 0 or p_on.prog_text_cached is None) else p_on.prog_text_cached).run(s)
+                drv.run(t, i == 0, s)     # the prompt embeddings do not change inside the loop
                 self._cfg(p_on, smp.ptr, self.denoise_guidance, self.sched.step_fields(t, self.nsteps),
                           out2=smp.ptr + half, x=smp.ptr)
             if sp is not None:
@@ -337,7 +326,7 @@ class SliderTrainer:
             self.denoised.copy_(smp.tensor[:bs])
             t_cur = self.t1000[int(k * 1000 / self.nsteps)]
         else:
-            t_cur = self._denoise_unfused(p_on, noise, k)
+            t_cur = self._denoise_unfused(drv, noise, k)
         # 2. frozen-model predictions, adapters off (train_lora_xl.py:236-295)
         def frozen():
             if self.dedup_frozen:

@@ -18,6 +18,7 @@ from . import lib
 from .arena import Arena
 from .config import UNetConfig
 from .lora_store import LoraStore
+from .passes import Pass
 from .planner import AttnMapSpec, BackwardPlan, UNetPlan
 from .weights import WeightStore
 
@@ -195,19 +196,14 @@ class UNetEngine:
         return "train" if torch.is_grad_enabled() else "on"
 
     def load_inputs(self, p: UNetPlan, sample, timestep, encoder_hidden_states, added_cond_kwargs):
-        B = p.B
-        io = p.io
-        io["sample"].tensor.copy_(sample.to(torch.bfloat16))
+        drv = Pass(self, p)
+        drv.load_latents(sample)
         t = timestep
         if not torch.is_tensor(t):
             t = torch.tensor(float(t))
-        io["t"].tensor.copy_(t.to(device=self.device, dtype=torch.float32).reshape(-1, 1).expand(B, 1))
-        io["ctx"].tensor.copy_(encoder_hidden_states.to(torch.bfloat16))
-        if self.cfg.is_xl:
-            te = added_cond_kwargs["text_embeds"]
-            ti = added_cond_kwargs["time_ids"]
-            io["time_ids"].tensor.copy_(ti.to(torch.float32).reshape(B, 6))
-            io["add_in"].tensor[:, : self.cfg.pooled_dim].copy_(te.to(torch.bfloat16))
+        p.io["t"].tensor.copy_(t.to(device=self.device, dtype=torch.float32).reshape(-1, 1).expand(p.B, 1))
+        te, ti = (added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]) if self.cfg.is_xl else (None, None)
+        drv.load_cond(encoder_hidden_states, te, ti)
 
     def forward_plan(self, p: UNetPlan):
         p.prog.run(torch.cuda.current_stream().cuda_stream)
