@@ -6,8 +6,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-import torch
-
 from sliders_amd import lib
 from sliders_amd.arena import Arena
 from sliders_amd.config import CONFIGS
@@ -18,7 +16,6 @@ from test_host import _FakeWeights
 model, hw, B, mode = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
 cfg = CONFIGS[model]()
 store = LoraStore(cfg, train_method="noxattn", init="none")
-store.temb_tcol = torch.zeros(1, dtype=torch.int32)
 p = UNetPlan(cfg, _FakeWeights(cfg), Arena(1 << 50, None), Arena(1 << 40, None), B, hw, hw, 77,
              store if mode != "off" else None, mode, 0x10)
 names = {v: k for k, v in vars(lib).items() if k.startswith("OP_")}

@@ -89,6 +89,7 @@ class LoraStore:
         self.exp_avg_sq = torch.zeros(n, dtype=state_dtype, device=device)
         self.master = torch.zeros(n, dtype=torch.float32, device=device) if state_dtype == torch.float32 else None
         self.opt_step = 0
+        self._temb_tcol = None
         self._build_up_t()
         if init == "reference":
             self.init_reference(kaiming_a)
@@ -153,7 +154,7 @@ class LoraStore:
         """Element offset, inside self.up_t, of the [4 * len(grp)][sum out_dim] matrix whose row 4g + r holds column r of
         member g's up matrix over that member's own output columns and zeros elsewhere (block-diagonal for a fused q|k|v
         group): U = dY . B, a down-projection of the output gradient, rides in the backward-data GEMM as its third operand
-        (planner.BackwardPlan._b_gemm).  One slot per dense group of the layout; None for convolutions / unknown groups."""
+        (backward.BackwardPlan._b_gemm).  One slot per dense group of the layout; None for convolutions / unknown groups."""
         slot = self._up_t_slots.get(tuple(e.name for e in grp))
         return None if slot is None else slot[0]
 
@@ -171,6 +172,19 @@ class LoraStore:
                 col += n
         self.up_t_index = idx.to(self.device)
         self.up_t = torch.zeros(max(self._up_t_numel, 1), dtype=torch.bfloat16, device=self.device)
+
+    def temb_tcol_table(self, w) -> torch.Tensor:
+        """int32 [w.temb_total], on the parameters' device: for every column of the batched time_emb_proj GEMV (all resnets' rows
+        concatenated at w.temb_offsets) the first of its adapter's four columns of T.  Built on the first request."""
+        if self._temb_tcol is None:
+            tcol = torch.empty(w.temb_total, dtype=torch.int32)
+            for i, p in enumerate(w.resnet_paths):
+                e = self.temb_entries[i]
+                assert e.target.module_path == p + ".time_emb_proj"
+                o = w.temb_offsets[p]
+                tcol[o:o + e.target.out_dim] = 4 * i
+            self._temb_tcol = tcol.to(self.params.device)
+        return self._temb_tcol
 
     def fused_group(self, paths: List[str]) -> Optional[List[LoraEntry]]:
         """Entries for `paths` if they are all adapted AND stored adjacently (downs then ups), else None."""

@@ -10,7 +10,8 @@ activations [B*H*W][C]:
     when the adapters are switched off (multiplier 0 adds an exact 0 in the reference),
   * q/k/v (and cross k/v) projections are fused into one GEMM, all time_emb_proj layers into one GEMV.
 Modes: "off" (LoRA disabled), "on" (LoRA enabled, no grad), "train" (LoRA enabled, activations kept, GEGLU
-unfused so its pre-activation is available; `build_backward()` then emits the backward program).
+unfused so its pre-activation is available; the pass leaves a tape of typed records, from which backward.BackwardPlan
+emits the backward program).
 """
 from __future__ import annotations
 
@@ -70,6 +71,100 @@ Src = Union[Act, Tuple[Act, Act]]
 PH = 0x1000                      # placeholder for a pointer _emit fills in (aligned like every arena buffer: the tile rule looks)
 
 
+def src_parts(x: Src):
+    return x if isinstance(x, tuple) else (x, None)
+
+
+def sources(x0: Act, x1: Optional[Act], p: str, ld: str, c: str) -> dict:
+    """The two-source operand fields of a descriptor (a channel concat folded into the operand addressing), by field-name
+    prefix: pointers p0 / p1, row strides ld0 / ld1, widths c0 / c1; all zero for a second source that is not there."""
+    return {p + "0": x0.ptr, p + "1": x1.ptr if x1 else 0, ld + "0": x0.ld, ld + "1": x1.ld if x1 else 0,
+            c + "0": x0.C, c + "1": x1.C if x1 else 0}
+
+
+def head_t(D: int, T: int) -> Tuple[int, int]:
+    """(Dp, ldt) of a head-transposed [B][heads][Dp][ldt] array: head dim and tokens rounded up to whole 64s"""
+    return (D + 63) // 64 * 64, (T + 63) // 64 * 64
+
+
+@dataclass(frozen=True)
+class Conv3:
+    """A product that is a 3x3 convolution (pad 1); None stands for a Linear / 1x1 convolution."""
+    stride: int = 1
+    xform: int = 0                 # 1: the source is read nearest-2x upsampled
+
+
+def conv_fields(d, conv: Conv3, src: Act, Ho: int, Wo: int):
+    """The implicit-GEMM fields of a descriptor (slh_gemm, slh_skinny, slh_lora_wgrad) that reads src as a 3x3 convolution does"""
+    d.mode = 1
+    d.batch, d.hs, d.ws = src.B, src.H, src.W
+    d.src_xform, d.stride = conv.xform, conv.stride
+    d.ho, d.wo = Ho, Wo
+
+
+# The tape of a training forward: one record per differentiable step, in launch order, each with exactly what the backward reads
+# (backward.BackwardPlan.HANDLERS has one handler per type).
+@dataclass
+class GemmRec:
+    name: str
+    x: Src
+    wname: str
+    N: int
+    K: int
+    Ho: int
+    Wo: int
+    conv: Optional[Conv3]
+    grp: Optional[List[LoraEntry]]         # the adapter group
+    residual: Optional[Act]
+    temb_path: Optional[str]               # the resnet whose time_emb_proj row is this product's per-sample bias
+    out: Optional[Act] = None              # the output and the adapter's T: what _emit allocates, set before the record is appended
+    T: Optional[Buf] = None
+
+
+@dataclass
+class GnRec:
+    name: str
+    x: Src
+    out: Act
+    wname: str
+    eps: float
+    act: int
+    stats: Buf
+
+
+@dataclass
+class LnRec:
+    name: str
+    x: Act
+    out: Act
+    wname: str
+    mr: Buf
+
+
+@dataclass
+class AttnRec:
+    name: str
+    q: Act
+    k: Act
+    v: Act
+    o: Act
+    lse: Buf
+    Tk: int
+    heads: int
+
+
+@dataclass
+class GegluRec:
+    name: str
+    pre: Act
+    out: Act
+
+
+@dataclass
+class ConvOutRec:
+    x: Act
+
+
 @dataclass
 class Product:
     """One slh_gemm launch as UNetPlan._decide settled it.  d says the rest: d.vt_out - V^T / dO^T is stored, d.xa_k - the
@@ -77,10 +172,14 @@ class Product:
     d: "lib.GemmDesc"              # complete but for the pointers of what _emit allocates: output, T, statistics, V^T (placeholders)
     ln_cols: int                   # chunk width of the row statistics left for a folded LayerNorm (0: none)
     fused: bool                    # the adapter's down-projection runs inside the launch
-    x: Src
     geglu_pre: Optional[Act]
     ln_norm: Optional[str]         # LayerNorm folded into the adapter's down-projection as well
-    rec: dict                      # the tape record, `out` and `T` filled in by _emit; rec["grp"] = the adapter group
+    rec: GemmRec                   # its tape record (rec.x: the product's input)
+
+    def behind_ln_record(self, stand_in: Act, mr: Buf):
+        """Training LayerNorm fold: the tape keeps the LayerNorm as a record of its own, so this product's record reads the
+        stand-in for the normalised tensor, and the launch leaves the rows' (mean, rstd) for the LayerNorm backward in mr."""
+        self.d.ln_mr_out, self.rec.x = mr.ptr, stand_in
 
 
 SPLITK_TICKETS = 4096            # 64-bit arrival tickets per plan (one per output tile of the largest split-K product)
@@ -120,32 +219,65 @@ class Switches:
         return cls(**{f.name: read[f.metadata["parse"]](os.environ.get(f.metadata["env"])) for f in fields(cls)})
 
 
-def _plan_tickets(plan, n: int) -> int:
-    """The arrival tickets of a plan's split-K products: ONE array per plan - every launch leaves its tickets zero and the
-    launches of a plan are ordered on one stream.  Lives in the zero-init arena (zeroed at the head of the program)."""
-    assert n <= SPLITK_TICKETS, f"split-K product with {n} output tiles"
-    if plan._splitk_tickets is None:
-        plan._splitk_tickets = plan.zarena.alloc((2 * SPLITK_TICKETS,), torch.float32, "splitk.tickets")
-    return plan._splitk_tickets.ptr
+class Plan:
+    """What the forward and the backward plan share: the arenas, the weights and the switches; the op list, serialised once; the
+    split-K workspace; and the memset at the head of the program that zeroes the span of the zero arena the plan used."""
 
+    def __init__(self, w, arena: Arena, zarena: Arena, sw: Switches):
+        self.w, self.arena, self.zarena, self.sw = w, arena, zarena, sw
+        self.ops: List[tuple] = []                # (opcode, descriptor, name) in launch order
+        self._splitk_tickets = None
+        self.zmark = zarena.mark()
 
-def provision_splitk(plan, d, name: str):
-    """Give a product whose tile splits K (or, in tuning mode, may) its slab workspace: one fp32 slab (M, N rounded up to whole
-    tiles) per K slice
-    (each slice writes its own, the last slice of a tile to arrive adds them in slice order inside the launch - bit-reproducible) and, with a
-    fused adapter, two [M][ld_t] slabs per slice for T."""
-    slabs = splitk_slabs(d)
-    if not slabs:
-        return
-    d.splitk_slabs = slabs
-    d.splitk_c32 = plan.arena.alloc((slabs, (d.M + 255) // 256 * 256, (d.N + 127) // 128 * 128), torch.float32, name + ".splitk").ptr
-    d.splitk_ticket = _plan_tickets(plan, ((d.M + 63) // 64) * ((d.N + 63) // 64))
-    if d.lora_down:
-        # one pair of T slabs per slice and per COLUMN TILE (each column tile's last slice reduces its own copy); sized for
-        # the narrowest tile (64 columns) unless the tile is fixed
-        ni = tile_fields(d.tile).ni if (d.tile and not splitk_tuning()) else 1
-        tiles_n = (d.N + 64 * ni - 1) // (64 * ni)
-        d.splitk_t32 = plan.arena.alloc((tiles_n * 2 * slabs, d.M, d.ld_t), torch.float32, name + ".splitk_T").ptr
+    @property
+    def w_layout(self) -> int:
+        return 1 if self.w.packed else 0
+
+    def add(self, opcode: int, desc, name: str):
+        self.ops.append((opcode, desc, name))
+
+    def _tickets(self, n: int) -> int:
+        """The arrival tickets of a plan's split-K products: ONE array per plan - every launch leaves its tickets zero and the
+        launches of a plan are ordered on one stream.  Lives in the zero-init arena (zeroed at the head of the program)."""
+        assert n <= SPLITK_TICKETS, f"split-K product with {n} output tiles"
+        if self._splitk_tickets is None:
+            self._splitk_tickets = self.zarena.alloc((2 * SPLITK_TICKETS,), torch.float32, "splitk.tickets")
+        return self._splitk_tickets.ptr
+
+    def provision_splitk(self, d, name: str):
+        """Give a product whose tile splits K (or, in tuning mode, may) its slab workspace: one fp32 slab (M, N rounded up to whole
+        tiles) per K slice (each slice writes its own, the last slice of a tile to arrive adds them in slice order inside the launch
+        - bit-reproducible) and, with a fused adapter, two [M][ld_t] slabs per slice for T."""
+        slabs = splitk_slabs(d)
+        if not slabs:
+            return
+        d.splitk_slabs = slabs
+        d.splitk_c32 = self.arena.alloc((slabs, (d.M + 255) // 256 * 256, (d.N + 127) // 128 * 128), torch.float32, name + ".splitk").ptr
+        d.splitk_ticket = self._tickets(((d.M + 63) // 64) * ((d.N + 63) // 64))
+        if d.lora_down:
+            # one pair of T slabs per slice and per COLUMN TILE (each column tile's last slice reduces its own copy); sized for
+            # the narrowest tile (64 columns) unless the tile is fixed
+            ni = tile_fields(d.tile).ni if (d.tile and not splitk_tuning()) else 1
+            tiles_n = (d.N + 64 * ni - 1) // (64 * ni)
+            d.splitk_t32 = self.arena.alloc((tiles_n * 2 * slabs, d.M, d.ld_t), torch.float32, name + ".splitk_T").ptr
+
+    def put_head(self, zero_name: str, head: List[tuple]):
+        """Close the op list: ahead of what was collected go the memset of the zero arena's span this plan allocated (fp32
+        accumulators, arrival tickets) and then `head`, the plan's own launches that must precede everything."""
+        self.zend = self.zarena.mark()
+        zero = []
+        if self.zend > self.zmark:
+            p, n = self.zarena.region(self.zmark, self.zend)
+            zero.append((lib.OP_MEMSET, lib.MemsetDesc(ptr=p, nbytes=n, value=0, pad=0), zero_name))
+        self.ops = zero + head + self.ops
+
+    def program(self, skip=()) -> "lib.Program":
+        """The op list as a command buffer, without the ops named in skip"""
+        prog = lib.Program()
+        for o, d, nm in self.ops:
+            if nm not in skip:
+                prog.add(o, d, nm)
+        return prog
 
 
 PREFETCH_MIN_BYTES = int(os.environ.get("SLIDERS_PREFETCH_MIN", str(6 << 20)))
@@ -205,20 +337,7 @@ class AttnMapSpec:
         return s
 
 
-def _program(ops) -> "lib.Program":
-    prog = lib.Program()
-    for o, d, nm in ops:
-        prog.add(o, d, nm)
-    return prog
-
-
-def _src_parts(x: Src):
-    if isinstance(x, tuple):
-        return x[0], x[1]
-    return x, None
-
-
-class UNetPlan:
+class UNetPlan(Plan):
     def __init__(self, cfg: UNetConfig, weights: WeightStore, arena: Arena, zarena: Arena, B: int, H: int, W: int,
                  ctx_len: int = 77, lora: Optional[LoraStore] = None, mode: str = "off",
                  lora_scale_ptr: int = 0, io: Optional[dict] = None, attn_maps=None):
@@ -228,34 +347,26 @@ class UNetPlan:
         if self.attn_maps is not None and mode == "train":
             raise ValueError("attn_maps: attention maps are collected in the no-grad plans (mode 'off' / 'on'), not in 'train'")
         self.map_ops: Dict[int, list] = {}        # factor -> the slh_xattn_map descriptors of that level, in plan order
-        self.cfg, self.w, self.arena, self.zarena = cfg, weights, arena, zarena
+        super().__init__(weights, arena, zarena, Switches.from_env())
+        self.cfg = cfg
         self.B, self.H, self.W, self.ctx_len = B, H, W, ctx_len
         self.lora = lora if mode != "off" else None
         self.mode = mode
         self.train = mode == "train"
         self.lora_scale_ptr = lora_scale_ptr
-        self.sw = Switches.from_env()
-        self.ops: List[tuple] = []                # (opcode, descriptor, name) in launch order; serialised once, below
-        self.tape: List[dict] = []
+        self.tape: list = []                      # GemmRec, GnRec ... of a training pass, in launch order
         self.lnfold_items: List[tuple] = []       # adapter sides of LayerNorm folds (slh_lora_lnfold_item as int64 words)
-        self._splitk_tickets = None
-        self.zmark = zarena.mark()
         self._build_io(io)
         self._forward()
         self._finish_maps()
-        self.zend = zarena.mark()
-        # zero the fp32 accumulators (GroupNorm statistics ...) used by this program first
         head = []
-        if self.zend > self.zmark:
-            p, n = zarena.region(self.zmark, self.zend)
-            head.append((lib.OP_MEMSET, lib.MemsetDesc(ptr=p, nbytes=n, value=0, pad=0), "zero_stats"))
         if self.lnfold_items:
             self._lnfold_table = torch.tensor(self.lnfold_items, dtype=torch.int64, device=self.lora.params.device)
             head.append((lib.OP_LORA_LN_FOLD, lib.LoraLnFoldDesc(items=self._lnfold_table.data_ptr(), n=len(self.lnfold_items)),
                          "lora_ln_fold"))
-        self.ops = head + self.ops
+        self.put_head("zero_stats", head)
         attach_weight_touch(self.ops, self.sw)
-        self.prog = _program(self.ops)
+        self.prog = self.program()
         # The text K/V of every cross-attention block depend only on the prompt embeddings (and frozen weights): inside a
         # denoise loop (train_util.py:263-294: same embeddings for every timestep) steps 2.. replay the pass without
         # the batched K/V projection and its head transpose.  Valid only while no other plan ran in between (plans
@@ -263,10 +374,7 @@ class UNetPlan:
         self.prog_text_cached = None
         if self.kv_all is not None:
             skip = {"attn2_kv_all", "attn2_vt_all", "lora_ln_fold"}     # (the adapters do not change inside a denoise loop either)
-            self.prog_text_cached = _program(op for op in self.ops if op[2] not in skip)
-
-    def add(self, opcode: int, desc, name: str):
-        self.ops.append((opcode, desc, name))
+            self.prog_text_cached = self.program(skip)
 
     # ------------------------------------------------------------------------------------------------
     # buffers
@@ -355,25 +463,15 @@ class UNetPlan:
             return None
         return self.lora.fused_group(paths)
 
-    def _conv_fields(self, d, src: Act, conv: dict, Ho: int, Wo: int):
-        d.mode = 1
-        d.batch, d.hs, d.ws = src.B, src.H, src.W
-        d.src_xform = conv.get("xform", 0)
-        d.stride = conv.get("stride", 1)
-        d.ho, d.wo = Ho, Wo
-
-    def skinny(self, x: Src, w_ptr: int, R: int, K: int, conv: Optional[dict], Mout: int, Ho: int, Wo: int,
+    def skinny(self, x: Src, w_ptr: int, R: int, K: int, conv: Optional[Conv3], Mout: int, Ho: int, Wo: int,
                name: str, out: Optional[Buf] = None, bias_ptr: int = 0, out_kind: int = 0) -> Buf:
-        x0, x1 = _src_parts(x)
+        x0, x1 = src_parts(x)
         if out is None:
             out = self.f32((Mout, R), name + ".T")
-        d = lib.SkinnyDesc(a0=x0.ptr, a1=x1.ptr if x1 else 0, w=w_ptr, bias=bias_ptr, out=out.ptr,
-                           lda0=x0.ld, lda1=x1.ld if x1 else 0, ca0=x0.C, ca1=x1.C if x1 else 0,
-                           M=Mout, R=R, K=K, ldo=R, out_kind=out_kind)
+        d = lib.SkinnyDesc(**sources(x0, x1, "a", "lda", "ca"), w=w_ptr, bias=bias_ptr, out=out.ptr,
+                           M=Mout, R=R, K=K, ldo=R, out_kind=out_kind, stride=1)
         if conv is not None:
-            self._conv_fields(d, x0, conv, Ho, Wo)
-        else:
-            d.stride = 1
+            conv_fields(d, conv, x0, Ho, Wo)
         self.add(lib.OP_SKINNY, d, name)
         return out
 
@@ -384,17 +482,17 @@ class UNetPlan:
         assert p is not None, f"{name}: no tile takes this product"
         return self._emit(p)
 
-    def _decide(self, x: Src, wname: str, N: int, name: str, bias: bool = True, conv: Optional[dict] = None,
+    def _decide(self, x: Src, wname: str, N: int, name: str, bias: bool = True, conv: Optional[Conv3] = None,
                 rowbias: Optional[Tuple[int, int]] = None, residual: Optional[Act] = None,
                 lora_paths: Optional[List[str]] = None, geglu: bool = False, vt_heads: Optional[int] = None,
                 ln_stats: bool = False, ln_fold: Optional[Act] = None, geglu_pre: Optional[Act] = None,
                 ln_mr: bool = False, geglu16: bool = False, xattn: Optional[dict] = None,
-                ln_norm: Optional[str] = None) -> Optional[Product]:
+                ln_norm: Optional[str] = None, temb_path: Optional[str] = None) -> Optional[Product]:
         """The form of one product, settled before anything is allocated or recorded: builds the descriptor - placeholder pointers
         (PH, 8, 16) for what _emit will allocate - and asks choose_tile.  Touches no arena, no tape, no list of the plan.  Returns None
         when the LayerNorm it was asked to fold (ln_fold) cannot be folded on the tile that would run: the caller (ln_gemm) then
         records the LayerNorm launch and the plain product.
-        conv: {'stride','xform'} for 3x3.
+        conv: the product is a 3x3 convolution.  temb_path: the resnet whose time_emb_proj output rowbias is (kept for the backward).
         vt_heads: the product is a fused q|k|v projection of that many heads; where the kernel supports it (head_dim % 64 == 0) its
         V third is written head-transposed for slh_attn_fwd straight from the epilogue (Product.d.vt_out; the returned
         activation's .vt names the buffer) - one launch and one HBM round trip of V less per self-attention.
@@ -411,13 +509,12 @@ class UNetPlan:
         ln_fold together with lora_paths (ln_norm = the LayerNorm's weight name): the adapter's down-projection is folded as well
         (slh_gemm_desc.ln_lora_*; A . gamma and its row sums / offsets are rebuilt from the live parameters by ONE
         slh_lora_ln_fold launch at the head of the program) - only on the ping-pong tiles; None when another tile would run."""
-        x0, x1 = _src_parts(x)
+        x0, x1 = src_parts(x)
         cin = x0.C + (x1.C if x1 else 0)
         if conv is not None:
-            sh = 1 if conv.get("xform", 0) else 0
+            sh = 1 if conv.xform else 0
             HL, WL = x0.H << sh, x0.W << sh
-            st = conv.get("stride", 1)
-            Ho, Wo = (HL - 1) // st + 1, (WL - 1) // st + 1   # 3x3, pad 1
+            Ho, Wo = (HL - 1) // conv.stride + 1, (WL - 1) // conv.stride + 1   # 3x3, pad 1
             K = 9 * cin
         else:
             Ho, Wo, K = x0.H, x0.W, cin
@@ -429,7 +526,7 @@ class UNetPlan:
         sfx = "16" if geglu16 else ""      # GEGLU.proj in the 16 | 16 block order (slh_gemm_desc.geglu = 3)
         assert not geglu16 or (geglu and geglu_pre is None and not lora_paths)
         fold = ln_fold is not None
-        d = lib.GemmDesc(a0=x0.ptr, a1=x1.ptr if x1 else 0, w=self.w.ptr(wname + (".lnw" if fold else ".w") + sfx),
+        d = lib.GemmDesc(**sources(x0, x1, "a", "lda", "ca"), w=self.w.ptr(wname + (".lnw" if fold else ".w") + sfx),
                          bias=self.w.ptr(wname + ".b" + sfx) if (bias and not fold) else 0,
                          rowbias=rowbias[0] if rowbias else 0,
                          lora_t=PH if (grp is not None and not fused) else 0, lora_up=self.lora.up_ptr(grp[0]) if grp else 0,
@@ -437,16 +534,13 @@ class UNetPlan:
                          lora_t_out=PH if (fused and self.train) else 0,      # (T is only written out for the backward)
                          lora_rank=(4 * len(grp)) if fused else 0,
                          lora_scale=self.lora_scale_ptr if grp else 0,
-                         residual=residual.ptr if residual else 0, c=PH,
-                         lda0=x0.ld, lda1=x1.ld if x1 else 0, ca0=x0.C, ca1=x1.C if x1 else 0,
-                         mode=0, stride=1, ldw=K, M=M, N=N, K=K,
+                         residual=residual.ptr if residual else 0, c=PH, mode=0, stride=1, ldw=K, M=M, N=N, K=K,
                          ld_rowbias=rowbias[1] if rowbias else 0, rows_per_sample=Ho * Wo,
                          ld_t=(4 * len(grp)) if grp else 0, lora_groups=len(grp) if grp else 0,
                          ld_res=residual.ld if residual else 0, ldc=N // 2 if geglu else N,
-                         geglu=(3 if geglu16 else 1) if geglu else 0, tile=0,
-                         w_layout=1 if self.w.packed else 0)
+                         geglu=(3 if geglu16 else 1) if geglu else 0, tile=0, w_layout=self.w_layout)
         if conv is not None:
-            self._conv_fields(d, x0, conv, Ho, Wo)
+            conv_fields(d, conv, x0, Ho, Wo)
         if fold:
             d.ln_in, d.ln_in_chunks, d.ln_eps = ln_fold.ln[0].ptr, ln_fold.ln[1], 1e-5
             d.ln_s, d.ln_b = self.w.ptr(wname + ".lns" + sfx), self.w.ptr(wname + ".lnb" + sfx)
@@ -472,24 +566,22 @@ class UNetPlan:
         ln_cols = choose_tile(d, ln_out=want_ln_out, vt=vt, xa=xa)
         if ln_cols is None:
             return None
-        rec = dict(op="gemm", x=x, out=None, wname=wname, N=N, K=K, conv=conv, grp=grp, T=None, residual=residual, rowbias=rowbias,
-                   name=name, Ho=Ho, Wo=Wo)
-        return Product(d, ln_cols, fused, x, geglu_pre, ln_norm, rec)
+        return Product(d, ln_cols, fused, geglu_pre, ln_norm, GemmRec(name, x, wname, N, K, Ho, Wo, conv, grp, residual, temb_path))
 
     def _emit(self, p: Product) -> Act:
         """Allocate what the product settled by _decide needs, fill in the real pointers, record the launch and its tape record.  The
         order of the allocations is part of the plan (addresses): output; T (unfused adapter: T, then the down-projection's launch);
         the folded adapter's A . gamma and sums; split-K workspace; statistics chunks; V^T."""
         d, rec = p.d, p.rec
-        name, grp, M, N, K, Ho, Wo = rec["name"], rec["grp"], d.M, d.N, d.K, rec["Ho"], rec["Wo"]
-        B = _src_parts(p.x)[0].B
+        name, grp, M, N, K, Ho, Wo = rec.name, rec.grp, d.M, d.N, d.K, rec.Ho, rec.Wo
+        B = src_parts(rec.x)[0].B
         out = self.act(B, Ho, Wo, d.ldc, name)
         d.c = out.ptr
         T = None
         if grp is not None:
             R = sum(e.target.rank for e in grp)
             if not p.fused:
-                T = self.skinny(p.x, self.lora.down_ptr(grp[0]), R, K, rec["conv"], M, Ho, Wo, name + ".lora_down")
+                T = self.skinny(rec.x, self.lora.down_ptr(grp[0]), R, K, rec.conv, M, Ho, Wo, name + ".lora_down")
                 d.lora_t = T.ptr
             elif self.train:
                 T = self.f32((M, R), name + ".T")
@@ -501,7 +593,7 @@ class UNetPlan:
             d.lora_down, d.ln_lora_s, d.ln_lora_c = a2.ptr, sc.ptr, sc.ptr + 64
             self.lnfold_items.append(lib.lnfold_item(self.lora.down_ptr(grp[0]), self.w.ptr(p.ln_norm + ".g"), self.w.ptr(p.ln_norm + ".b"),
                                                      a2.ptr, sc.ptr, sc.ptr + 64, R, K))
-        provision_splitk(self, d, name)
+        self.provision_splitk(d, name)
         if p.ln_cols:
             st = self.f32((N // p.ln_cols, M, 2), name + ".ln_chunks")
             d.ln_out = st.ptr
@@ -513,12 +605,12 @@ class UNetPlan:
         out.attended = bool(d.xa_k)
         self.add(lib.OP_GEMM, d, name)
         if self.train:
-            rec["out"], rec["T"] = p.geglu_pre if p.geglu_pre is not None else out, T
+            rec.out, rec.T = p.geglu_pre if p.geglu_pre is not None else out, T
             self.tape.append(rec)
         return out
 
     def groupnorm(self, x: Src, wname: str, eps: float, act: int, name: str) -> Act:
-        x0, x1 = _src_parts(x)
+        x0, x1 = src_parts(x)
         C = x0.C + (x1.C if x1 else 0)
         B, H, W = x0.B, x0.H, x0.W
         G = self.cfg.norm_num_groups
@@ -529,9 +621,9 @@ class UNetPlan:
         part = self.f32((B, prow, G, 2), name + ".partial")
         ticket = self.f32((B, ntick), name + ".ticket", zero=True)
         y = self.act(B, H, W, C, name)
-        d = lib.GnDesc(x0=x0.ptr, x1=x1.ptr if x1 else 0, gamma=self.w.ptr(wname + ".g"), beta=self.w.ptr(wname + ".b"),
-                       stats=stats.ptr, y=y.ptr, ldx0=x0.ld, ldx1=x1.ld if x1 else 0, c0=x0.C, c1=x1.C if x1 else 0,
-                       batch=B, hw=H * W, groups=G, ldy=y.ld, eps=eps, act=act, partial=part.ptr, ticket=ticket.ptr)
+        d = lib.GnDesc(**sources(x0, x1, "x", "ldx", "c"), gamma=self.w.ptr(wname + ".g"), beta=self.w.ptr(wname + ".b"),
+                       stats=stats.ptr, y=y.ptr, batch=B, hw=H * W, groups=G, ldy=y.ld, eps=eps, act=act, partial=part.ptr,
+                       ticket=ticket.ptr)
         one = lib.gn_fused_ok(C, H * W, G)      # 1: tiny tensor, one workgroup per group set; 2: cache-resident slab, sibling workgroups
         if one == 2 and self.sw.gn_split_slab:
             one = 0
@@ -541,7 +633,7 @@ class UNetPlan:
             self.add(lib.OP_GN_STATS, d, name + ".stats")
             self.add(lib.OP_GN_APPLY, d, name + ".apply")
         if self.train:
-            self.tape.append(dict(op="gn", x=x, out=y, wname=wname, eps=eps, act=act, stats=stats, name=name))
+            self.tape.append(GnRec(name, x, y, wname, eps, act, stats))
         return y
 
     def layernorm(self, x: Act, wname: str, name: str) -> Act:
@@ -551,7 +643,7 @@ class UNetPlan:
                        mean_rstd=mr.ptr if mr else 0, M=x.M, C=x.C, ldx=x.ld, ldy=y.ld, eps=1e-5)
         self.add(lib.OP_LAYERNORM, d, name)
         if self.train:
-            self.tape.append(dict(op="ln", x=x, out=y, wname=wname, mr=mr, name=name))
+            self.tape.append(LnRec(name, x, y, wname, mr))
         return y
 
     def ln_gemm(self, h: Act, norm: str, wname: str, N: int, bias: bool = True, lora_paths: Optional[List[str]] = None,
@@ -578,8 +670,8 @@ class UNetPlan:
             if p is not None:
                 mr = self.f32((h.M, 2), norm + ".mean_rstd")
                 stand_in = self.key_act(h.B, h.H, h.W, h.C, norm + ".unwritten")
-                self.tape.append(dict(op="ln", x=h, out=stand_in, wname=norm, mr=mr, name=norm))
-                p.d.ln_mr_out, p.rec["x"] = mr.ptr, stand_in
+                self.tape.append(LnRec(norm, h, stand_in, norm, mr))
+                p.behind_ln_record(stand_in, mr)
         if p is not None:
             return self._emit(p)
         n = self.layernorm(h, norm, norm)
@@ -592,8 +684,7 @@ class UNetPlan:
         B, Tq, C = q.B, q.HW, q.C
         D = C // heads
         assert D * heads == C and D % 8 == 0 and D <= 192, f"unsupported head_dim {D}"
-        Dp = (D + 63) // 64 * 64
-        ldt = (Tk + 63) // 64 * 64
+        Dp, ldt = head_t(D, Tk)
         if vt_pre is None:
             vt = self.arena.alloc((B, heads, Dp, ldt), torch.bfloat16, name + ".vt")
             self.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(src=v.ptr, dst=vt.ptr, B=B, H=heads, T=Tk, ld=v.ld,
@@ -607,7 +698,7 @@ class UNetPlan:
                          ldq=q.ld, ldk=k.ld, ldvt=ldt, ldo=o.ld, scale=D ** -0.5, D=D, vt_batch_heads=vt_heads)
         self.add(lib.OP_ATTN_FWD, d, name)
         if self.train:
-            self.tape.append(dict(op="attn", q=q, k=k, v=v, o=o, lse=lse, Tk=Tk, heads=heads, name=name))
+            self.tape.append(AttnRec(name, q, k, v, o, lse, Tk, heads))
         return o
 
     # ------------------------------------------------------------------------------------------------
@@ -650,20 +741,12 @@ class UNetPlan:
             d = lib.GemvDesc(x=emb.ptr, w=self.lora.params.data_ptr() + 2 * self.lora.temb_down_off, y=lt.ptr,
                              nb=B, N=4 * L, K=ted, ldx=ted, ldy=4 * L, in_act=1, out_f32=1)
             self.add(lib.OP_GEMV, d, "temb.lora_down")
-            if not hasattr(self.lora, "temb_tcol"):
-                tcol = torch.empty(tot, dtype=torch.int32)
-                for i, p in enumerate(w.resnet_paths):
-                    e = self.lora.temb_entries[i]
-                    assert e.target.module_path == p + ".time_emb_proj"
-                    o = w.temb_offsets[p]
-                    tcol[o:o + e.target.out_dim] = 4 * i
-                self.lora.temb_tcol = tcol.to(self.lora.params.device)
         d = lib.GemvDesc(x=emb.ptr, w=w.ptr("temb_proj.w"), bias=w.ptr("temb_proj.b"), y=self.temb_all.ptr,
                          nb=B, N=tot, K=ted, ldx=ted, ldy=tot, in_act=1, out_f32=0)
         if lt is not None:
             d.lora_t = lt.ptr
             d.ld_t = lt.shape[1]
-            d.lora_tcol = self.lora.temb_tcol.data_ptr()
+            d.lora_tcol = self.lora.temb_tcol_table(w).data_ptr()
             d.lora_up = self.lora.params.data_ptr() + 2 * self.lora.temb_up_off
             d.lora_scale = self.lora_scale_ptr
         self.add(lib.OP_GEMV, d, "time_emb_proj_all")
@@ -676,14 +759,13 @@ class UNetPlan:
         self.add(lib.OP_GEMV, d, name)
 
     def _resnet(self, x: Src, path: str, cout: int) -> Act:
-        x0, x1 = _src_parts(x)
+        x0, x1 = src_parts(x)
         cin = x0.C + (x1.C if x1 else 0)
         eps = self.cfg.norm_eps
         a1 = self.groupnorm(x, path + ".norm1", eps, 1, path + ".norm1")
         rb = (self.temb_all.ptr + 2 * self.w.temb_offsets[path], self.w.temb_total)
-        h = self.gemm(a1, path + ".conv1", cout, path + ".conv1", conv={}, rowbias=rb, lora_paths=[path + ".conv1"])
-        if self.train:
-            self.tape[-1]["temb_path"] = path
+        h = self.gemm(a1, path + ".conv1", cout, path + ".conv1", conv=Conv3(), rowbias=rb, temb_path=path,
+                      lora_paths=[path + ".conv1"])
         a2 = self.groupnorm(h, path + ".norm2", eps, 1, path + ".norm2")
         if cin != cout:
             sc = self.gemm(x, path + ".conv_shortcut", cout, path + ".conv_shortcut",
@@ -691,7 +773,7 @@ class UNetPlan:
         else:
             assert x1 is None
             sc = x0
-        return self.gemm(a2, path + ".conv2", cout, path + ".conv2", conv={}, residual=sc,
+        return self.gemm(a2, path + ".conv2", cout, path + ".conv2", conv=Conv3(), residual=sc,
                          lora_paths=[path + ".conv2"])
 
     def _tblock(self, h: Act, path: str, heads: int, ctx: Act) -> Act:
@@ -710,7 +792,7 @@ class UNetPlan:
             k2, v2, kv = self.kv_all.cols(k_off, C), self.kv_all.cols(v_off, C), self.kv_all
             if self.vt_all is not None:
                 D = C // heads
-                Dp, ldt = (D + 63) // 64 * 64, (self.ctx_len + 63) // 64 * 64
+                Dp, ldt = head_t(D, self.ctx_len)
                 vt_pre = (self.vt_all.ptr + 2 * ((v_off - self.w.kv_all_vbase) // D) * Dp * ldt, self.vt_all_heads)
         else:
             kv = self.gemm(ctx, a2 + ".kv", 2 * C, a2 + ".kv", bias=False, lora_paths=[a2 + ".to_k", a2 + ".to_v"])
@@ -726,7 +808,7 @@ class UNetPlan:
         if not self.train and vt_pre is not None and D2 == 64 and C % 64 == 0 and 64 < self.ctx_len <= 96 and h.HW % 128 == 0 and \
                 self._lora_group([a2 + ".to_q"]) is None and not self.sw.no_fused_xattn and map_factor is None:
             xa = dict(k=k2, vt_ptr=vt_pre[0], vt_heads=vt_pre[1], Tk=self.ctx_len, Tq=h.HW, scale=D2 ** -0.5,
-                      ldvt=(self.ctx_len + 63) // 64 * 64)
+                      ldvt=head_t(D2, self.ctx_len)[1])
         q2 = self.ln_gemm(h1, path + ".norm2", a2 + ".q", C, bias=False, lora_paths=[a2 + ".to_q"], xattn=xa)
         if q2.attended:
             o2 = q2
@@ -742,13 +824,13 @@ class UNetPlan:
             ff = self.act(h.B, h.H, h.W, 4 * C, path + ".geglu")
             self.add(lib.OP_ELEMENTWISE, lib.EwDesc(a=pre.ptr, out=ff.ptr, M=pre.M, C=4 * C, lda=pre.ld, ldo=ff.ld,
                                                     op=lib.EW_GEGLU_FWD), path + ".geglu")
-            self.tape.append(dict(op="geglu", pre=pre, out=ff, name=path + ".geglu"))
+            self.tape.append(GegluRec(path + ".geglu", pre, ff))
         elif self.train:
             # one launch: the GEGLU epilogue also stores proj(x) for the backward (and norm3 folds into it when h2's producer
             # left row statistics)
             pre = self.act(h.B, h.H, h.W, 8 * C, path + ".ff1")
             ff = self.ln_gemm(h2, path + ".norm3", path + ".ff1", 8 * C, geglu=True, geglu_pre=pre)
-            self.tape.append(dict(op="geglu", pre=pre, out=ff, name=path + ".geglu"))
+            self.tape.append(GegluRec(path + ".geglu", pre, ff))
         else:
             grp = self._lora_group([path + ".ff.net.0.proj"])
             if grp is not None:
@@ -788,8 +870,8 @@ class UNetPlan:
                 D = dims.pop()
                 vb = self.w.kv_all_vbase
                 self.vt_all_heads = vb // D
-                Dp, ldt = (D + 63) // 64 * 64, (self.ctx_len + 63) // 64 * 64
-                self.vt_all = self.arena.alloc((B, self.vt_all_heads, Dp, ldt), torch.bfloat16, "attn2_vt_all")
+                Dp, ldt = head_t(D, self.ctx_len)
+                self.vt_all =self.arena.alloc((B, self.vt_all_heads, Dp, ldt), torch.bfloat16, "attn2_vt_all")
                 self.add(lib.OP_TRANSPOSE_HEADS, lib.TransposeDesc(
                     src=self.kv_all.ptr + 2 * vb, dst=self.vt_all.ptr, B=B, H=self.vt_all_heads, T=self.ctx_len,
                     ld=self.kv_all.ld, ldt=ldt, D=D), "attn2_vt_all")
@@ -815,7 +897,7 @@ class UNetPlan:
                 skips.append(h)
             if not final:
                 p = f"{path}.downsamplers.0.conv"
-                h = self.gemm(h, p, cout, p, conv={"stride": 2}, lora_paths=[p])
+                h = self.gemm(h, p, cout, p, conv=Conv3(stride=2), lora_paths=[p])
                 skips.append(h)
             self.block_out[path] = h
         mp = "mid_block"
@@ -837,452 +919,20 @@ class UNetPlan:
                     h = self._transformer(h, f"{path}.attentions.{j}", rtl[i], rheads[i])
             if not final:
                 p = f"{path}.upsamplers.0.conv"
-                h = self.gemm(h, p, cout, p, conv={"xform": 1}, lora_paths=[p])
+                h = self.gemm(h, p, cout, p, conv=Conv3(xform=1), lora_paths=[p])
             self.block_out[path] = h
         assert not skips
         g = self.groupnorm(h, "conv_norm_out", cfg.norm_eps, 1, "conv_norm_out")
-        self.skinny(g, self.w.ptr("conv_out.w"), cfg.out_channels, 9 * g.C, {}, g.M, g.H, g.W, "conv_out",
+        self.skinny(g, self.w.ptr("conv_out.w"), cfg.out_channels, 9 * g.C, Conv3(), g.M, g.H, g.W, "conv_out",
                     out=self.io["eps"], bias_ptr=self.w.ptr("conv_out.b"), out_kind=1)
         if self.train:
-            self.tape.append(dict(op="conv_out", x=g, name="conv_out"))
+            self.tape.append(ConvOutRec(g))
 
 
-# ======================================================================================================
-# backward through the frozen net into the LoRA adapters (loss.backward(), train_lora_xl.py:345)
-# ======================================================================================================
-class BackwardPlan:
-    """Reverse walk over a train-mode UNetPlan's tape.  Gradients flow only for samples [b0, b0+nb): in the
-    reference's CFG pair the unconditional half receives an exactly-zero gradient (d/du of u + 1*(t-u) is
-    1 - 1 = 0 in bf16, train_util.py:250-253 with guidance_scale=1), so its backward is skipped.
+def __getattr__(name):
+    """`from sliders_amd.planner import BackwardPlan` keeps working: it lives in backward.py, which imports this module"""
+    if name != "BackwardPlan":
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    from .backward import BackwardPlan
+    return BackwardPlan
 
-    Every backward-data product reuses slh_gemm with the pre-transposed frozen weights; LoRA gradients are
-    skinny reductions (slh_skinny with the up matrix as a [K][4] down-projection of dY, slh_lora_wgrad)."""
-
-    def __init__(self, fwd: UNetPlan, b0: int, nb: int, one_ptr: int):
-        assert fwd.train and fwd.lora is not None
-        self.f = fwd
-        self.cfg, self.w, self.arena, self.zarena, self.lora = fwd.cfg, fwd.w, fwd.arena, fwd.zarena, fwd.lora
-        self.b0, self.nb = b0, nb
-        self.one_ptr = one_ptr
-        self.scale_ptr = fwd.lora_scale_ptr
-        self.sw = fwd.sw                      # one environment for a forward plan and its backward
-        self.prog = lib.Program()
-        self._splitk_tickets = None
-        self._g: Dict[int, Act] = {}          # base buffer ptr -> full-width gradient buffer (nb samples)
-        self._written = set()
-        zmark = self.zarena.mark()
-        H, W = fwd.H, fwd.W
-        self.deps_pix = self.arena.alloc((nb * H * W, 4), torch.float32, "bwd.deps_pix")
-        # launches that do not sit on the dependency chain are collected and issued as ONE batched launch each
-        # (slh_batch_desc): the head transposes of FORWARD activations (K^T, Q^T of every attention layer) at the head of the
-        # program, and the adapters' weight gradients at its tail - except the up-gradient (dB) of a module whose output
-        # gradient buffer doubles as its residual input's (alias_grad): later accumulations would change dY under it
-        # dO^T of a self-attention (for dK / dV) comes out of the backward-data product that produces dO (vt_out + vt_also_c)
-        # instead of a transpose launch: attention output buffer -> (heads, Tq), filled from the tape; -> (buffer, ldt) once made
-        self._wants_dot: Dict[int, Tuple[int, int]] = {}
-        self._dot_made: Dict[int, Tuple] = {}
-        for rec in fwd.tape:
-            if rec["op"] == "attn" and rec["k"].buf.ptr not in fwd.nograd_kv and not self.sw.bwd_dot_launch:
-                self._wants_dot[rec["o"].buf.ptr] = (rec["heads"], rec["q"].HW)
-        # GEGLU outputs -> their tape record: the backward-data product of the Linear that consumes one writes d(proj) itself
-        self._geglu_of: Dict[int, dict] = {}
-        if not self.sw.bwd_unfused_geglu:
-            for rec in fwd.tape:
-                if rec["op"] == "geglu":
-                    self._geglu_of[rec["out"].buf.ptr] = rec
-        self._tr_batch: List = []
-        self._wg_batch: Dict[int, List] = {4: [], 12: []}
-        self._keep: List = []            # device tables of the batched launches
-        self.batched = not self.sw.bwd_unbatched
-        # weight gradients reduced over their M splits in a fixed order (slabs + tickets) instead of fp32 atomics: the LoRA
-        # gradient buffer is bit-reproducible.  SLIDERS_WGRAD_ATOMIC=1: the old form (A/B)
-        self.wgrad_fixed_order = not self.sw.wgrad_atomic
-        self.fuse_u = not self.sw.bwd_unfused_u
-        self._uses_up_t = False
-        self._walk()
-        dev = None if self.arena.virtual else fwd.lora.params.device
-        for R, descs in self._wg_batch.items():
-            if descs:
-                if self.wgrad_fixed_order:
-                    for d in descs:
-                        d.slabs = 8                 # marker: slab geometry (the workspace is the batch's)
-                bd, keep = lib.batch_table(lib.OP_WGRAD_BATCH, descs, dev, arg=R)
-                if self.wgrad_fixed_order:
-                    # one slab of 256 R floats and one ticket per workgroup: the M splits of a column block meet in a fixed order
-                    bd.slabs = self.arena.alloc((bd.total, 256 * R), torch.float32, f"bwd.wgrad_slabs_R{R}").ptr
-                    bd.tickets = self.zarena.alloc((bd.total,), torch.int32, f"bwd.wgrad_tickets_R{R}").ptr
-                self._keep.append(keep)
-                self.prog.add(lib.OP_WGRAD_BATCH, bd, f"bwd.wgrad_batch_R{R}")
-        zend = self.zarena.mark()
-        head = lib.Program()
-        if zend > zmark:
-            p, n = self.zarena.region(zmark, zend)
-            head.memset(p, n, 0, "zero_bwd_stats")
-        if self._uses_up_t:
-            if self.arena.virtual:
-                gd = lib.Gather16Desc(src=0x1000, idx=0x1000, out=0x1000, n=1)
-            else:
-                gd = lib.Gather16Desc(src=fwd.lora.params.data_ptr(), idx=fwd.lora.up_t_index.data_ptr(),
-                                      out=fwd.lora.up_t.data_ptr(), n=fwd.lora.up_t.numel())
-            head.add(lib.OP_GATHER16, gd, "bwd.up_t")
-        if self._tr_batch:
-            bd, keep = lib.batch_table(lib.OP_TRANSPOSE_BATCH, self._tr_batch, dev)
-            self._keep.append(keep)
-            head.add(lib.OP_TRANSPOSE_BATCH, bd, "bwd.kt_qt_batch")
-        head.extend(self.prog)
-        self.prog = head
-
-    # ---- gradient buffers ------------------------------------------------------------------------
-    def _sl(self, a: Act) -> Act:
-        return a.sample(self.b0, self.nb)
-
-    def grad(self, a: Act, write: bool = True):
-        """(gradient view matching `a` for the selected samples, accumulate?)"""
-        base = a.buf.ptr
-        g = self._g.get(base)
-        if g is None:
-            rows = self.nb * a.HW
-            buf = self.arena.alloc((rows, a.ld), torch.bfloat16, "g:" + a.name)
-            g = Act(buf.ptr, self.nb, a.H, a.W, a.ld, a.ld, buf, "g:" + a.name)
-            self._g[base] = g
-        c0 = ((a.ptr - a.buf.ptr) // 2) % a.ld
-        view = Act(g.ptr + 2 * c0, self.nb, a.H, a.W, a.C, g.ld, g.buf, g.name)
-        key = (base, c0, a.C)
-        acc = key in self._written
-        if write:
-            self._written.add(key)
-        return view, acc
-
-    def has_grad(self, a: Act) -> bool:
-        """True once any column range of a's buffer has received a gradient."""
-        return any(k[0] == a.buf.ptr for k in self._written)
-
-    def alias_grad(self, a: Act, g: Act):
-        self._g[a.buf.ptr] = Act(g.ptr, g.B, g.H, g.W, a.ld, g.ld, g.buf, g.name)
-        self._written.add((a.buf.ptr, 0, a.C))
-
-    # ---- op emitters -----------------------------------------------------------------------------
-    def _ew(self, op, a: Act, out: Act, b: Optional[Act] = None, name="", C=None, iarg=0, iarg2=0, M=None):
-        d = lib.EwDesc(a=a.ptr, b=b.ptr if b else 0, out=out.ptr, M=M if M is not None else a.M, C=C or a.C, lda=a.ld,
-                       ldb=b.ld if b else 0, ldo=out.ld, op=op, iarg=iarg, iarg2=iarg2)
-        self.prog.add(lib.OP_ELEMENTWISE, d, name)
-
-    def add_into(self, dst_fwd: Act, src: Act, name: str):
-        g, acc = self.grad(dst_fwd)
-        if acc:
-            self._ew(lib.EW_ADD, g, g, src, name + ".add")
-        else:
-            self._ew(lib.EW_COPY, src, g, name=name + ".copy")
-
-    def _walk(self):
-        f = self.f
-        for rec in reversed(f.tape):
-            getattr(self, "_b_" + rec["op"])(rec)
-
-    def _b_conv_out(self, rec):
-        x = rec["x"]
-        gx, acc = self.grad(x)
-        d = lib.LoraCdgradDesc(u=self.deps_pix.ptr, a_down=self.w.ptr("conv_out.w"), scale=self.one_ptr, gx=gx.ptr,
-                               batch=self.nb, hl=x.H, wl=x.W, ho=x.H, wo=x.W, stride=1, cin=x.C, ldu=4, ldgx=gx.ld,
-                               accumulate=1 if acc else 0)
-        self.prog.add(lib.OP_LORA_CONV_DGRAD, d, "bwd.conv_out")
-
-    def _b_gn(self, rec):
-        x0, x1 = _src_parts(rec["x"])
-        y = rec["out"]
-        if not self.has_grad(y):
-            return
-        need0 = x0.buf.ptr not in self.f.nograd
-        need1 = x1 is not None and x1.buf.ptr not in self.f.nograd
-        if not (need0 or need1):
-            return
-        gy, _ = self.grad(y, write=False)
-        G = self.cfg.norm_num_groups
-        bst = self.arena.alloc((self.nb, G, 2), torch.float32, "bwd." + rec["name"] + ".bstats")
-        prow, ntick = lib.gn_workspace(x0.C + (x1.C if x1 is not None else 0), x0.HW, G)
-        bpart = self.arena.alloc((self.nb, prow, G, 2), torch.float32, "bwd." + rec["name"] + ".bpartial")
-        btick = self.zarena.alloc((self.nb, ntick), torch.float32, "bwd." + rec["name"] + ".bticket")
-        x0s = self._sl(x0)
-        x1s = self._sl(x1) if x1 is not None else None
-        g0, a0 = self.grad(x0) if need0 else (None, False)
-        g1, a1 = self.grad(x1) if need1 else (None, False)
-        st = rec["stats"].ptr + 4 * self.b0 * G * 2
-        d = lib.GnBwdDesc(x0=x0s.ptr, x1=x1s.ptr if x1s else 0, gamma=self.w.ptr(rec["wname"] + ".g"),
-                          beta=self.w.ptr(rec["wname"] + ".b"), stats=st, bstats=bst.ptr, dy=gy.ptr,
-                          dx0=g0.ptr if g0 else 0, dx1=g1.ptr if g1 else 0, ldx0=x0s.ld, ldx1=x1s.ld if x1s else 0,
-                          c0=x0.C, c1=x1.C if x1 is not None else 0, batch=self.nb, hw=x0.HW, groups=G, lddy=gy.ld,
-                          lddx0=g0.ld if g0 else 0, lddx1=g1.ld if g1 else 0, eps=rec["eps"], act=rec["act"],
-                          accumulate0=1 if a0 else 0, accumulate1=1 if a1 else 0, bpartial=bpart.ptr, bticket=btick.ptr)
-        self.prog.add(lib.OP_GN_BWD_STATS, d, "bwd." + rec["name"] + ".stats")
-        self.prog.add(lib.OP_GN_BWD_APPLY, d, "bwd." + rec["name"] + ".apply")
-
-    def _b_ln(self, rec):
-        x, y = rec["x"], rec["out"]
-        if not self.has_grad(y):
-            return
-        gy, _ = self.grad(y, write=False)
-        gx, acc = self.grad(x)
-        xs = self._sl(x)
-        mr = rec["mr"].ptr + 4 * 2 * self.b0 * x.HW
-        d = lib.LnBwdDesc(x=xs.ptr, gamma=self.w.ptr(rec["wname"] + ".g"), dy=gy.ptr, mean_rstd=mr, dx=gx.ptr,
-                          M=xs.M, C=x.C, ldx=xs.ld, lddy=gy.ld, lddx=gx.ld, accumulate=1 if acc else 0)
-        self.prog.add(lib.OP_LAYERNORM_BWD, d, "bwd." + rec["name"])
-
-    def _b_geglu(self, rec):
-        pre, out = rec["pre"], rec["out"]
-        if not self.has_grad(out):
-            return
-        go, _ = self.grad(out, write=False)
-        gp, acc = self.grad(pre)
-        assert not acc
-        ps = self._sl(pre)
-        self._ew(lib.EW_GEGLU_BWD, ps, gp, go, "bwd." + rec["name"], C=out.C)
-
-    def _transpose(self, src: Act, heads: int, T: int, name: str, forward_data: bool = False):
-        """forward_data: src is an activation of the forward pass (final before the backward starts): the transpose joins
-        the one batched launch at the head of the program instead of sitting in the chain."""
-        D = src.C // heads
-        ldt = (T + 63) // 64 * 64
-        t = self.arena.alloc((self.nb, heads, (D + 63) // 64 * 64, ldt), torch.bfloat16, name)
-        d = lib.TransposeDesc(src=src.ptr, dst=t.ptr, B=self.nb, H=heads, T=T, ld=src.ld, ldt=ldt, D=D)
-        if forward_data and self.batched:
-            self._tr_batch.append(d)
-        else:
-            self.prog.add(lib.OP_TRANSPOSE_HEADS, d, name)
-        return t, ldt
-
-    def _b_attn(self, rec):
-        q, k, v, o = rec["q"], rec["k"], rec["v"], rec["o"]
-        if not self.has_grad(o):
-            return
-        heads, Tk, Tq = rec["heads"], rec["Tk"], q.HW
-        go, _ = self.grad(o, write=False)
-        need_dkv = 1 if (k.buf.ptr not in self.f.nograd_kv) else 0
-        qs, ks, vs, os_ = self._sl(q), self._sl(k), self._sl(v), self._sl(o)
-        kt, ldkt = self._transpose(ks, heads, Tk, "bwd." + rec["name"] + ".kt", forward_data=True)
-        gq, aq = self.grad(q)
-        assert not aq
-        delta = self.arena.alloc((self.nb * heads * Tq + 64,), torch.float32, "bwd." + rec["name"] + ".delta")
-        d = lib.AttnBwdDesc(q=qs.ptr, k=ks.ptr, v=vs.ptr, o=os_.ptr, d_o=go.ptr, kt=kt.ptr,
-                            lse=rec["lse"].ptr + 4 * self.b0 * heads * Tq, delta=delta.ptr, dq=gq.ptr,
-                            B=self.nb, H=heads, Tq=Tq, Tk=Tk, ldq=qs.ld, ldk=ks.ld, ldv=vs.ld, ldo=os_.ld, lddo=go.ld,
-                            ldkt=ldkt, lddq=gq.ld, scale=(q.C // heads) ** -0.5, need_dkv=need_dkv, D=q.C // heads)
-        if need_dkv:
-            qt, ldqt = self._transpose(qs, heads, Tq, "bwd." + rec["name"] + ".qt", forward_data=True)
-            made = self._dot_made.get(o.buf.ptr)
-            if made is not None:
-                dot = made[0]                 # written head-transposed by the product that produced dO
-                assert made[1] == ldqt
-            else:
-                dot, _ = self._transpose(go, heads, Tq, "bwd." + rec["name"] + ".dot")
-            gk, ak = self.grad(k)
-            gv, av = self.grad(v)
-            assert not ak and not av
-            d.qt, d.dot, d.ldqt, d.dk, d.dv, d.lddk, d.lddv = qt.ptr, dot.ptr, ldqt, gk.ptr, gv.ptr, gk.ld, gv.ld
-        self.prog.add(lib.OP_ATTN_BWD, d, "bwd." + rec["name"])
-
-    def _tile(self, d, name, vt=None):
-        choose_tile(d, vt=vt, backward=True)
-        provision_splitk(self, d, name)
-
-    def _wgrad(self, d, name: str, defer: bool):
-        if defer and self.batched:
-            self._wg_batch[d.R].append(d)
-        else:
-            if self.wgrad_fixed_order:
-                nb = lib.wgrad_single_blocks(d)
-                d.slabs = self.arena.alloc((nb, 256 * d.R), torch.float32, name + ".slabs").ptr
-                d.tickets = self.zarena.alloc((nb,), torch.int32, name + ".tickets").ptr
-            self.prog.add(lib.OP_WGRAD, d, name)
-
-    def _b_gemm(self, rec):
-        y = rec["out"]
-        if not self.has_grad(y):
-            return
-        name = "bwd." + rec["name"]
-        gy, _ = self.grad(y, write=False)
-        x0, x1 = _src_parts(rec["x"])
-        need0 = x0.buf.ptr not in self.f.nograd
-        need1 = x1 is not None and x1.buf.ptr not in self.f.nograd
-        self._b_gemm_residual(rec, gy, name)
-        if rec.get("temb_path") and self.lora.temb_entries:
-            self._b_gemm_temb(rec, gy, name)
-        U, up_t_off, dA_after = self._b_gemm_lora(rec, gy, name, need0 or need1) if rec["grp"] is not None else (None, None, [])
-        if not (need0 or need1):
-            return
-        if rec["conv"] is None:
-            self._b_gemm_linear(rec, gy, name, need0, need1, U, up_t_off, dA_after)
-        else:
-            self._b_gemm_conv(rec, gy, name, U)
-
-    def _b_gemm_residual(self, rec, gy: Act, name: str):
-        """residual branch: d(out)/d(residual) = identity"""
-        r = rec["residual"]
-        if r is not None and r.buf.ptr not in self.f.nograd:
-            if r.buf.ptr not in self._g and r.ld == r.C and gy.ld == gy.C and r.C == gy.C:
-                self.alias_grad(r, gy)
-            else:
-                self.add_into(r, gy, name + ".res")
-
-    def _b_gemm_temb(self, rec, gy: Act, name: str):
-        """time-embedding add: gradient w.r.t. the per-sample bias feeds the time_emb_proj adapter"""
-        f, N, Ho, Wo = self.f, rec["N"], rec["Ho"], rec["Wo"]
-        path = rec["temb_path"]
-        i = f.w.resnet_paths.index(path)
-        e = self.lora.temb_entries[i]
-        gsum = self.zarena.alloc((self.nb, N), torch.float32, name + ".gtemb")
-        self._ew(lib.EW_COLSUM, gy, Act(gsum.ptr, self.nb, 1, 1, N, N, gsum), name=name + ".colsum", iarg2=Ho * Wo)
-        ted = self.cfg.time_embed_dim
-        L4 = f.temb_lora_T.shape[1]
-        for s in range(self.nb):
-            d = lib.TembLoraBwdDesc(g=gsum.ptr + 4 * s * N, t=f.temb_lora_T.ptr + 4 * ((self.b0 + s) * L4 + 4 * i),
-                                    up=self.lora.up_ptr(e), emb=f.emb.ptr + 2 * (self.b0 + s) * ted,
-                                    d_up=self.lora.gup_ptr(e), d_down=self.lora.gdown_ptr(e), scale=self.scale_ptr,
-                                    C=N, ted=ted)
-            self.prog.add(lib.OP_TEMB_LORA_BWD, d, name + ".temb_lora")
-
-    def _b_gemm_lora(self, rec, gy: Act, name: str, dgrad: bool):
-        """LoRA: U = dY . B_up per fused member; dB = s dY^T T ; dA = s U^T X.  dgrad: a backward-data product follows.  Returns
-        (U, the offset of the group's k-major up matrices when U comes out of that product - else None -, the down-gradients that
-        must wait for it)."""
-        f = self.f
-        x0, x1 = _src_parts(rec["x"])
-        conv, grp, N, K, r = rec["conv"], rec["grp"], rec["N"], rec["K"], rec["residual"]
-        Ho, Wo = rec["Ho"], rec["Wo"]
-        Ms = self.nb * Ho * Wo
-        dA_after = []
-        ng = len(grp)
-        Ng = N // ng
-        U = self.arena.alloc((Ms, 4 * ng), torch.float32, name + ".U")
-        T = rec["T"]
-        Ts = T.ptr + 4 * self.b0 * (Ho * Wo) * 4 * ng
-        # U = dY . B (the up matrices as a rank-4 down-projection of the output gradient): inside the backward-data GEMM
-        # of a dense module - third operand tile = the k-major copy of B (LoraStore.up_t), written out through lora_t_out
-        # for the down-gradient - unless that product does not exist (no gradient needed upstream)
-        up_t_off = self.lora.up_t_offset(grp) if (self.fuse_u and conv is None and x1 is None and dgrad) else None
-        fused_u = up_t_off is not None          # (split-K included: the slice that arrives last reduces T as well)
-        if not fused_u:
-            for g_i, e in enumerate(grp):
-                d = lib.SkinnyDesc(a0=gy.ptr + 2 * g_i * Ng, w=self.lora.up_ptr(e), out=U.ptr + 4 * 4 * g_i, lda0=gy.ld,
-                                   ca0=Ng, mode=0, stride=1, M=Ms, R=4, K=Ng, ldo=4 * ng, w_kmajor=1)
-                self.prog.add(lib.OP_SKINNY, d, name + f".U{g_i}")
-        d = lib.WgradDesc(z0=gy.ptr, v=Ts, out=self.lora.gup_ptr(grp[0]), scale=self.scale_ptr, ldz0=gy.ld, c0=N,
-                          mode=0, stride=1, M=Ms, R=4, ldv=4 * ng, ldo=4, out_rmajor=0,
-                          vgroup_cols=Ng if ng > 1 else 0)
-        # dY of a module with a residual input may be the residual's gradient buffer too (alias_grad above): it keeps
-        # accumulating after this point, so its up-gradient cannot wait for the batched launch at the tail
-        self._wgrad(d, name + ".dB", defer=r is None or r.buf.ptr in f.nograd)
-        x0s = self._sl(x0)
-        x1s = self._sl(x1) if x1 is not None else None
-        # the down matrices of a fused q|k|v group are adjacent ([12][K]) and so are their U columns: one R = 12 launch
-        # reads X once instead of three times
-        one = ng == 3 and conv is None
-        for g_i, e in enumerate(grp[:1] if one else grp):
-            d = lib.WgradDesc(z0=x0s.ptr, z1=x1s.ptr if x1s else 0, v=U.ptr + 4 * 4 * g_i, out=self.lora.gdown_ptr(e),
-                              scale=self.scale_ptr, ldz0=x0s.ld, ldz1=x1s.ld if x1s else 0, c0=x0.C,
-                              c1=x1.C if x1 is not None else 0, mode=0, stride=1, M=Ms, R=12 if one else 4, ldv=4 * ng,
-                              ldo=K, out_rmajor=1, vgroup_cols=0)
-            if conv is not None:
-                d.mode, d.batch, d.hs, d.ws = 1, self.nb, x0.H, x0.W
-                d.src_xform, d.stride, d.ho, d.wo = conv.get("xform", 0), conv.get("stride", 1), Ho, Wo
-            if fused_u:
-                dA_after.append((d, name + f".dA{g_i}"))            # U is written by the dgrad launch below
-            else:
-                self._wgrad(d, name + f".dA{g_i}", defer=True)      # forward activations and U: final
-        return U, up_t_off, dA_after
-
-    def _b_gemm_linear(self, rec, gy: Act, name: str, need0: bool, need1: bool, U, up_t_off, dA_after):
-        """backward data of a Linear / 1x1 convolution"""
-        x0, x1 = _src_parts(rec["x"])
-        grp, N, Ho, Wo = rec["grp"], rec["N"], rec["Ho"], rec["Wo"]
-        Ms = self.nb * Ho * Wo
-        cin = x0.C + (x1.C if x1 is not None else 0)
-        wT = self.w.ptr(rec["wname"] + ".wT")
-        geglu_rec = self._geglu_of.get(x0.buf.ptr) if (x1 is None and grp is None and not self.has_grad(x0)) else None
-        if geglu_rec is not None and x0.C % 32 == 0:
-            # the Linear behind a GEGLU (ff.net.2): its backward-data product writes d(proj) directly (GEGLU backward in
-            # the epilogue, slh_gemm_desc.geglu = 2) - no d(ff) tensor, no elementwise launch
-            pre = geglu_rec["pre"]
-            gp, pacc = self.grad(pre)
-            assert not pacc
-            ps = self._sl(pre)
-            d = lib.GemmDesc(a0=gy.ptr, w=wT, c=gp.ptr, lda0=gy.ld, ca0=N, mode=0, stride=1, ldw=N, M=Ms, N=cin, K=N,
-                             ldc=gp.ld, rows_per_sample=Ho * Wo, geglu=2, geglu_pre=ps.ptr, ld_pre=ps.ld,
-                             w_layout=1 if self.w.packed else 0)
-            self._tile(d, name)
-            self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-            return
-        if x1 is None:
-            gx, acc = self.grad(x0)
-            tgt, tacc = gx, acc
-        else:
-            tb = self.arena.alloc((Ms, cin), torch.bfloat16, name + ".gxcat")
-            tgt, tacc = Act(tb.ptr, self.nb, x0.H, x0.W, cin, cin, tb), False
-        d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=0,
-                         stride=1, ldw=N, M=Ms, N=cin, K=N, ld_res=tgt.ld, ldc=tgt.ld, rows_per_sample=Ho * Wo,
-                         w_layout=1 if self.w.packed else 0)
-        if grp is not None:
-            d.ld_t, d.lora_up, d.lora_scale = 4 * len(grp), self.lora.down_ptr(grp[0]), self.scale_ptr
-            d.lora_groups, d.lora_rank, d.lora_up_rmajor = 1, 4 * len(grp), 1
-            if up_t_off is not None:
-                self._uses_up_t = True
-                base = 0x2000 if self.arena.virtual else self.lora.up_t.data_ptr()
-                d.lora_down, d.lora_t_out = base + 2 * up_t_off, U.ptr
-            else:
-                d.lora_t = U.ptr
-        want = self._wants_dot.get(x0.buf.ptr) if (x1 is None and not tacc and tgt.ptr == gx.ptr) else None
-        vt = None
-        if want is not None:
-            heads, Tq = want
-            Dh = cin // heads
-            if Dh % 64 == 0 and Tq % 64 == 0 and Ms == self.nb * Tq and cin == x0.C and tgt.ld % 8 == 0:
-                vt = dict(vt_col0=0, vt_D=Dh, vt_heads=heads, vt_tokens=Tq, vt_ld=Tq, vt_also_c=1)
-        self._tile(d, name, vt)
-        if d.vt_out:
-            dot = self.arena.alloc((self.nb, heads, Dh, Tq), torch.bfloat16, name + ".dot")
-            d.vt_out = dot.ptr
-            self._dot_made[x0.buf.ptr] = (dot, Tq)
-        self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-        for dA, nm in dA_after:
-            self._wgrad(dA, nm, defer=True)
-        if x1 is not None:
-            if need0:
-                self.add_into(x0, tgt.cols(0, x0.C), name + ".gx0")
-            if need1:
-                self.add_into(x1, tgt.cols(x0.C, x1.C), name + ".gx1")
-
-    def _b_gemm_conv(self, rec, gy: Act, name: str, U):
-        """backward data of a 3x3 convolution"""
-        x0, x1 = _src_parts(rec["x"])
-        conv, grp, N, Ho, Wo = rec["conv"], rec["grp"], rec["N"], rec["Ho"], rec["Wo"]
-        cin = x0.C
-        wT = self.w.ptr(rec["wname"] + ".wT")
-        assert x1 is None
-        xform, stride = conv.get("xform", 0), conv.get("stride", 1)
-        if xform == 1:     # forward read a nearest-2x upsampled image: dgrad lands on the 2h x 2w grid first
-            HL, WL = 2 * x0.H, 2 * x0.W
-            tb = self.arena.alloc((self.nb * HL * WL, cin), torch.bfloat16, name + ".gx_up")
-            tgt, tacc = Act(tb.ptr, self.nb, HL, WL, cin, cin, tb), False
-        else:
-            HL, WL = x0.H, x0.W
-            tgt, tacc = self.grad(x0)
-        d = lib.GemmDesc(a0=gy.ptr, w=wT, c=tgt.ptr, residual=tgt.ptr if tacc else 0, lda0=gy.ld, ca0=N, mode=1,
-                         batch=self.nb, hs=Ho, ws=Wo, src_xform=2 if stride == 2 else 0, stride=1, ho=HL, wo=WL,
-                         ldw=9 * N, M=self.nb * HL * WL, N=cin, K=9 * N, ld_res=tgt.ld, ldc=tgt.ld,
-                         rows_per_sample=HL * WL, w_layout=1 if self.w.packed else 0)
-        self._tile(d, name)
-        self.prog.add(lib.OP_GEMM, d, name + ".dgrad")
-        if grp is not None:
-            d2 = lib.LoraCdgradDesc(u=U.ptr, a_down=self.lora.down_ptr(grp[0]), scale=self.scale_ptr, gx=tgt.ptr,
-                                    batch=self.nb, hl=HL, wl=WL, ho=Ho, wo=Wo, stride=stride, cin=cin, ldu=4,
-                                    ldgx=tgt.ld, accumulate=1)
-            self.prog.add(lib.OP_LORA_CONV_DGRAD, d2, name + ".lora_dgrad")
-        if xform == 1:
-            gx, acc = self.grad(x0)
-            if acc:
-                t2b = self.arena.alloc((self.nb * x0.HW, cin), torch.bfloat16, name + ".gx_dn")
-                t2 = Act(t2b.ptr, self.nb, x0.H, x0.W, cin, cin, t2b)
-                self._ew(lib.EW_UPSAMPLE_BWD, tgt, t2, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=t2.M)
-                self._ew(lib.EW_ADD, gx, gx, t2, name + ".add")
-            else:
-                self._ew(lib.EW_UPSAMPLE_BWD, tgt, gx, name=name + ".upsample_bwd", iarg=x0.W, iarg2=x0.HW, M=gx.M)

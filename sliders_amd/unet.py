@@ -19,7 +19,8 @@ from .arena import Arena
 from .config import UNetConfig
 from .lora_store import LoraStore
 from .passes import Pass
-from .planner import AttnMapSpec, BackwardPlan, UNetPlan
+from .backward import BackwardPlan
+from .planner import AttnMapSpec, UNetPlan
 from .weights import WeightStore
 
 
@@ -279,8 +280,10 @@ class _VirtualLora:
 
     def __init__(self, s: LoraStore):
         self._s = s
-        self.temb_tcol = _FakeTensor()
         self.params = _FakeTensor()
+
+    def temb_tcol_table(self, w):
+        return _FakeTensor()
 
     def __getattr__(self, name):
         if name == "_s":
