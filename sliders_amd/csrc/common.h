@@ -190,18 +190,69 @@ __device__ __forceinline__ bool last_arriver(unsigned* ticket, unsigned expected
     return *lds_flag != 0;
 }
 
+// ---- GroupNorm statistics: workspace, launch geometry, reductions, finish (norm.hip, vae.hip) --------------------------
+// Workspace of the statistics launches (slh_gn_desc.partial / .ticket in include/sliders_hip.h describes it for callers; this
+// struct is the only code that knows it).  The row blocks of a sample form clusters of GN_CLUSTER:
+//   partial : [batch][row_blocks + clusters][groups][2]   a sample's level-1 pairs (one per row block), then its cluster pairs
+//   ticket  : [batch][1 + clusters]                       ticket[0] = level 2, ticket[1 + c] = cluster c
+constexpr int GN_CLUSTER = 16;
+struct GnWorkspace {
+    int row_blocks;
+    __host__ __device__ int clusters() const { return (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER; }
+    __host__ __device__ int partial_rows() const { return row_blocks + clusters(); }      // per sample
+    __host__ __device__ int ticket_count() const { return 1 + clusters(); }               // per sample
+    __host__ __device__ int cluster_of(int rb) const { return rb / GN_CLUSTER; }
+    __host__ __device__ int first(int cl) const { return cl * GN_CLUSTER; }               // a cluster's first row block ...
+    __host__ __device__ int members(int cl) const { return min(GN_CLUSTER, row_blocks - first(cl)); }     // ... and how many it has
+    // sample b's partial rows and its tickets
+    __host__ __device__ float* rows(float* partial, int b, int groups) const { return partial + (long)b * partial_rows() * groups * 2; }
+    __host__ __device__ unsigned* tickets(unsigned* ticket, int b) const { return ticket + (long)b * ticket_count(); }
+    // group g's pair of a sample's partial row i: i < row_blocks is row block i's (level 1), cluster_row(c) is cluster c's
+    __host__ __device__ int cluster_row(int cl) const { return row_blocks + cl; }
+    __host__ __device__ static float* pair(float* rows, int groups, int i, int g) { return rows + ((long)i * groups + g) * 2; }
+    __host__ __device__ static unsigned* level2_ticket(unsigned* tickets) { return tickets; }
+    __host__ __device__ static unsigned* cluster_ticket(unsigned* tickets, int cl) { return tickets + 1 + cl; }
+};
+
+// Launch geometry of the row-block kernels, computed once on the host (gn_geom) and handed to the kernels by value; what follows
+// from it (C, threads, LDS size and slots, the workspace) is asked of it.  A thread owns one chunk of EPC consecutive channels (one
+// 16-byte access: 8 bf16, 4 fp32) of every rpi-th row of its block; cg channels per group; lpg: see gn_geom.
+template <int EPC>
+struct GnGeom {
+    int nchunk, rpi, rows_per_block, cg, lpg, row_blocks;
+    __host__ __device__ int C() const { return nchunk * EPC; }
+    __host__ __device__ int threads() const { return nchunk * rpi; }
+    __host__ __device__ int* flag(float* lds) const { return (int*)(lds + 2 * rpi * C()); }      // last_arriver's slot, behind gn_block_reduce's
+    __host__ __device__ unsigned lds_bytes() const { return (unsigned)((2 * rpi * C() + 4) * sizeof(float)); }
+    __host__ __device__ GnWorkspace ws() const { return GnWorkspace{row_blocks}; }
+    static int rpi_of(int C) { return C / EPC >= 256 ? 1 : 256 / (C / EPC); }
+};
+template <int EPC>
+inline GnGeom<EPC> gn_geom(int C, int hw, int groups, int rows_per_block) {
+    GnGeom<EPC> g;
+    g.nchunk = C / EPC;
+    g.rpi = GnGeom<EPC>::rpi_of(C);
+    g.rows_per_block = rows_per_block;
+    g.row_blocks = (hw + rows_per_block - 1) / rows_per_block;
+    g.cg = C / groups;
+    g.lpg = 1;                                   // lanes that share one group in the fixed-order reductions
+    while (g.lpg < 16 && 2 * g.lpg * groups <= g.threads()) g.lpg *= 2;
+    return g;
+}
+
 // Fixed-order reduction of per-thread, per-channel (s, q) pairs to per-group pairs inside one workgroup.
-// lds: [2][rpi * C] floats.  Thread (chunk, rl) owns CH consecutive channels; afterwards the threads t = g * lpg
+// lds: [2][rpi * C] floats.  Thread (chunk, rl) owns EPC consecutive channels; afterwards the threads t = g * lpg
 // (g < groups) hold group g's sums in (S, Q) and the function returns true for exactly those threads.  The order of
 // every addition is a function of the launch geometry only - no LDS / global atomics (they commit in arrival order).
-template <int CH>
-__device__ __forceinline__ bool gn_block_reduce(float* lds, int C, int cg, int groups, int rpi, int lpg, int chunk, int rl,
+template <int EPC>
+__device__ __forceinline__ bool gn_block_reduce(float* lds, const GnGeom<EPC>& geo, int groups, int chunk, int rl,
                                                 const float* s, const float* q, float& S, float& Q) {
+    const int C = geo.C(), cg = geo.cg, rpi = geo.rpi, lpg = geo.lpg;
     float* ls = lds;
     float* lq = lds + rpi * C;
-    const int base = rl * C + chunk * CH;
+    const int base = rl * C + chunk * EPC;
 #pragma unroll
-    for (int e = 0; e < CH; e += 4) {
+    for (int e = 0; e < EPC; e += 4) {
         *(f32x4*)(ls + base + e) = f32x4{s[e], s[e + 1], s[e + 2], s[e + 3]};
         *(f32x4*)(lq + base + e) = f32x4{q[e], q[e + 1], q[e + 2], q[e + 3]};
     }
@@ -253,31 +304,44 @@ __device__ __forceinline__ void gn_combine_partials(const float* partial, int co
     S = a; Q = b;
 }
 
-// Two-level fixed-order reduction of one sample's published pairs (GroupNorm statistics kernels).  The row blocks of a
-// sample form clusters of GN_CLUSTER; the last block to arrive in a cluster adds its cluster's pairs (level 1) and
-// publishes one pair per group, the last CLUSTER to finish adds those (level 2).  Each level is one batch of 16 loads
-// per lane, so the serial tail behind the last workgroup is two L2-bypassing round trips, whatever the tensor size
-// (a flat combine of 1024 row blocks cost 50 us of dependent loads).
-//   part   : [row_blocks + nclusters][groups][2]   level-1 pairs, then level-2 pairs
-//   ticket : [1 + nclusters]                       ticket[0] = level 2, ticket[1 + c] = cluster c
-// Returns true in the threads t = g * lpg (g < groups) of the ONE workgroup that ends up with the sample's totals.
-constexpr int GN_CLUSTER = 16;
-__device__ __forceinline__ bool gn_two_level_reduce(float* part, unsigned* ticket, int row_blocks, int rb, int groups, int lpg,
+// Two-level fixed-order reduction of one sample's published pairs (GroupNorm statistics kernels).  The last block to arrive
+// in a cluster adds its cluster's pairs (level 1) and publishes one pair per group, the last CLUSTER to finish adds those
+// (level 2).  Each level is one batch of 16 loads per lane, so the serial tail behind the last workgroup is two L2-bypassing
+// round trips, whatever the tensor size (a flat combine of 1024 row blocks cost 50 us of dependent loads).
+// Every thread of the workgroup calls these (they hold last_arriver); g = tid / lpg.
+//
+// Level 1: row block rb publishes its pairs and takes its cluster's ticket (rows, tickets: the sample's, GnWorkspace).  True
+// (workgroup-uniform) in the cluster's last arriver, which then holds the cluster's sums in (S, Q) in the threads t = g * lpg
+// (g < groups).
+__device__ __forceinline__ bool gn_cluster_reduce(const GnWorkspace ws, float* rows, unsigned* tickets, int rb, int groups, int lpg, int g,
+                                                  bool owner, float S1, float Q1, int* lds_flag, double& S, double& Q) {
+    const int cl = ws.cluster_of(rb);
+    if (owner) store_pair_sc1(ws.pair(rows, groups, rb, g), S1, Q1);
+    const int members = ws.members(cl);
+    if (!last_arriver(ws.cluster_ticket(tickets, cl), (unsigned)members, lds_flag)) return false;
+    gn_combine_partials(ws.pair(rows, groups, ws.first(cl), 0), members, groups, lpg, S, Q);
+    return true;
+}
+// Both levels.  Returns true in the threads t = g * lpg (g < groups) of the ONE workgroup that ends up with the sample's totals.
+__device__ __forceinline__ bool gn_two_level_reduce(const GnWorkspace ws, float* rows, unsigned* tickets, int rb, int groups, int lpg,
                                                     bool owner, float S1, float Q1, int* lds_flag, double& S, double& Q) {
     const int tid = threadIdx.x;
     const int g = tid / lpg;
-    const int ncl = (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER;
-    const int cl = rb / GN_CLUSTER;
-    if (owner) store_pair_sc1(part + ((long)rb * groups + g) * 2, S1, Q1);
-    const int first = cl * GN_CLUSTER;
-    const int members = min(GN_CLUSTER, row_blocks - first);
-    if (!last_arriver(ticket + 1 + cl, (unsigned)members, lds_flag)) return false;
-    gn_combine_partials(part + (long)first * groups * 2, members, groups, lpg, S, Q);
-    if (ncl == 1) return g < groups && (tid & (lpg - 1)) == 0;
-    if (g < groups && (tid & (lpg - 1)) == 0) store_pair_sc1(part + ((long)(row_blocks + cl) * groups + g) * 2, (float)S, (float)Q);
-    if (!last_arriver(ticket, (unsigned)ncl, lds_flag)) return false;
-    gn_combine_partials(part + (long)row_blocks * groups * 2, ncl, groups, lpg, S, Q);
+    if (!gn_cluster_reduce(ws, rows, tickets, rb, groups, lpg, g, owner, S1, Q1, lds_flag, S, Q)) return false;
+    if (ws.clusters() == 1) return g < groups && (tid & (lpg - 1)) == 0;
+    if (g < groups && (tid & (lpg - 1)) == 0) store_pair_sc1(ws.pair(rows, groups, ws.cluster_row(ws.cluster_of(rb)), g), (float)S, (float)Q);
+    if (!last_arriver(ws.level2_ticket(tickets), (unsigned)ws.clusters(), lds_flag)) return false;
+    gn_combine_partials(ws.pair(rows, groups, ws.cluster_row(0), 0), ws.clusters(), groups, lpg, S, Q);
     return g < groups && (tid & (lpg - 1)) == 0;
+}
+
+// Shifted sums (S, Q) over the hw * cg elements of a (sample, group), taken about `pivot`, to (mean, rstd).  The one place where
+// the pass is "two-pass-safe in one pass" (gn_stats_kernel, norm.hip): every GroupNorm form ends here, in double.
+__device__ __forceinline__ f32x2 gn_finish(double S, double Q, int hw, int cg, double pivot, float eps) {
+    const double n = (double)hw * (double)cg;
+    const double m = S / n;
+    const double var = fmax(Q / n - m * m, 0.0);
+    return f32x2{(float)(pivot + m), (float)(1.0 / sqrt(var + (double)eps))};
 }
 
 // ---- host side -------------------------------------------------------------------------------

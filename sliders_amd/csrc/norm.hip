@@ -12,24 +12,13 @@ namespace {
 
 constexpr int GN_ITERS = 8;  // rows per thread per block
 
-struct GnGeom {
-    int C, nchunk, rpi, threads, rows_per_block, row_blocks, cg, lpg;
-    unsigned lds_bytes;
-};
+typedef GnGeom<8> Geom;       // bf16: 8 channels per 16-byte chunk
+static Geom gn_geom(int C, int hw, int groups) { return ::gn_geom<8>(C, hw, groups, Geom::rpi_of(C) * GN_ITERS); }
 
-static GnGeom gn_geom(int c0, int c1, int hw, int groups) {
-    GnGeom g;
-    g.C = c0 + c1;
-    g.nchunk = g.C / 8;
-    g.rpi = g.nchunk >= 256 ? 1 : 256 / g.nchunk;
-    g.threads = g.nchunk * g.rpi;
-    g.rows_per_block = g.rpi * GN_ITERS;
-    g.row_blocks = (hw + g.rows_per_block - 1) / g.rows_per_block;
-    g.cg = g.C / groups;
-    g.lpg = 1;                                   // lanes that share one group in the fixed-order reductions
-    while (g.lpg < 16 && 2 * g.lpg * groups <= g.threads) g.lpg *= 2;
-    g.lds_bytes = (unsigned)((2 * g.threads * 8 + 4) * sizeof(float));
-    return g;
+// channel c of pixel `row` of the two-source input (slh_gn_desc and slh_gn_bwd_desc: x0 | x1, the concat never materialised)
+template <class Desc>
+__device__ __forceinline__ const __bf16* gn_src(const Desc& d, long row, int c) {
+    return c < d.c0 ? (const __bf16*)d.x0 + row * d.ldx0 + c : (const __bf16*)d.x1 + row * d.ldx1 + (c - d.c0);
 }
 
 // Forward statistics: one-shot workgroups (all of a workgroup's rows in flight at once: the launch streams at full width) whose
@@ -37,22 +26,23 @@ static GnGeom gn_geom(int c0, int c1, int hw, int groups) {
 // pair per group); the few cluster pairs of a sample (<= ~65) are added - again in index order - by every workgroup of
 // slh_gn_apply in its prologue, which also leaves (mean, rstd) in d.stats.  Round 3 combined the cluster pairs under a second
 // ticket level inside the statistics launch: that serial tail (publish - ticket - dependent loads) was ~1/3 of the launch.
-__device__ __forceinline__ const __bf16* gn_src(const slh_gn_desc& d, long row, int c) {
-    return c < d.c0 ? (const __bf16*)d.x0 + row * d.ldx0 + c : (const __bf16*)d.x1 + row * d.ldx1 + (c - d.c0);
-}
-
+//
 // Statistics of one (sample, group): stats[b][g] = (mean, rstd).  Two-pass-safe in one pass: the sums run over
 // x - K_g with K_g = the group's first element (an actual sample of the data, so |mean - K_g| is a few standard
 // deviations at most and E[(x-K)^2] - E[x-K]^2 does not cancel, whatever DC offset the activations carry).
-__global__ void gn_stats_kernel(const slh_gn_desc d, int nchunk, int rpi, int rows_per_block, int cg, int lpg, int row_blocks) {
+// (The geometry arrives here as its six fields, not as the Geom the other kernels take: the bytes of the argument block are the
+// same, but hipcc schedules this kernel's eight row loads differently behind a by-reference aggregate - 80 VGPRs instead of 94,
+// addresses and loads interleaved - and this is the launch whose streaming width was tuned.)
+__global__ void gn_stats_kernel(const slh_gn_desc d, int nchunk, int rpi_, int rows_per_block, int cg_, int lpg_, int row_blocks) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
+    const Geom geo = {nchunk, rpi_, rows_per_block, cg_, lpg_, row_blocks};
     const int tid = threadIdx.x;
-    const int chunk = tid % nchunk, rl = tid / nchunk;
+    const int rpi = geo.rpi, cg = geo.cg, lpg = geo.lpg;
+    const int chunk = tid % geo.nchunk, rl = tid / geo.nchunk;
     const int c = chunk * 8;
     const int b = blockIdx.y;
-    const int C = nchunk * 8;
-    const int r0 = blockIdx.x * rows_per_block;
-    const int r1 = min(d.hw, r0 + rows_per_block);
+    const int r0 = blockIdx.x * geo.rows_per_block;
+    const int r1 = min(d.hw, r0 + geo.rows_per_block);
     float ks[8], s[8], q[8];
     if (cg >= 8) {          // 8 consecutive channels touch at most two groups: two shift loads
         const int ga = c / cg, gb = (c + 7) / cg;
@@ -83,21 +73,17 @@ __global__ void gn_stats_kernel(const slh_gn_desc d, int nchunk, int rpi, int ro
         }
     }
     float S, Q;
-    const bool owner = gn_block_reduce<8>(gn_lds, C, cg, d.groups, rpi, lpg, chunk, rl, s, q, S, Q);
-    // level 1 only: the cluster's last arriver leaves the cluster's pair at part[row_blocks + cluster] (plain store: the next
-    // kernel on the stream reads it)
-    const int ncl = (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER;
-    float* part = d.partial + (long)b * (row_blocks + ncl) * d.groups * 2;
+    const bool owner = gn_block_reduce(gn_lds, geo, d.groups, chunk, rl, s, q, S, Q);
+    // level 1 only: the cluster's last arriver leaves the cluster's pair in the cluster's row (plain store: the next kernel on the
+    // stream reads it)
+    const GnWorkspace ws = geo.ws();
+    float* rows = ws.rows(d.partial, b, d.groups);
     const int g = tid / lpg;
-    const int rb = blockIdx.x, cl = rb / GN_CLUSTER;
-    if (owner) store_pair_sc1(part + ((long)rb * d.groups + g) * 2, S, Q);
-    const int first = cl * GN_CLUSTER;
-    const int members = min(GN_CLUSTER, row_blocks - first);
-    if (!last_arriver(d.ticket + (long)b * (1 + ncl) + 1 + cl, (unsigned)members, (int*)(gn_lds + 2 * rpi * C))) return;
+    const int rb = blockIdx.x;
     double Sd, Qd;
-    gn_combine_partials(part + (long)first * d.groups * 2, members, d.groups, lpg, Sd, Qd);
+    if (!gn_cluster_reduce(ws, rows, ws.tickets(d.ticket, b), rb, d.groups, lpg, g, owner, S, Q, geo.flag(gn_lds), Sd, Qd)) return;
     if (g < d.groups && (tid & (lpg - 1)) == 0)
-        *(f32x2*)(part + ((long)(row_blocks + cl) * d.groups + g) * 2) = f32x2{(float)Sd, (float)Qd};
+        *(f32x2*)ws.pair(rows, d.groups, ws.cluster_row(ws.cluster_of(rb)), g) = f32x2{(float)Sd, (float)Qd};
 }
 
 // (mean, rstd) of every group of sample b from the `srb` cluster pairs slh_gn_stats left at `part`, in index order (double
@@ -126,24 +112,22 @@ __device__ __forceinline__ void gn_stats_from_partials(const slh_gn_desc& d, int
         q += __shfl_xor(q, o, 64);
     }
     if (g < d.groups && j == 0) {
-        const double n = (double)d.hw * (double)cg;
-        const double k = (double)(float)*gn_src(d, (long)b * d.hw, g * cg);
-        const double m = a / n;
-        const double var = fmax(q / n - m * m, 0.0);
-        st[g] = (float)(k + m);
-        st[64 + g] = (float)(1.0 / sqrt(var + (double)d.eps));
+        const f32x2 mr = gn_finish(a, q, d.hw, cg, (double)(float)*gn_src(d, (long)b * d.hw, g * cg), d.eps);
+        st[g] = mr[0];
+        st[64 + g] = mr[1];
     }
     __syncthreads();
 }
 
-__global__ void gn_apply_kernel(const slh_gn_desc d, int nchunk, int rpi, int rows_per_block, int cg, int lpg, int row_blocks) {
+__global__ void gn_apply_kernel(const slh_gn_desc d, const Geom geo) {
     __shared__ float st[128];
     const int tid = threadIdx.x;
-    const int chunk = tid % nchunk, rl = tid / nchunk;
+    const int rpi = geo.rpi, cg = geo.cg;
+    const int chunk = tid % geo.nchunk, rl = tid / geo.nchunk;
     const int c = chunk * 8;
     const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_block;
-    const int r1 = min(d.hw, r0 + rows_per_block);
+    const int r0 = blockIdx.x * geo.rows_per_block;
+    const int r1 = min(d.hw, r0 + geo.rows_per_block);
     float a[8], sft[8];
     const bf16x8 gm = *(const bf16x8*)((const __bf16*)d.gamma + c);
     const bf16x8 bt = *(const bf16x8*)((const __bf16*)d.beta + c);
@@ -154,8 +138,8 @@ __global__ void gn_apply_kernel(const slh_gn_desc d, int nchunk, int rpi, int ro
         const int r = min(r0 + rl + it * rpi, d.hw - 1);       // unconditional (see gn_stats_kernel)
         v[it] = *(const bf16x8*)gn_src(d, (long)b * d.hw + r, c);
     }
-    const int ncl = (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER;
-    gn_stats_from_partials(d, b, d.partial + ((long)b * (row_blocks + ncl) + row_blocks) * d.groups * 2, ncl, cg, lpg, st);
+    const GnWorkspace ws = geo.ws();
+    gn_stats_from_partials(d, b, ws.pair(ws.rows(d.partial, b, d.groups), d.groups, ws.cluster_row(0), 0), ws.clusters(), cg, geo.lpg, st);
     if (blockIdx.x == 0 && tid < d.groups)                     // for the backward (slh_gn_bwd_*) and anyone else who reads d.stats
         *(f32x2*)(d.stats + ((long)b * d.groups + tid) * 2) = f32x2{st[tid], st[64 + tid]};
 #pragma unroll
@@ -193,18 +177,6 @@ constexpr int GNF_ITEMS = 3;           // 16-byte chunks per thread.  Measured (
                                        // at 16x16 it ties and at 32x32 it LOSES 2.5x (41 us vs 8 + 7): 16-64 workgroups then carry
                                        // all of the SiLU / select arithmetic that the two-launch form spreads over the chip
 constexpr int GNF_MAXG = 4;            // groups per workgroup
-
-struct GnFusedGeom { int gq, nch, items; bool ok; };
-__host__ __device__ inline GnFusedGeom gn_fused_geom(int C, int hw, int groups) {
-    GnFusedGeom g;
-    const int cg = C / groups;
-    g.gq = 1;
-    while (g.gq <= GNF_MAXG && (g.gq * cg) % 8) g.gq *= 2;
-    g.nch = g.gq * cg / 8;
-    g.items = (hw * g.nch + 255) / 256;
-    g.ok = g.gq <= GNF_MAXG && groups % g.gq == 0 && g.items <= GNF_ITEMS && hw * g.nch >= 64;
-    return g;
-}
 
 // r = idx / nch as (idx * magic) >> 32 with magic = ceil(2^32 / nch) (64-bit: it is 2^32 for nch = 1): exact for idx * nch < 2^32;
 // group of channel x inside the workgroup's <= 4 groups by comparison - both replace ~30-instruction integer divisions
@@ -263,11 +235,8 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const slh_gn_desc d, int 
     if (tid < gq) {
         const double S = ((double)red[0][2 * tid] + (double)red[1][2 * tid]) + ((double)red[2][2 * tid] + (double)red[3][2 * tid]);
         const double Q = ((double)red[0][2 * tid + 1] + (double)red[1][2 * tid + 1]) + ((double)red[2][2 * tid + 1] + (double)red[3][2 * tid + 1]);
-        const double n = (double)d.hw * (double)cg;
-        const double m = S / n;
-        const double var = fmax(Q / n - m * m, 0.0);
-        const float mean = (float)((double)(float)*gn_src(d, (long)b * d.hw, c_base + tid * cg) + m);     // this group's shift + mean of the shifted data
-        const float rstd = (float)(1.0 / sqrt(var + (double)d.eps));
+        const f32x2 mr = gn_finish(S, Q, d.hw, cg, (double)(float)*gn_src(d, (long)b * d.hw, c_base + tid * cg), d.eps);   // pivot: this group's shift
+        const float mean = mr[0], rstd = mr[1];
         fin[2 * tid] = mean; fin[2 * tid + 1] = rstd;
         const int g_glob = blockIdx.x * gq + tid;
         d.stats[((long)b * d.groups + g_glob) * 2] = mean;
@@ -319,27 +288,38 @@ constexpr int GN1_U = 8;                      // accesses in flight per thread a
 
 __device__ __forceinline__ float silu_rcp_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   // 1 ulp rcp: no IEEE division sequence
 
-struct GnOneGeom { int V, nch, threads; bool ok; };
-__host__ __device__ inline GnOneGeom gn_one_geom(int c0, int c1, int hw, int groups) {
-    GnOneGeom g;
-    const int C = c0 + c1, cg = C / groups;
-    g.V = (cg % 8 == 0) ? 8 : (cg % 4 == 0 && c0 % 4 == 0) ? 4 : 2;
-    g.nch = cg / g.V;
-    const int total = hw * g.nch;
-    g.threads = total >= 4096 ? 1024 : total >= 1024 ? 512 : 256;
-    g.ok = cg % 2 == 0 && c0 % 2 == 0 && total >= 256;
-    return g;
-}
-// size limits of the one-launch form; SLH_GN1_MAX_HW / SLH_GN1_MAX_ELEMS override them for measurements (scripts/probe_gn.py)
-static bool gn_one_fits(int channels, int hw, int groups) {
-    static const int max_hw = getenv("SLH_GN1_MAX_HW") ? atoi(getenv("SLH_GN1_MAX_HW")) : GN1_MAX_HW;
-    static const long max_elems = getenv("SLH_GN1_MAX_ELEMS") ? atol(getenv("SLH_GN1_MAX_ELEMS")) : (long)GN1_MAX_ELEMS;
-    return hw <= max_hw && (long)hw * (channels / groups) <= max_elems;
-}
-static int gn_one_siblings(int batch, int groups, int total_chunks, int threads) {
-    int S = 1;
-    while (S < 8 && 2 * S * batch * groups <= 320 && total_chunks / (2 * S) >= threads / 4) S *= 2;
-    return S;
+// The form a GroupNorm of C channels (a multiple of 8, gn_check) takes, and the launch parameters of the one-launch forms: the ONE
+// decision behind slh_gn_fused_ok (whose values the forms carry) and slh_gn_fused.
+enum { GN_TWO_LAUNCH = 0, GN_REGISTER = 1, GN_SIBLINGS = 2 };
+struct GnForm {
+    int form, cg;
+    int gq;                         // GN_REGISTER: groups per workgroup
+    int V, threads, S, per;         // GN_SIBLINGS: elements per access, workgroup size, siblings per (sample, group), chunks per sibling
+    int nch;                        // chunks per row of a workgroup's channels ...
+    unsigned long long magic;       // ... and ceil(2^32 / nch) for gnf_div (2^32 itself for nch = 1: 64-bit)
+};
+static GnForm gn_form(int C, int hw, int groups, int batch) {
+    GnForm f = {};
+    f.cg = C / groups;
+    // tiny tensors: the register-resident kernel
+    f.gq = 1;
+    while (f.gq <= GNF_MAXG && (f.gq * f.cg) % 8) f.gq *= 2;
+    f.nch = f.gq * f.cg / 8;
+    if (f.gq <= GNF_MAXG && groups % f.gq == 0 && (hw * f.nch + 255) / 256 <= GNF_ITEMS && hw * f.nch >= 64) f.form = GN_REGISTER;
+    else {
+        // cache-resident slabs: sibling workgroups
+        f.V = f.cg % 8 == 0 ? 8 : f.cg % 4 == 0 ? 4 : 2;
+        f.nch = f.cg / f.V;
+        const int total = hw * f.nch;
+        f.threads = total >= 4096 ? 1024 : total >= 1024 ? 512 : 256;
+        const bool ok = f.cg % 2 == 0 && total >= 256 && hw <= GN1_MAX_HW && (long)hw * f.cg <= GN1_MAX_ELEMS;
+        f.form = ok ? GN_SIBLINGS : GN_TWO_LAUNCH;
+        f.S = 1;
+        while (f.S < 8 && 2 * f.S * batch * groups <= 320 && total / (2 * f.S) >= f.threads / 4) f.S *= 2;
+        f.per = (total + f.S - 1) / f.S;
+    }
+    if (f.form != GN_TWO_LAUNCH) f.magic = (0x100000000ull + f.nch - 1) / f.nch;
+    return f;
 }
 
 template <int V>
@@ -393,11 +373,8 @@ __global__ __launch_bounds__(1024) void gn_one_kernel(const slh_gn_desc d, int c
     if (tid == 0) {
         double S_ = 0.0, Q_ = 0.0;
         for (int w = 0; w < (nt >> 6); ++w) { S_ += (double)red[w][0]; Q_ += (double)red[w][1]; }
-        const double n = (double)d.hw * (double)cg;
-        const double m = S_ / n;
-        const double var = fmax(Q_ / n - m * m, 0.0);
-        const float mean = (float)((double)k + m);
-        const float rstd = (float)(1.0 / sqrt(var + (double)d.eps));
+        const f32x2 mr = gn_finish(S_, Q_, d.hw, cg, (double)k, d.eps);
+        const float mean = mr[0], rstd = mr[1];
         fin[0] = mean; fin[1] = rstd;
         if (sib == 0) *(f32x2*)(d.stats + ((long)b * d.groups + g) * 2) = f32x2{mean, rstd};      // for the backward
     }
@@ -425,10 +402,6 @@ __global__ __launch_bounds__(1024) void gn_one_kernel(const slh_gn_desc d, int c
 }
 
 // ---- backward -------------------------------------------------------------------------------------
-__device__ __forceinline__ const __bf16* gnb_src(const slh_gn_bwd_desc& d, long row, int c) {
-    return c < d.c0 ? (const __bf16*)d.x0 + row * d.ldx0 + c : (const __bf16*)d.x1 + row * d.ldx1 + (c - d.c0);
-}
-
 // dxhat[e] = dy * act'(z) * gamma, xhat[e]; z = xhat*gamma+beta
 __device__ __forceinline__ void gnb_elem(const slh_gn_bwd_desc& d, const bf16x8& xv, const bf16x8& dyv,
                                          const float* mean, const float* rstd, const float* gm, const float* bt,
@@ -447,16 +420,15 @@ __device__ __forceinline__ void gnb_elem(const slh_gn_bwd_desc& d, const bf16x8&
     }
 }
 
-__global__ void gn_bwd_stats_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi, int rows_per_block, int cg, int lpg,
-                                    int row_blocks) {
+__global__ void gn_bwd_stats_kernel(const slh_gn_bwd_desc d, const Geom geo) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
     const int tid = threadIdx.x;
-    const int chunk = tid % nchunk, rl = tid / nchunk;
+    const int rpi = geo.rpi, cg = geo.cg, lpg = geo.lpg;
+    const int chunk = tid % geo.nchunk, rl = tid / geo.nchunk;
     const int c = chunk * 8;
     const int b = blockIdx.y;
-    const int C = nchunk * 8;
-    const int r0 = blockIdx.x * rows_per_block;
-    const int r1 = min(d.hw, r0 + rows_per_block);
+    const int r0 = blockIdx.x * geo.rows_per_block;
+    const int r1 = min(d.hw, r0 + geo.rows_per_block);
     float mean[8], rstd[8], gm[8], bt[8];
     const bf16x8 gmv = *(const bf16x8*)((const __bf16*)d.gamma + c);
     const bf16x8 btv = *(const bf16x8*)((const __bf16*)d.beta + c);
@@ -472,7 +444,7 @@ __global__ void gn_bwd_stats_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi
     for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
     for (int r = r0 + rl; r < r1; r += rpi) {
         const long row = (long)b * d.hw + r;
-        const bf16x8 xv = *(const bf16x8*)gnb_src(d, row, c);
+        const bf16x8 xv = *(const bf16x8*)gn_src(d, row, c);
         const bf16x8 dyv = *(const bf16x8*)((const __bf16*)d.dy + row * d.lddy + c);
         float dxh[8], xh[8];
         gnb_elem(d, xv, dyv, mean, rstd, gm, bt, dxh, xh);
@@ -480,11 +452,11 @@ __global__ void gn_bwd_stats_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi
         for (int e = 0; e < 8; ++e) { s[e] += dxh[e]; q[e] += dxh[e] * xh[e]; }
     }
     float S, Q;
-    const bool owner = gn_block_reduce<8>(gn_lds, C, cg, d.groups, rpi, lpg, chunk, rl, s, q, S, Q);
-    const int ncl = (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER;
+    const bool owner = gn_block_reduce(gn_lds, geo, d.groups, chunk, rl, s, q, S, Q);
     double Sd, Qd;
-    const bool fin = gn_two_level_reduce(d.bpartial + (long)b * (row_blocks + ncl) * d.groups * 2, d.bticket + (long)b * (1 + ncl),
-                                         row_blocks, blockIdx.x, d.groups, lpg, owner, S, Q, (int*)(gn_lds + 2 * rpi * C), Sd, Qd);
+    const GnWorkspace ws = geo.ws();
+    const bool fin = gn_two_level_reduce(ws, ws.rows(d.bpartial, b, d.groups), ws.tickets(d.bticket, b), blockIdx.x, d.groups, lpg, owner, S, Q,
+                                         geo.flag(gn_lds), Sd, Qd);
     const int g = tid / lpg;
     if (fin) {
         d.bstats[((long)b * d.groups + g) * 2] = (float)Sd;
@@ -492,13 +464,14 @@ __global__ void gn_bwd_stats_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi
     }
 }
 
-__global__ void gn_bwd_apply_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi, int rows_per_block, int cg) {
+__global__ void gn_bwd_apply_kernel(const slh_gn_bwd_desc d, const Geom geo) {
     const int tid = threadIdx.x;
-    const int chunk = tid % nchunk, rl = tid / nchunk;
+    const int rpi = geo.rpi, cg = geo.cg;
+    const int chunk = tid % geo.nchunk, rl = tid / geo.nchunk;
     const int c = chunk * 8;
     const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_block;
-    const int r1 = min(d.hw, r0 + rows_per_block);
+    const int r0 = blockIdx.x * geo.rows_per_block;
+    const int r1 = min(d.hw, r0 + geo.rows_per_block);
     const float inv_n = 1.f / ((float)d.hw * (float)cg);
     float mean[8], rstd[8], gm[8], bt[8], m1[8], m2[8];
     const bf16x8 gmv = *(const bf16x8*)((const __bf16*)d.gamma + c);
@@ -521,7 +494,7 @@ __global__ void gn_bwd_apply_kernel(const slh_gn_bwd_desc d, int nchunk, int rpi
     if (!dxb) return;
     for (int r = r0 + rl; r < r1; r += rpi) {
         const long row = (long)b * d.hw + r;
-        const bf16x8 xv = *(const bf16x8*)gnb_src(d, row, c);
+        const bf16x8 xv = *(const bf16x8*)gn_src(d, row, c);
         const bf16x8 dyv = *(const bf16x8*)((const __bf16*)d.dy + row * d.lddy + c);
         float dxh[8], xh[8];
         gnb_elem(d, xv, dyv, mean, rstd, gm, bt, dxh, xh);
@@ -635,103 +608,90 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const slh_ln_bwd_des
 
 }  // namespace
 
-static int gn_check(const char* who, int c0, int c1, int groups, int ldx0, int ldx1, const void* x1) {
-    const int C = c0 + c1;
-    SLH_CHECK(C > 0 && C % 8 == 0 && c0 % 8 == 0 && c1 % 8 == 0, "%s: channels must be multiples of 8", who);
-    SLH_CHECK(groups > 0 && groups <= 64 && C % groups == 0, "%s: bad group count", who);
-    SLH_CHECK(ldx0 % 8 == 0 && ldx1 % 8 == 0, "%s: leading dims must be multiples of 8", who);
-    SLH_CHECK((x1 != nullptr) == (c1 > 0), "%s: x1/c1 mismatch", who);
+// What the five GroupNorm entry points require alike, of either descriptor: the input pointers and the shape.  `ptrs`: the
+// entry point's own mandatory pointers, d itself first, are there.
+template <class Desc>
+static int gn_check(const char* who, const Desc* d, bool ptrs) {
+    SLH_CHECK(ptrs && d->x0 && d->stats, "%s: null pointer", who);
+    const int C = d->c0 + d->c1;
+    SLH_CHECK(C > 0 && C % 8 == 0 && d->c0 % 8 == 0 && d->c1 % 8 == 0, "%s: channels must be multiples of 8", who);
+    SLH_CHECK(d->groups > 0 && d->groups <= 64 && C % d->groups == 0, "%s: bad group count", who);
+    SLH_CHECK(d->ldx0 % 8 == 0 && d->ldx1 % 8 == 0, "%s: leading dims must be multiples of 8", who);
+    SLH_CHECK((d->x1 != nullptr) == (d->c1 > 0), "%s: x1/c1 mismatch", who);
     SLH_CHECK(C / 8 <= 1024, "%s: too many channels", who);
     return 0;
 }
+// ... and the two that write y (slh_gn_apply, slh_gn_fused); `why`: what re-reads x while y is written (null: nothing does)
+static int gn_check_y(const char* who, const slh_gn_desc* d, const char* why) {
+    SLH_CHECK(d->ldy % 8 == 0, "%s: ldy", who);
+    SLH_CHECK(wt_span_ok((long)d->batch * d->hw, d->ldy, d->c0 + d->c1), "%s: y reaches past 2 GiB from its base (32-bit store offsets)", who);
+    SLH_CHECK(!why || (d->y != d->x0 && (!d->x1 || d->y != d->x1)), "%s: y must not alias x0 / x1 (%s)", who, why);
+    return 0;
+}
+static bool gn_shape_ok(int channels, int hw, int groups) { return channels > 0 && channels % 8 == 0 && hw > 0 && groups > 0 && channels % groups == 0; }
 
 extern "C" int slh_gn_row_blocks(int channels, int hw, int groups) {
-    if (channels <= 0 || channels % 8 || hw <= 0 || groups <= 0 || channels % groups) return -1;
-    return gn_geom(channels, 0, hw, groups).row_blocks;
+    return gn_shape_ok(channels, hw, groups) ? gn_geom(channels, hw, groups).row_blocks : -1;
 }
 
-extern "C" int slh_gn_clusters(int row_blocks) { return row_blocks > 0 ? (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER : -1; }
+extern "C" int slh_gn_clusters(int row_blocks) { return row_blocks > 0 ? GnWorkspace{row_blocks}.clusters() : -1; }
 
 extern "C" int slh_gn_stats(const slh_gn_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x0 && d->stats, "slh_gn_stats: null pointer");
+    if (gn_check("slh_gn_stats", d, d != nullptr)) return -1;
     SLH_CHECK(d->partial && d->ticket, "slh_gn_stats: needs the partial-sum workspace and the zeroed ticket counters");
-    if (gn_check("slh_gn_stats", d->c0, d->c1, d->groups, d->ldx0, d->ldx1, d->x1)) return -1;
-    const GnGeom g = gn_geom(d->c0, d->c1, d->hw, d->groups);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads), g.lds_bytes, (hipStream_t)stream, *d,
-                       g.nchunk, g.rpi, g.rows_per_block, g.cg, g.lpg, g.row_blocks);
+    const Geom g = gn_geom(d->c0 + d->c1, d->hw, d->groups);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads()), g.lds_bytes(), (hipStream_t)stream, *d,
+                       g.nchunk, g.rpi, g.rows_per_block, g.cg, g.lpg, g.row_blocks);       // field by field: see the kernel
     SLH_LAUNCH_CHECK("slh_gn_stats");
     return 0;
 }
 
 extern "C" int slh_gn_fused_ok(int channels, int hw, int groups) {
-    if (channels <= 0 || channels % 8 || hw <= 0 || groups <= 0 || channels % groups) return 0;
-    if (gn_fused_geom(channels, hw, groups).ok) return 1;                 // tiny tensors: the register-resident kernel
-    return gn_one_geom(channels, 0, hw, groups).ok && gn_one_fits(channels, hw, groups) ? 2 : 0;     // cache-resident slabs: sibling workgroups
+    return gn_shape_ok(channels, hw, groups) ? gn_form(channels, hw, groups, 1).form : 0;       // the form does not depend on the batch
 }
 
 extern "C" int slh_gn_fused(const slh_gn_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x0 && d->stats && d->y && d->gamma && d->beta, "slh_gn_fused: null pointer");
-    if (gn_check("slh_gn_fused", d->c0, d->c1, d->groups, d->ldx0, d->ldx1, d->x1)) return -1;
-    SLH_CHECK(d->ldy % 8 == 0, "slh_gn_fused: ldy");
-    SLH_CHECK(wt_span_ok((long)d->batch * d->hw, d->ldy, d->c0 + d->c1), "slh_gn_fused: y reaches past 2 GiB from its base (32-bit store offsets)");
-    const GnFusedGeom g = gn_fused_geom(d->c0 + d->c1, d->hw, d->groups);
-    if (!g.ok) {
-        const GnOneGeom o = gn_one_geom(d->c0, d->c1, d->hw, d->groups);
-        SLH_CHECK(o.ok && gn_one_fits(d->c0 + d->c1, d->hw, d->groups), "slh_gn_fused: shape C=%d hw=%d is not a one-launch case (slh_gn_fused_ok)",
-                  d->c0 + d->c1, d->hw);
-        SLH_CHECK(d->y != d->x0 && (!d->x1 || d->y != d->x1), "slh_gn_fused: y must not alias x0 / x1 (sibling workgroups re-read the slab)");
-        const int cg = (d->c0 + d->c1) / d->groups, total = d->hw * o.nch;
-        const int S = gn_one_siblings(d->batch, d->groups, total, o.threads);
-        const int per = (total + S - 1) / S;
-        const unsigned long long magic = (0x100000000ull + o.nch - 1) / o.nch;
-        const dim3 grid(d->groups * S * d->batch), block(o.threads);
-        if (o.V == 8) hipLaunchKernelGGL(gn_one_kernel<8>, grid, block, 0, (hipStream_t)stream, *d, cg, o.nch, magic, S, per);
-        else if (o.V == 4) hipLaunchKernelGGL(gn_one_kernel<4>, grid, block, 0, (hipStream_t)stream, *d, cg, o.nch, magic, S, per);
-        else hipLaunchKernelGGL(gn_one_kernel<2>, grid, block, 0, (hipStream_t)stream, *d, cg, o.nch, magic, S, per);
-        SLH_LAUNCH_CHECK("slh_gn_fused");
-        return 0;
-    }
-    hipLaunchKernelGGL(gn_fused_kernel, dim3(d->groups / g.gq, d->batch), dim3(256), 0, (hipStream_t)stream, *d,
-                       (d->c0 + d->c1) / d->groups, g.gq, g.nch, (0x100000000ull + g.nch - 1) / g.nch);       // 2^32 itself for nch = 1: 64-bit
+    if (gn_check("slh_gn_fused", d, d && d->y && d->gamma && d->beta)) return -1;
+    const GnForm f = gn_form(d->c0 + d->c1, d->hw, d->groups, d->batch);
+    SLH_CHECK(f.form != GN_TWO_LAUNCH, "slh_gn_fused: shape C=%d hw=%d is not a one-launch case (slh_gn_fused_ok)", d->c0 + d->c1, d->hw);
+    if (gn_check_y("slh_gn_fused", d, f.form == GN_SIBLINGS ? "sibling workgroups re-read the slab" : nullptr)) return -1;
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(d->groups * f.S * d->batch), block(f.threads);
+    if (f.form == GN_REGISTER) hipLaunchKernelGGL(gn_fused_kernel, dim3(d->groups / f.gq, d->batch), dim3(256), 0, s, *d, f.cg, f.gq, f.nch, f.magic);
+    else if (f.V == 8) hipLaunchKernelGGL(gn_one_kernel<8>, grid, block, 0, s, *d, f.cg, f.nch, f.magic, f.S, f.per);
+    else if (f.V == 4) hipLaunchKernelGGL(gn_one_kernel<4>, grid, block, 0, s, *d, f.cg, f.nch, f.magic, f.S, f.per);
+    else hipLaunchKernelGGL(gn_one_kernel<2>, grid, block, 0, s, *d, f.cg, f.nch, f.magic, f.S, f.per);
     SLH_LAUNCH_CHECK("slh_gn_fused");
     return 0;
 }
 
 extern "C" int slh_gn_apply(const slh_gn_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x0 && d->stats && d->y && d->gamma && d->beta, "slh_gn_apply: null pointer");
+    if (gn_check("slh_gn_apply", d, d && d->y && d->gamma && d->beta)) return -1;
     SLH_CHECK(d->partial, "slh_gn_apply: needs the partial sums slh_gn_stats left (same descriptor)");
     // every workgroup rebuilds (mean, rstd) from the partial sums AND the pivot x[b][row 0][first channel of the group], which it
     // re-reads from the input: an in-place call would let workgroups that run later see a normalised pivot - different means per
     // workgroup, silently
-    SLH_CHECK(d->y != d->x0 && (!d->x1 || d->y != d->x1), "slh_gn_apply: y must not alias x0 / x1 (the statistics' pivot is re-read from x)");
-    if (gn_check("slh_gn_apply", d->c0, d->c1, d->groups, d->ldx0, d->ldx1, d->x1)) return -1;
-    SLH_CHECK(d->ldy % 8 == 0, "slh_gn_apply: ldy");
-    SLH_CHECK(wt_span_ok((long)d->batch * d->hw, d->ldy, d->c0 + d->c1), "slh_gn_apply: y reaches past 2 GiB from its base (32-bit store offsets)");
-    const GnGeom g = gn_geom(d->c0, d->c1, d->hw, d->groups);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads), 0, (hipStream_t)stream, *d,
-                       g.nchunk, g.rpi, g.rows_per_block, g.cg, g.lpg, g.row_blocks);
+    if (gn_check_y("slh_gn_apply", d, "the statistics' pivot is re-read from x")) return -1;
+    const Geom g = gn_geom(d->c0 + d->c1, d->hw, d->groups);
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads()), 0, (hipStream_t)stream, *d, g);
     SLH_LAUNCH_CHECK("slh_gn_apply");
     return 0;
 }
 
 extern "C" int slh_gn_bwd_stats(const slh_gn_bwd_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x0 && d->stats && d->bstats && d->dy, "slh_gn_bwd_stats: null pointer");
+    if (gn_check("slh_gn_bwd_stats", d, d && d->bstats && d->dy)) return -1;
     SLH_CHECK(d->bpartial && d->bticket, "slh_gn_bwd_stats: needs the partial-sum workspace and the zeroed ticket counters");
-    if (gn_check("slh_gn_bwd_stats", d->c0, d->c1, d->groups, d->ldx0, d->ldx1, d->x1)) return -1;
-    const GnGeom g = gn_geom(d->c0, d->c1, d->hw, d->groups);
-    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads), g.lds_bytes, (hipStream_t)stream,
-                       *d, g.nchunk, g.rpi, g.rows_per_block, g.cg, g.lpg, g.row_blocks);
+    const Geom g = gn_geom(d->c0 + d->c1, d->hw, d->groups);
+    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads()), g.lds_bytes(), (hipStream_t)stream, *d, g);
     SLH_LAUNCH_CHECK("slh_gn_bwd_stats");
     return 0;
 }
 
 extern "C" int slh_gn_bwd_apply(const slh_gn_bwd_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x0 && d->stats && d->bstats && d->dy, "slh_gn_bwd_apply: null pointer");
-    if (gn_check("slh_gn_bwd_apply", d->c0, d->c1, d->groups, d->ldx0, d->ldx1, d->x1)) return -1;
+    if (gn_check("slh_gn_bwd_apply", d, d && d->bstats && d->dy)) return -1;
     SLH_CHECK(d->lddx0 % 8 == 0 && d->lddx1 % 8 == 0 && d->lddy % 8 == 0, "slh_gn_bwd_apply: leading dims");
-    const GnGeom g = gn_geom(d->c0, d->c1, d->hw, d->groups);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads), 0, (hipStream_t)stream,
-                       *d, g.nchunk, g.rpi, g.rows_per_block, g.cg);
+    const Geom g = gn_geom(d->c0 + d->c1, d->hw, d->groups);
+    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads()), 0, (hipStream_t)stream, *d, g);
     SLH_LAUNCH_CHECK("slh_gn_bwd_apply");
     return 0;
 }

@@ -362,14 +362,14 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
 // thread, reduces per group in LDS in a fixed order and publishes one pair per (block, group); the last block to arrive
 // combines them in index order and writes (mean, rstd) - bit-reproducible, see common.h.  apply: y = xhat*gamma+beta (+SiLU).
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gn32_stats_kernel(const slh_gn32_desc d, int rows_per_block, int lpg, int row_blocks) {
+__global__ __launch_bounds__(256) void gn32_stats_kernel(const slh_gn32_desc d, const GnGeom<4> geo) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
     const int tid = threadIdx.x;
-    const int nchunk = d.C / 4, cg = d.C / d.groups;      // nchunk is a power of two <= 256 (checked on the host)
+    const int nchunk = geo.nchunk, cg = geo.cg, rpi = geo.rpi, lpg = geo.lpg;     // nchunk is a power of two <= 256 (checked on the host)
     const int b = blockIdx.y;
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(d.hw, r0 + rows_per_block);
+    const int r0 = blockIdx.x * geo.rows_per_block, r1 = min(d.hw, r0 + geo.rows_per_block);
     const float* X = (const float*)d.x;
-    const int chunk = tid % nchunk, rl = tid / nchunk, rpi = 256 / nchunk;
+    const int chunk = tid % nchunk, rl = tid / nchunk;
     const int c = chunk * 4;
     const int g0 = c / cg;                     // cg is a multiple of 4: a float4 never straddles groups
     const float k = X[(long)b * d.hw * d.ldx + g0 * cg];   // shift: the group's first element (see gn_stats_kernel, norm.hip)
@@ -380,19 +380,16 @@ __global__ __launch_bounds__(256) void gn32_stats_kernel(const slh_gn32_desc d, 
         for (int e = 0; e < 4; ++e) { const float f = v[e] - k; s[e] += f; q[e] += f * f; }
     }
     float S, Q;
-    const bool owner = gn_block_reduce<4>(gn_lds, d.C, cg, d.groups, rpi, lpg, chunk, rl, s, q, S, Q);
-    const int ncl = (row_blocks + GN_CLUSTER - 1) / GN_CLUSTER;
+    const bool owner = gn_block_reduce(gn_lds, geo, d.groups, chunk, rl, s, q, S, Q);
     double Sd, Qd;
-    const bool fin = gn_two_level_reduce(d.partial + (long)b * (row_blocks + ncl) * d.groups * 2, d.ticket + (long)b * (1 + ncl),
-                                         row_blocks, blockIdx.x, d.groups, lpg, owner, S, Q, (int*)(gn_lds + 2 * rpi * d.C), Sd, Qd);
+    const GnWorkspace ws = geo.ws();
+    const bool fin = gn_two_level_reduce(ws, ws.rows(d.partial, b, d.groups), ws.tickets(d.ticket, b), blockIdx.x, d.groups, lpg, owner, S, Q,
+                                         geo.flag(gn_lds), Sd, Qd);
     const int g = tid / lpg;
     if (fin) {
-        const double n = (double)d.hw * (double)cg;
-        const double kg = (double)X[(long)b * d.hw * d.ldx + g * cg];
-        const double m = Sd / n;
-        const double var = fmax(Qd / n - m * m, 0.0);
-        d.stats[((long)b * d.groups + g) * 2] = (float)(kg + m);
-        d.stats[((long)b * d.groups + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)d.eps));
+        const f32x2 mr = gn_finish(Sd, Qd, d.hw, cg, (double)X[(long)b * d.hw * d.ldx + g * cg], d.eps);
+        d.stats[((long)b * d.groups + g) * 2] = mr[0];
+        d.stats[((long)b * d.groups + g) * 2 + 1] = mr[1];
     }
 }
 
@@ -607,12 +604,8 @@ extern "C" int slh_gn32_row_blocks(int hw) { return hw > 0 ? (hw + GN32_ROWS_PER
 extern "C" int slh_gn32_stats(const slh_gn32_desc* d, slh_stream_t stream) {
     if (gn32_check(d, "slh_gn32_stats")) return -1;
     SLH_CHECK(d->partial && d->ticket, "slh_gn32_stats: needs the partial-sum workspace and the zeroed ticket counters");
-    const int row_blocks = slh_gn32_row_blocks(d->hw);
-    int lpg = 1;
-    while (lpg < 16 && 2 * lpg * d->groups <= 256) lpg *= 2;
-    const unsigned lds = (unsigned)((2 * 256 * 4 + 4) * sizeof(float));
-    hipLaunchKernelGGL(gn32_stats_kernel, dim3(row_blocks, d->batch), dim3(256), lds, (hipStream_t)stream, *d,
-                       GN32_ROWS_PER_BLOCK, lpg, row_blocks);
+    const GnGeom<4> g = gn_geom<4>(d->C, d->hw, d->groups, GN32_ROWS_PER_BLOCK);      // 256 threads: gn32_check
+    hipLaunchKernelGGL(gn32_stats_kernel, dim3(g.row_blocks, d->batch), dim3(g.threads()), g.lds_bytes(), (hipStream_t)stream, *d, g);
     SLH_LAUNCH_CHECK("slh_gn32_stats");
     return 0;
 }

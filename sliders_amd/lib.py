@@ -239,15 +239,20 @@ def check(rc: int, what: str = ""):
         raise SlidersHipError(f"{what} failed (rc={rc}): {last_error()}")
 
 
-def gn_workspace(channels: int, hw: int, groups: int):
-    """(rows of the [rows][groups][2] fp32 partial-sum scratch, zeroed uint32 tickets) PER SAMPLE of slh_gn_stats /
-    slh_gn_bwd_stats (include/sliders_hip.h, slh_gn_desc)."""
+def _gn_workspace(row_blocks_fn: str, *shape):
+    """(rows of the [rows][groups][2] fp32 partial-sum scratch, zeroed uint32 tickets) PER SAMPLE of a statistics launch with
+    R = row_blocks_fn(*shape) row blocks (include/sliders_hip.h, slh_gn_desc)."""
     l = load()
-    r = l.slh_gn_row_blocks(channels, hw, groups)
+    r = getattr(l, row_blocks_fn)(*shape)
     if r <= 0:
-        raise SlidersHipError(f"slh_gn_row_blocks({channels}, {hw}, {groups}): unsupported shape")
+        raise SlidersHipError(f"{row_blocks_fn}{shape}: unsupported shape")
     c = l.slh_gn_clusters(r)
     return r + c, 1 + c
+
+
+def gn_workspace(channels: int, hw: int, groups: int):
+    """_gn_workspace of slh_gn_stats / slh_gn_bwd_stats"""
+    return _gn_workspace("slh_gn_row_blocks", channels, hw, groups)
 
 
 TILE_64x160 = 0x5425      # the 64 x 160 tile of csrc/gemm5.hip (bits 12-15 = 5: family; 4 ring slots; 2 x 5 blocks of 16 x 16 per wave)
@@ -286,10 +291,8 @@ def gn_fused_ok(channels: int, hw: int, groups: int) -> int:
 
 
 def gn32_workspace(hw: int):
-    l = load()
-    r = l.slh_gn32_row_blocks(hw)
-    c = l.slh_gn_clusters(r)
-    return r + c, 1 + c
+    """_gn_workspace of slh_gn32_stats"""
+    return _gn_workspace("slh_gn32_row_blocks", hw)
 
 
 _BATCH_KINDS = {OP_WGRAD_BATCH: ("slh_lora_wgrad_blocks", WgradDesc), OP_TRANSPOSE_BATCH: ("slh_transpose_heads_blocks", TransposeDesc)}

@@ -950,6 +950,7 @@ def test_groupnorm(dev, C0, C1, act, mean, std, HW):
     lib.call(lib.OP_GN_BWD_STATS, bd, stream())
     lib.call(lib.OP_GN_BWD_APPLY, bd, stream())
     torch.cuda.synchronize()
+    assert int(bticket.abs().sum()) == 0, "the last arrivers of both ticket levels re-arm the tickets"
     xi = ximg.double().clone().requires_grad_(True)
     o = F.group_norm(xi, 32, g.double(), bta.double(), 1e-5)
     if act:
@@ -964,6 +965,7 @@ def test_groupnorm(dev, C0, C1, act, mean, std, HW):
     lib.call(lib.OP_GN_BWD_APPLY, bd, stream())
     torch.cuda.synchronize()
     assert torch.equal(bst, b0) and torch.equal(torch.cat([dx0, dx1[:, :C1]], 1) if C1 else dx0, g0)
+    assert int(bticket.abs().sum()) == 0
 
 
 @pytest.mark.parametrize("C", [64, 320, 640, 1280])

@@ -78,9 +78,11 @@ def test_sgemm_dense_alpha_rowbias(dev):
 
 def test_gn32_and_softmax32(dev):
     torch.manual_seed(4)
-    B, HW, C = 2, 300, 128
+    B, C = 2, 128
     gm, bt = torch.randn(C, device=dev), torch.randn(C, device=dev)
-    for act, off in ((0, 0.5), (1, 0.5), (1, 300.0)):       # 300: DC offset >> spread, the one-pass variance hazard
+    # HW = 300: 5 row blocks of 64 rows, one cluster; 1093: 18 row blocks, 2 clusters (the second of 2 blocks, the last of 5 rows) -
+    # both ticket levels of the shared reduction.  offset 300: DC offset >> spread, the one-pass variance hazard
+    for HW, act, off in [(HW, act, off) for HW in (300, 1093) for act, off in ((0, 0.5), (1, 0.5), (1, 300.0))]:
         x = torch.randn(B * HW, C, device=dev) * 2 + off
         stats = torch.full((B, 32, 2), float("nan"), device=dev)
         prow, ntick = lib.gn32_workspace(HW)
@@ -95,7 +97,7 @@ def test_gn32_and_softmax32(dev):
         ref = F.group_norm(x.double().view(B, HW, C).transpose(1, 2), 32, gm.double(), bt.double(), eps=1e-6)
         if act:
             ref = F.silu(ref)
-        report(f"gn32 act={act} offset={off}", y, ref.float().transpose(1, 2).reshape(B * HW, C), 2e-5 if off < 1 else 6e-5)
+        report(f"gn32 hw={HW} act={act} offset={off}", y, ref.float().transpose(1, 2).reshape(B * HW, C), 2e-5 if off < 1 else 6e-5)
         y0 = y.clone()
         lib.call(lib.OP_GN32_STATS, d, stream())
         lib.call(lib.OP_GN32_APPLY, d, stream())
