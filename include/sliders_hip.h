@@ -463,6 +463,32 @@ typedef struct slh_ddpm_edit_desc {
 } slh_ddpm_edit_desc;
 int slh_ddpm_edit_step(const slh_ddpm_edit_desc* d, slh_stream_t stream);
 
+/* The step between two UNet passes of the samplers euler, euler_a, lms, ddpm and dpmpp_2m on an fp32 master latent: CFG combine,
+ * predicted clean sample, multistep update, and the next pass's scaled bf16 input, in one launch (csrc/sigma_step.hip,
+ * docs/SAMPLING.md).  Never recorded in a program: it has no opcode and no descriptor struct; it takes three host arrays.  Per
+ * element, with u, t the bf16 unconditional and text model outputs and x the master latent, fp32 throughout, one rounding per
+ * operation, nothing contracted:
+ *   m   = u + g (t - u)                          single branch: m = u, g is not read
+ *   x0  = p x + q m
+ *   H0  = kind == 0 ? (x - x0) / sigma : x0      0: the derivative (euler, euler_a, lms); 1: the denoised sample (ddpm, dpmpp_2m)
+ *   acc = a x;  acc += c[0] H0;  acc += c[k] H[k] for k = 1 .. n_hist ascending;  acc += c_n noise (if noise)
+ *   out = acc;  hist_out = H0;  in_bf16 = in2_bf16 = round-to-nearest-even(out * s_next)
+ * The rows (p, q, sigma, a, c, c_n, s_next) of every scheduler: sliders_amd/schedulers.py, step_row.
+ * ptrs[11]: 0 eps       bf16 [2*nb][chw], unconditional half first ([nb][chw] for the single branch)
+ *           1 eps_text  optional, as slh_cfg_ddim_desc (not with the single branch)
+ *           2 x         fp32 [nb][chw]
+ *           3..5 H[1..3] fp32 [nb][chw], the first n_hist are read (H[1] the newest); the others may be NULL
+ *           6 noise     fp32 [nb][chw] or NULL
+ *           7 out       fp32 [nb][chw]; may alias x
+ *           8 hist_out  optional fp32 [nb][chw]; may alias the oldest history slot that is read, or any slot that is not
+ *           9, 10 in_bf16, in2_bf16   optional bf16 [nb][chw]: the two halves of the CFG pair's sample input
+ * dims[5]:  0 nb, 1 chw (any value >= 1), 2 n_hist (0..3), 3 kind (0, 1), 4 single (1: the single branch)
+ * coef[11]: 0 p, 1 q, 2 sigma (kind 0 only), 3 a, 4..7 c[0..3], 8 c_n, 9 s_next, 10 g
+ * Refused before the launch (slh_last_error): a null eps / x / out or a null H[k], k <= n_hist; an fp32 pointer that is not 4-byte
+ * or a bf16 pointer that is not 2-byte aligned; nb < 1, chw < 1; n_hist, kind or single out of range; sigma == 0 with kind 0.
+ * Apart from the two aliases named above, no output may overlap an input. */
+int slh_sigma_step(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+
 /* The edit step of a localised edit: e = mu + resid exactly as slh_ddpm_edit_step mode 1 forms it (one piece of code), then, with
  * k = keep[i] and m = mask[b*hw + i % hw] (one mask value per latent pixel, shared by the channels),
  *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          fp32, one rounding per operation, no contraction.

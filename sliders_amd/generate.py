@@ -56,12 +56,16 @@ def build_parser(defaults: bool = True) -> argparse.ArgumentParser:
     add("--start_noise", type=int, default=750)
     add("--ddim_steps", type=int, default=50, help="sampling steps (default 50; 4 with --turbo)")
     add("--guidance_scale", type=float, default=7.5)
-    add("--scheduler", default="ddim", choices=["ddim", "lms", "euler", "euler_a", "ddpm"],
+    add("--scheduler", default="ddim", choices=["ddim", "lms", "euler", "euler_a", "ddpm", "dpmpp_2m"],
                    help="ddim (default): fused HIP step; lms: what eval-scripts/generate_images_sd1.py:51 constructs; euler: the SDXL "
-                        "checkpoints' scheduler_config (generate_images_xl.py); euler_a: what --turbo samples with")
+                        "checkpoints' scheduler_config (generate_images_xl.py); euler_a: what --turbo samples with; dpmpp_2m: "
+                        "DPM-Solver++ 2M on fp32 latents (docs/SAMPLING.md)")
     add("--timestep_spacing", default=None, choices=["leading", "linspace", "trailing"],
-                   help="timestep grid of euler / euler_a (default: each scheduler's own); trailing (euler_a) starts at t = 999: the "
-                        "few-step grid")
+                   help="timestep grid of euler / euler_a / dpmpp_2m (default: each scheduler's own); trailing (euler_a, dpmpp_2m) "
+                        "starts at t = 999: the few-step grid")
+    add("--fp32_latents", action="store_true",
+                   help="lms / euler / euler_a / ddpm: keep an fp32 master latent and step it with one fused launch per pass instead of "
+                        "the tensor-op scheduler on a bf16 latent (dpmpp_2m always does)")
     add("--no_cfg", dest="no_cfg", action="store_true",
                    help="no classifier-free guidance: only the text prompt is encoded, one UNet row per image.  Implied by "
                         "--guidance_scale <= 1 together with --timestep_spacing")
@@ -173,7 +177,7 @@ def main(argv=None):
         store = LoraStore(eng.cfg, rank=rank, alpha=alpha, train_method=method, device=dev, init="none")
         store.load_state_dict(swept, strict=True)
     smp = SliderSampler(eng, store, dec, scheduler=a.scheduler, scheduler_seed=a.seed, sliders=sliders,
-                        timestep_spacing=a.timestep_spacing)
+                        timestep_spacing=a.timestep_spacing, latents="fp32" if a.fp32_latents else None)
     os.makedirs(a.out, exist_ok=True)
     from PIL import Image
     scales = [float(v) for v in a.scales.split(",")]

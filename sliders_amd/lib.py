@@ -182,6 +182,7 @@ _HOST_FNS = {
     "slh_lora_wgrad_blocks": (c_i32, [_P(WgradDesc)]), "slh_lora_wgrad_single_blocks": (c_i32, [_P(WgradDesc)]),
     "slh_lora_wgrad_geometry": (c_i32, [_P(WgradDesc), c_i32, _P(c_i32)]),
     "slh_transpose_heads_blocks": (c_i32, [_P(TransposeDesc)]), "slh_lora_merge_blocks": (c_i32, [_P(LoraMergeItem)]),
+    "slh_sigma_step": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
 }
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
@@ -435,6 +436,21 @@ def call(opcode: int, desc, stream: int):
     name, _ = _ENTRY[opcode]
     check_batch(opcode, desc)
     check(getattr(lib, name)(C.byref(desc), c_vp(stream)), name)
+
+
+def sigma_step(stream: int, *, eps: int, x: int, out: int, nb: int, chw: int, kind: int, p: float, q: float, sigma: float = 0.0,
+               a: float = 1.0, c=(0.0,), c_n: float = 0.0, s_next: float = 1.0, guidance: float = 0.0, single: bool = False,
+               eps_text: int = 0, hist=(), noise: int = 0, hist_out: int = 0, in_bf16: int = 0, in2_bf16: int = 0):
+    """slh_sigma_step (include/sliders_hip.h): one launch of the fp32 sampler step.  Pointers are device addresses (0: absent); hist:
+    the addresses of H[1..n_hist], newest first; c: c[0..n_hist] (the coefficients beyond are passed as 0); the other scalars are
+    rounded to fp32 here, as the kernel reads them."""
+    hist, c = tuple(hist), tuple(c)
+    if len(hist) > 3 or len(c) > 4:
+        raise SlidersHipError(f"slh_sigma_step: {len(hist)} history buffers, {len(c)} coefficients: at most 3 and 4")
+    ptrs = (c_vp * 11)(eps, eps_text, x, *(hist + (0,) * (3 - len(hist))), noise, out, hist_out, in_bf16, in2_bf16)
+    dims = (c_i32 * 5)(nb, chw, len(hist), kind, int(bool(single)))
+    coef = (c_f32 * 11)(p, q, sigma, a, *(c + (0.0,) * (4 - len(c))), c_n, s_next, guidance)
+    check(load().slh_sigma_step(ptrs, dims, coef, c_vp(stream)), "slh_sigma_step")
 
 
 _GRAPHS_ON = os.environ.get("SLIDERS_HIPGRAPH", "1") != "0"

@@ -36,20 +36,34 @@ from .vae import VaeDecoder
 class SliderSampler:
     def __init__(self, engine: UNetEngine, store: Optional[LoraStore] = None, decoder: Optional[VaeDecoder] = None,
                  prediction_type: str = "epsilon", scheduler: str = "ddim", scheduler_seed: int = 0,
-                 sliders: Optional[SliderSet] = None, timestep_spacing: Optional[str] = None):
+                 sliders: Optional[SliderSet] = None, timestep_spacing: Optional[str] = None, latents: Optional[str] = None):
         """sliders: several sliders of any rank, folded into the frozen weights (sliders_amd/merge.py) instead of the fused rank-4
         adapter path of `store`: the loop samples on the base weights while t > start_noise, merges once when it crosses
         start_noise, runs the adapter-free program on the merged weights and restores the original bits when the image is done.
         scheduler: "ddim" (fused HIP step), "lms" (what eval-scripts/generate_images_sd1.py:51 and the SD-1 notebook
         construct), "euler" (the SDXL checkpoints' scheduler_config: what generate_images_xl.py's pipeline runs), "euler_a",
-        "ddpm" - the non-DDIM ones from sliders_amd/schedulers.py.
-        timestep_spacing (euler and euler_a only; None: each scheduler's default): "leading" / "linspace", and for euler_a "trailing",
-        the few-step grid of the distilled checkpoints (demo_SDXL_Turbo.ipynb: 1-4 steps of euler_a, no CFG; docs/SAMPLING.md)."""
+        "ddpm" - the non-DDIM ones from sliders_amd/schedulers.py - and "dpmpp_2m" (DPM-Solver++ 2M; not one of the reference's).
+        timestep_spacing (euler, euler_a and dpmpp_2m only; None: each scheduler's default): "leading" / "linspace", and for euler_a
+        and dpmpp_2m "trailing", the few-step grid of the distilled checkpoints (demo_SDXL_Turbo.ipynb: 1-4 steps of euler_a, no CFG;
+        docs/SAMPLING.md).
+        latents: "bf16" (the default): the latent between two passes is a bf16 tensor and the tensor-op scheduler steps it; "fp32"
+        (euler, euler_a, lms, ddpm): an fp32 master latent stepped by one slh_sigma_step launch per pass (_sample_fp32).
+        scheduler "dpmpp_2m" (DPM-Solver++ 2M) exists in the fp32 form only, so fp32 is its default."""
         self.eng, self.store, self.decoder = engine, store, decoder
         key = scheduler.lower().replace(" ", "_")
         spacing = {} if timestep_spacing is None else {"timestep_spacing": timestep_spacing}
-        if spacing and key not in ("euler", "euler_a"):
-            raise ValueError(f"SliderSampler: timestep_spacing applies to the schedulers euler and euler_a, not {scheduler!r}")
+        if spacing and key not in ("euler", "euler_a", "dpmpp_2m"):
+            raise ValueError(f"SliderSampler: timestep_spacing applies to the schedulers euler, euler_a and dpmpp_2m, not {scheduler!r}")
+        if latents is None:
+            latents = "fp32" if key == "dpmpp_2m" else "bf16"
+        if latents not in ("bf16", "fp32"):
+            raise ValueError(f"SliderSampler: latents {latents!r}: bf16 and fp32 are implemented")
+        if latents == "fp32" and key == "ddim":
+            raise ValueError("SliderSampler: latents='fp32' does not apply to ddim: the fused DDIM step (slh_cfg_ddim) has its own rounding "
+                             "contract, the reference's bf16 tensor ops")
+        if latents == "bf16" and key == "dpmpp_2m":
+            raise ValueError("SliderSampler: dpmpp_2m exists only with latents='fp32' (the fused fp32 step)")
+        self.latents = latents
         if sliders is not None and store is not None:
             raise ValueError("SliderSampler: give either store= (one rank-4 slider, fused adapters) or sliders= (merged weights)")
         self.merger = WeightMerger(engine.weights, sliders) if sliders is not None else None
@@ -59,6 +73,9 @@ class SliderSampler:
             self.sched = DDIMSchedule(prediction_type=prediction_type)
         elif key == "euler":     # the SDXL checkpoints' own scheduler (generate_images_xl.py pipelines)
             self.sched = schedulers.EulerDiscreteScheduler(prediction_type=prediction_type, **spacing)
+            self.sched_generator = None
+        elif key == "dpmpp_2m":
+            self.sched = schedulers.DPMSolverPP2MScheduler(prediction_type=prediction_type, **spacing)
             self.sched_generator = None
         else:
             self.sched = (schedulers.EulerAncestralDiscreteScheduler(prediction_type=prediction_type, **spacing) if spacing
@@ -85,6 +102,8 @@ class SliderSampler:
         drv = Pass(eng, p)
         drv.load_cond(ctx, pooled, time_ids)
         with self.slider_session(scale, start_noise) as gate:
+            if self.latents == "fp32":
+                return self._sample_fp32(drv, gate, noise, ddim_steps, guidance_scale, single)
             if not self.sched.fused:
                 return self._sample_unfused(drv, gate, noise, ddim_steps, guidance_scale, single)
             io, smp = p.io, p.io["sample"]
@@ -156,6 +175,35 @@ class SliderSampler:
             return eps
 
         return schedulers.denoise(sch, predict, lat, steps, steps, generator=self.sched_generator, device=eng.device)
+
+    def _sample_fp32(self, drv: Pass, gate, noise, steps, guidance_scale, single=False):
+        """The same loop on an fp32 master latent: per step slider gate -> UNet replay -> ONE slh_sigma_step launch (the row of
+        schedulers.step_row), which does the guidance combine and the scheduler's step in fp32, keeps the multistep history (a ring of
+        min(order, steps) - 1 fp32 buffers owned by this call) and writes the next pass's scaled input into io["sample"], both halves
+        for the pair.  The first scaled input is written ahead of the loop; inside it Pass.load_latents is not called.  euler_a / ddpm:
+        the noise of all steps is one fp32 draw from sched_generator per call - seed-deterministic, and deliberately not the bf16
+        path's draws (those are bf16 tensors drawn step by step).  Returns the bf16 rounding of the final latent."""
+        eng, sch, io = self.eng, self.sched, drv.io
+        bs = noise.shape[0]
+        chw = noise[0].numel()
+        s = torch.cuda.current_stream().cuda_stream
+        sch.set_timesteps(steps, device=eng.device)        # init_noise_sigma is the grid's
+        rows = [schedulers.step_row(sch, i, steps) for i in range(steps)]
+        x = (noise.to(eng.device, torch.float32) * sch.init_noise_sigma).contiguous()
+        ring = [torch.empty_like(x) for _ in range(schedulers.history_depth(sch, steps))]
+        draws = (torch.randn((steps,) + tuple(x.shape), generator=self.sched_generator, device=eng.device, dtype=torch.float32)
+                 if any(r.c_n != 0.0 for r in rows) else None)
+        smp = io["sample"]
+        drv.load_latents(sch.scale_model_input(x, sch.timesteps[0]))
+        for i, (t, r) in enumerate(zip(sch.timesteps.tolist(), rows)):
+            drv.run(t, gate(t, i == 0), s)
+            lib.sigma_step(s, eps=io["eps"].ptr, x=x.data_ptr(), out=x.data_ptr(), nb=bs, chw=chw, kind=r.kind, p=r.p, q=r.q,
+                           sigma=r.sigma, a=r.a, c=r.c, c_n=r.c_n, s_next=r.s_next, guidance=float(guidance_scale), single=single,
+                           hist=[ring[(i - k) % len(ring)].data_ptr() for k in range(1, r.n_hist + 1)],
+                           noise=draws[i].data_ptr() if draws is not None and r.c_n != 0.0 else 0,
+                           hist_out=ring[i % len(ring)].data_ptr() if ring else 0,
+                           in_bf16=smp.ptr, in2_bf16=0 if single else smp.ptr + bs * chw * 2)
+        return x.to(torch.bfloat16)
 
     @torch.no_grad()
     def generate(self, ctx, noise, **kw) -> torch.Tensor:

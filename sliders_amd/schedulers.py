@@ -14,11 +14,16 @@ Interface = what the reference's loop uses: `.timesteps`, `.set_timesteps(n, dev
 SliderTrainer to run its scheduler-agnostic denoise loop.  Extension for tests: `step(..., noise=)` supplies the
 per-step noise instead of drawing it.
 
+Inference only (SliderSampler, latents="fp32"): `step_row` states one step of any of these classes - and of DPMSolverPP2MScheduler,
+which exists for that path alone - as the coefficient row of the fused fp32 step slh_sigma_step (docs/SAMPLING.md); the classes and
+the trainer's `denoise` are untouched by it.
+
 CPU-validated against oracle/sched_oracle.py (tests/test_schedulers.py); the trainer branch that drives them was written
 without GPU access at the end of round 2 and has not run on hardware yet.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass, field
 from typing import List, Optional
 
 import numpy as np
@@ -241,6 +246,120 @@ class LMSDiscreteScheduler(_SigmaBase):
         lms_coeffs = [self.get_lms_coefficient(order, step_index, curr_order) for curr_order in range(order)]
         prev_sample = sample + sum(coeff * derivative for coeff, derivative in zip(lms_coeffs, reversed(self.derivatives)))
         return SchedulerOutput(prev_sample, pred_original_sample)
+
+
+class DPMSolverPP2MScheduler(_SigmaBase):
+    """DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2) in sigma space, where alpha = 1 and lambda = -ln sigma: second-order multistep
+    over the history of predicted clean samples, first order on the first step and on a step that ends at sigma = 0.  Not one of the
+    reference's schedulers (create() does not know it) - inference only, and on the engine only as rows of the fused fp32 step
+    (step_row, slh_sigma_step): this tensor-op `step`, with float64 scalars from the fp32 sigma table, is the host-side statement
+    those rows are tested against.  Grids as EulerDiscreteScheduler, plus "trailing"."""
+
+    def __init__(self, *a, timestep_spacing: str = "leading", steps_offset: int = 1, **k):
+        if timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: linspace, leading and trailing are implemented")
+        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
+        super().__init__(*a, **k)
+
+    def _on_set_timesteps(self):
+        self.denoised: List[torch.Tensor] = []       # the predicted clean samples of the steps so far, oldest first (the last is read)
+        self._sigma_list = self.sigmas.tolist()
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, noise=None) -> SchedulerOutput:
+        i = self.index_of(timestep)
+        sig = self._sigma_list
+        x0 = self._pred_original(model_output, sample, self.sigmas[i])
+        old = self.denoised[-1] if self.denoised else None
+        self.denoised = [x0]
+        if sig[i + 1] == 0.0:
+            return SchedulerOutput(x0, x0)
+        h = np.log(sig[i]) - np.log(sig[i + 1])          # lambda_next - lambda
+        d = x0
+        if old is not None:
+            r = (np.log(sig[i - 1]) - np.log(sig[i])) / h
+            d = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * old
+        return SchedulerOutput((sig[i + 1] / sig[i]) * sample - float(np.expm1(-h)) * d, x0)
+
+
+@dataclass
+class StepRow:
+    """One step of a scheduler as the coefficients of slh_sigma_step (include/sliders_hip.h):
+        x0 = p x + q m;  H0 = kind == 0 ? (x - x0) / sigma : x0;  out = a x + c[0] H0 + sum_k c[k] H[k] + c_n noise;  input = out s_next
+    with H[1..n_hist] the H0 of the n_hist steps before, newest first.  c has n_hist + 1 entries."""
+    kind: int
+    p: float
+    q: float
+    sigma: float
+    a: float
+    c: tuple
+    c_n: float
+    s_next: float
+    n_hist: int = field(init=False)
+
+    def __post_init__(self):
+        self.c = tuple(self.c)
+        self.n_hist = len(self.c) - 1
+
+
+def history_depth(sched, n_steps: int) -> int:
+    """fp32 history buffers the rows of an n_steps grid read: min(order, n_steps) - 1"""
+    order = 4 if isinstance(sched, LMSDiscreteScheduler) else 2 if isinstance(sched, DPMSolverPP2MScheduler) else 1
+    return min(order, n_steps) - 1
+
+
+def step_row(sched, i: int, n_steps: int, rounded: bool = True) -> StepRow:
+    """Step i of sched's n_steps grid (sched.set_timesteps(n_steps) has been called) as a StepRow.  Every value is computed in float64
+    from the scheduler's own fp32 sigma / alpha tables and rounded once to fp32 (rounded = False: left in float64, for tests); lms
+    takes its coefficients from the class's get_lms_coefficient, so both paths integrate the same numbers."""
+    if sched.num_inference_steps != n_steps or not 0 <= i < n_steps:
+        raise ValueError(f"step_row: step {i} of {n_steps}: the scheduler is set to {sched.num_inference_steps} steps")
+    v = sched.prediction_type == "v_prediction"
+    if isinstance(sched, DDPMScheduler):
+        t = int(sched.timesteps[i])
+        prev_t = t - sched.num_train_timesteps // n_steps
+        ac = sched.alphas_cumprod.double()
+        a_t, a_p = float(ac[t]), float(ac[prev_t]) if prev_t >= 0 else 1.0
+        cur_alpha = a_t / a_p
+        cur_beta = 1 - cur_alpha
+        p, q = (a_t ** 0.5, -(1 - a_t) ** 0.5) if v else (1 / a_t ** 0.5, -(1 - a_t) ** 0.5 / a_t ** 0.5)
+        variance = max((1 - a_p) / (1 - a_t) * cur_beta, 1e-20)
+        row = StepRow(1, p, q, 0.0, cur_alpha ** 0.5 * (1 - a_p) / (1 - a_t), [a_p ** 0.5 * cur_beta / (1 - a_t)],
+                      variance ** 0.5 if t > 0 else 0.0, 1.0)
+    elif isinstance(sched, _SigmaBase):
+        sig = sched.sigmas.double().tolist()
+        s, s1 = sig[i], sig[i + 1]
+        p, q = (1 / (s * s + 1), -s / (s * s + 1) ** 0.5) if v else (1.0, -s)
+        kind, a, c, c_n = 0, 1.0, None, 0.0
+        if isinstance(sched, EulerDiscreteScheduler):
+            c = [s1 - s]
+        elif isinstance(sched, EulerAncestralDiscreteScheduler):
+            up = (s1 * s1 * (s * s - s1 * s1) / (s * s)) ** 0.5
+            c, c_n = [(s1 * s1 - up * up) ** 0.5 - s], up
+        elif isinstance(sched, LMSDiscreteScheduler):
+            order = min(i + 1, 4)
+            c = [sched.get_lms_coefficient(order, i, k) for k in range(order)]
+        elif isinstance(sched, DPMSolverPP2MScheduler):
+            kind = 1
+            if s1 == 0.0:
+                a, c = 0.0, [1.0]
+            else:
+                a = s1 / s
+                h = np.log(s) - np.log(s1)
+                e = float(np.expm1(-h))
+                if i == 0:
+                    c = [-e]
+                else:
+                    r = (np.log(sig[i - 1]) - np.log(s)) / h
+                    c = [-e * (1 + 1 / (2 * r)), e / (2 * r)]
+        if c is None:
+            raise ValueError(f"step_row: {type(sched).__name__} has no row")
+        row = StepRow(kind, p, q, s, a, c, c_n, 1 / (s1 * s1 + 1) ** 0.5)
+    else:
+        raise ValueError(f"step_row: {type(sched).__name__} has no row")
+    if rounded:
+        f32 = lambda x: float(np.float32(x))
+        row = StepRow(row.kind, f32(row.p), f32(row.q), f32(row.sigma), f32(row.a), [f32(x) for x in row.c], f32(row.c_n), f32(row.s_next))
+    return row
 
 
 def denoise(sched, predict, latents: torch.Tensor, k: int, num_steps: int, generator=None, device=None) -> torch.Tensor:
