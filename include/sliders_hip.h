@@ -489,6 +489,28 @@ int slh_ddpm_edit_step(const slh_ddpm_edit_desc* d, slh_stream_t stream);
  * Apart from the two aliases named above, no output may overlap an input. */
 int slh_sigma_step(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
 
+/* The blend behind every step of a localised sampling run (csrc/latent_blend.hip, docs/SAMPLING.md, "Localised sampling"): the latent
+ * a step just produced against the latent the scale-0 chain of the same seed had after the same step, under a mask with one value per
+ * latent pixel.  Never recorded in a program: no opcode, no descriptor struct; three host arrays, as slh_sigma_step.  Per element,
+ * with k = keep, m = mask, fp32 throughout (bf16 inputs widen exactly), one rounding per operation, nothing contracted:
+ *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          the select-then-lerp of slh_ddpm_edit_blend
+ * A NaN in e does not reach a pixel with m = 0, nor a NaN in keep a pixel with m = 1.  Mask values outside [0, 1] are the caller's error.
+ * ptrs[6]: 0 e        the latent the step just produced   [nb][chw]
+ *          1 keep     the base chain's latent after the same step   [nb][chw]
+ *          2 mask     fp32 [nb][hw] in [0,1], one value per latent pixel, shared by the channels (index b*hw + i % hw)
+ *          3 out      [nb][chw]; may alias e
+ *          4, 5 in_bf16, in2_bf16   optional bf16 [nb][chw]: the two halves of the CFG pair's sample input
+ * dims[4]: 0 nb, 1 chw, 2 hw (chw % hw == 0), 3 dtype (0: e/keep/out bf16; 1: fp32)
+ * coef[1]: 0 s_next (dtype 1 only; not read for dtype 0)
+ * dtype 1: out is fp32 and the bf16 copies are round-to-nearest-even(out * s_next), as slh_sigma_step writes them.
+ * dtype 0: out is the round-to-nearest-even bf16 of the fp32 result (m = 0: keep's bits, m = 1: e's bits); the copies are out's bits.
+ * Every thread reads all it needs before it writes, so out may alias e.  16-byte accesses where every pointer, chw and hw allow them
+ * (a multiple of 4 elements for dtype 1, of 8 for dtype 0), one element per thread otherwise; any chw >= 1 works.
+ * Refused before the launch (slh_last_error): a null e / keep / mask / out; an fp32 pointer that is not 4-byte or a bf16 pointer that
+ * is not 2-byte aligned; nb < 1, chw < 1, hw < 1, chw % hw != 0; dtype out of range; a non-finite s_next with dtype 1; keep or mask
+ * overlapping an output. */
+int slh_latent_blend(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+
 /* The edit step of a localised edit: e = mu + resid exactly as slh_ddpm_edit_step mode 1 forms it (one piece of code), then, with
  * k = keep[i] and m = mask[b*hw + i % hw] (one mask value per latent pixel, shared by the channels),
  *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          fp32, one rounding per operation, no contraction.

@@ -413,6 +413,21 @@ def word_map_reference(collect: Callable[[torch.Tensor, int], Dict[int, torch.Te
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the engine
 # ---------------------------------------------------------------------------------------------------------------------------------
+class _SpaceSource:
+    """A NoiseSpace as the source of SliderSampler._footprint / _word_map: the grid, the UNet input at step i (the inversion's own
+    latents), the conditioning and the guidance"""
+
+    def __init__(self, editor: "SliderEditor", space: NoiseSpace):
+        dev = editor.eng.device
+        self.visited = editor.trajectory(space).visited.to(dev, torch.float32)
+        self.x_start = space.x_start.to(dev, torch.float32)
+        self.timesteps, self.guidance = space.timesteps, space.guidance
+        self.ctx, self.pooled, self.time_ids = space.ctx, space.pooled, space.time_ids
+
+    def unet_input(self, i: int) -> torch.Tensor:
+        return self.x_start if i == 0 else self.visited[i - 1]
+
+
 class SliderEditor(SliderSampler):
     """SliderSampler (same constructor; the scheduler must be DDIM) that also inverts a given image's latents into a NoiseSpace and
     edits them.  With store= the inversion and the edit replay the adapter program ("on", multiplier 0 resp. `scale`); with sliders=
@@ -555,31 +570,8 @@ class SliderEditor(SliderSampler):
         program on the first pass after it) for the slider-on passes: 2 * len(draws) UNet passes."""
         self._check_prediction(space)
         self._check_conditioning(space, "footprint")
-        idx = footprint_draws(space.timesteps, start_noise, draws, t_min)
-        dev = self.eng.device
-        visited = self.trajectory(space).visited.to(dev, torch.float32)
-        x_start = space.x_start.to(dev, torch.float32)
-        bs, ch, h, w = x_start.shape
-        drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids)
-        io = drv.io
-        off = torch.empty((len(idx),) + tuple(io["eps"].tensor.shape), dtype=torch.bfloat16, device=dev)
-        A = torch.empty((len(idx), bs, h, w), dtype=torch.float32, device=dev)
-        s = torch.cuda.current_stream().cuda_stream
-        with self.slider_session(scale, start_noise, zero_merges=False) as gate:
-            def unet(n, i, multiplier):
-                """pass n of this call at step i of the grid; n and the multiplier choose the program as in the edit's chain"""
-                drv.load_latents(x_start if i == 0 else visited[i - 1])
-                drv.run(space.timesteps[i], gate(space.timesteps[i], n == 0, multiplier), s)
-
-            for j, i in enumerate(idx):
-                unet(j, i, 0.0)
-                off[j].copy_(io["eps"].tensor)
-            for j, i in enumerate(idx):
-                unet(len(idx) + j, i, scale)
-                d = lib.EpsAbsdiffDesc(eps_a=io["eps"].ptr, eps_b=off[j].data_ptr(), out=A[j].data_ptr(), nb=bs, chw=ch * h * w, hw=h * w,
-                                       guidance=float(space.guidance))
-                lib.call(lib.OP_EPS_ABSDIFF, d, s)
-        return footprint_mean(A)
+        footprint_draws(space.timesteps, start_noise, draws, t_min)          # the grid's errors before the trajectory is replayed
+        return self._footprint(_SpaceSource(self, space), scale, start_noise, draws, t_min)
 
     @torch.no_grad()
     def word_map(self, space: NoiseSpace, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None, draws: int = 8,
@@ -593,24 +585,8 @@ class SliderEditor(SliderSampler):
         none of them depends on a slider.  The edit's own plans are not touched; the next chain starts with its full program."""
         self._check_prediction(space)
         self._check_conditioning(space, "word_map")
-        idx = footprint_draws(space.timesteps, space.timesteps[0], draws, 0)
-        eng, dev = self.eng, self.eng.device
-        visited = self.trajectory(space).visited.to(dev, torch.float32)
-        x_start = space.x_start.to(dev, torch.float32)
-        bs, _, h, w = x_start.shape
-        wt = key_weights(bs, eng.ctx_len, tokens, weights)
-        drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids, attn_maps={"max_factor": int(max_factor)})
-        io = drv.io
-        io["xattn_wt"].tensor.copy_(wt)
-        levels = {int(k.split(".")[1]): b for k, b in io.items() if k.startswith("xattn_map.")}
-        s = torch.cuda.current_stream().cuda_stream
-        total = torch.zeros((bs, h, w), dtype=torch.float32, device=dev)
-        with self.slider_session(0.0, -1, zero_merges=False) as gate:
-            for n, i in enumerate(idx):
-                drv.load_latents(x_start if i == 0 else visited[i - 1])
-                drv.run(space.timesteps[i], gate(space.timesteps[i], n == 0), s)
-                total += level_mean({f: b.tensor for f, b in levels.items()}, h, w)
-        return total / float(len(idx))
+        footprint_draws(space.timesteps, space.timesteps[0], draws, 0)
+        return self._word_map(_SpaceSource(self, space), tokens, weights, draws, max_factor)
 
     @torch.no_grad()
     def edit(self, space: NoiseSpace, **kw) -> torch.Tensor:
@@ -686,6 +662,12 @@ def check_args(a):
         scales = [float(v) for v in a.scales.split(",")]
     except ValueError:
         raise SystemExit(f"--scales {a.scales!r}: expected comma-separated numbers")
+    check_mask_args(a, scales, lambda: edit_timesteps(DDIMSchedule(), a.steps, skip))
+    return scales
+
+
+def check_mask_args(a, scales: List[float], grid: Callable[[], List]):
+    """the argument errors of the mask options (shared with sliders_amd.generate); grid() -> the timesteps the run will visit"""
     word = bool(a.mask_word) or a.mask_tokens is not None
     if sum([bool(a.mask), bool(a.auto_mask), bool(a.mask_word), a.mask_tokens is not None]) > 1:
         raise SystemExit("--mask reads a mask, --auto_mask derives one from the slider, --mask_word / --mask_tokens from the prompt: give one of them")
@@ -728,17 +710,61 @@ def check_args(a):
             raise SystemExit(f"--auto_mask_threshold {a.auto_mask_threshold}: expected 0 < threshold <= 1")
         if a.auto_mask_dilate is not None and a.auto_mask_dilate < 0:
             raise SystemExit(f"--auto_mask_dilate {a.auto_mask_dilate}: expected >= 0")
-        grid = edit_timesteps(DDIMSchedule(), a.steps, skip)
         try:
-            footprint_draws(grid, a.start_noise, a.auto_mask_draws or 8)
+            footprint_draws(grid(), a.start_noise, a.auto_mask_draws or 8)
         except ValueError as e:
             raise SystemExit(f"--auto_mask: {e}")
-    return scales
+
+
+def _suffixed(path: str, suffix: str) -> str:
+    root, ext = os.path.splitext(path)
+    return root + suffix + ext
+
+
+def mask_from_args(a, ed, src, res: int, prompt: str, tokenizer, suffix: str = ""):
+    """The mask the command line asks for, or None: from the file (--mask), from the slider's footprint (--auto_mask: ed.footprint over
+    src) or from the prompt's words (--mask_word / --mask_tokens: ed.word_map over src); --save_attention and --save_mask are written
+    here (suffix: put in front of their extensions).  ed / src: a SliderEditor and its NoiseSpace, or a SliderSampler and a SampleTrace.
+    res: the image size the latents decode to."""
+    from PIL import Image
+    mask = None
+    if a.mask:
+        mask = feather_mask(load_mask(a.mask, res, a.mask_invert), a.mask_feather or 0.0)
+    elif a.auto_mask:
+        try:          # (check_args tried the grid of the command line; a saved inversion brings its own)
+            F = ed.footprint(src, a.auto_mask_scale, start_noise=a.start_noise, draws=a.auto_mask_draws or 8)
+            mask = footprint_mask(F.cpu(), threshold=0.5 if a.auto_mask_threshold is None else a.auto_mask_threshold,
+                                  dilate=1 if a.auto_mask_dilate is None else a.auto_mask_dilate,
+                                  feather=1.0 if a.mask_feather is None else a.mask_feather)
+        except ValueError as e:
+            raise SystemExit(f"--auto_mask: {e}")
+    elif a.mask_word or a.mask_tokens is not None:
+        try:
+            tokens = sorted({i for wd in a.mask_word for i in word_token_indices(prompt, wd, tokenizer, ed.eng.ctx_len)}) if a.mask_word \
+                else a.mask_token_list
+            F = ed.word_map(src, tokens=tokens, draws=a.mask_word_draws or 8).cpu()
+            mask = word_mask(F, threshold=0.3 if a.mask_word_threshold is None else a.mask_word_threshold,
+                             feather=1.0 if a.mask_feather is None else a.mask_feather)
+        except ValueError as e:
+            raise SystemExit(f"--mask_word / --mask_tokens: {e}")
+        if a.mask_invert:
+            mask = 1.0 - mask
+        print(f"word map over key positions {tokens}: maximum {float(F.max()):.4f}")
+        if a.save_attention:
+            a8 = (F[0] / F[0].max() * 255.0).round().to(torch.uint8)
+            Image.fromarray(a8.numpy()).save(_suffixed(a.save_attention, suffix))
+            print(f"attention saved to {_suffixed(a.save_attention, suffix)}")
+    if a.save_mask:
+        m8 = (mask.reshape(mask.shape[-2:]) * 255.0).round().to(torch.uint8)
+        Image.fromarray(m8.cpu().numpy()).save(_suffixed(a.save_mask, suffix))
+        print(f"mask saved to {_suffixed(a.save_mask, suffix)}: mean {float(mask.mean()):.3f}")
+    return mask
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     scales = check_args(a)
+    tokenizer = None
     from .generate import parse_compose, parse_slider_name, slider_rank
     held = [parse_compose(c) for c in a.compose]
     from PIL import Image
@@ -805,36 +831,9 @@ def main(argv=None):
     os.makedirs(a.out, exist_ok=True)
     Image.fromarray(VaeDecoder.to_uint8(dec.decode(space.recon))[0].cpu().numpy()).save(os.path.join(a.out, "recon.png"))
     kw = dict(start_noise=a.start_noise, guidance_scale=a.edit_guidance_scale)
-    if a.mask:
-        kw["mask"] = feather_mask(load_mask(a.mask, 8 * space.x0.shape[-1], a.mask_invert), a.mask_feather or 0.0)    # a saved inversion: its size
-    elif a.auto_mask:
-        try:          # (check_args tried the grid of --steps / --skip; a saved inversion brings its own)
-            F = ed.footprint(space, a.auto_mask_scale, start_noise=a.start_noise, draws=a.auto_mask_draws or 8)
-            kw["mask"] = footprint_mask(F.cpu(), threshold=0.5 if a.auto_mask_threshold is None else a.auto_mask_threshold,
-                                        dilate=1 if a.auto_mask_dilate is None else a.auto_mask_dilate,
-                                        feather=1.0 if a.mask_feather is None else a.mask_feather)
-        except ValueError as e:
-            raise SystemExit(f"--auto_mask: {e}")
-    elif a.mask_word or a.mask_tokens is not None:
-        try:
-            tokens = sorted({i for wd in a.mask_word for i in word_token_indices(a.prompt, wd, tokenizer, eng.ctx_len)}) if a.mask_word \
-                else a.mask_token_list
-            F = ed.word_map(space, tokens=tokens, draws=a.mask_word_draws or 8).cpu()
-            kw["mask"] = word_mask(F, threshold=0.3 if a.mask_word_threshold is None else a.mask_word_threshold,
-                                   feather=1.0 if a.mask_feather is None else a.mask_feather)
-        except ValueError as e:
-            raise SystemExit(f"--mask_word / --mask_tokens: {e}")
-        if a.mask_invert:
-            kw["mask"] = 1.0 - kw["mask"]
-        print(f"word map over key positions {tokens}: maximum {float(F.max()):.4f}")
-        if a.save_attention:
-            a8 = (F[0] / F[0].max() * 255.0).round().to(torch.uint8)
-            Image.fromarray(a8.numpy()).save(a.save_attention)
-            print(f"attention saved to {a.save_attention}")
-    if a.save_mask:
-        m8 = (kw["mask"].reshape(kw["mask"].shape[-2:]) * 255.0).round().to(torch.uint8)
-        Image.fromarray(m8.cpu().numpy()).save(a.save_mask)
-        print(f"mask saved to {a.save_mask}: mean {float(kw['mask'].mean()):.3f}")
+    mask = mask_from_args(a, ed, space, 8 * space.x0.shape[-1], a.prompt, tokenizer)    # a saved inversion: its size
+    if mask is not None:
+        kw["mask"] = mask
     if a.edit_prompt is not None:
         kw.update(ctx=cond[1][0].to(dev), pooled=None if cond[1][1] is None else cond[1][1].to(dev))
     for s in scales:

@@ -85,7 +85,79 @@ def build_parser(defaults: bool = True) -> argparse.ArgumentParser:
     add("--num_samples", type=int, default=1)
     add("--from_case", type=int, default=0)
     add("--till_case", type=int, default=1000000)
+    # localised sampling (docs/SAMPLING.md): the options of sliders_amd.edit, with the scale-0 image of the seed in place of a photograph
+    add("--mask", default=None, help="localise the slider: an image file, white = the slider acts, black = keep the scale-0 image bit for bit")
+    add("--mask_invert", action="store_true", help="with --mask: black = the slider acts")
+    add("--mask_feather", type=float, default=None, metavar="SIGMA",
+        help="Gaussian feathering of the mask in latent pixels (default 0 with --mask, 1 with --auto_mask)")
+    add("--auto_mask", action="store_true", help="localise the slider to its own footprint on the scale-0 image")
+    add("--auto_mask_scale", type=float, default=None, help="slider scale the footprint is measured at (default: the largest |scale| of --scales)")
+    add("--auto_mask_draws", type=int, default=None, help="noise levels the footprint averages over (default 8)")
+    add("--auto_mask_threshold", type=float, default=None, help="binarisation threshold of the footprint (default 0.5)")
+    add("--auto_mask_dilate", type=int, default=None, help="latent pixels the binary footprint is grown by (default 1)")
+    add("--mask_word", action="append", default=[], metavar="WORD",
+        help="localise the slider to where this word of the prompt lives in the cross-attention; repeatable (needs the model's tokenizer)")
+    add("--mask_tokens", default=None, metavar="I,J,...", help="the same from key positions of the prompt (BOS = 0)")
+    add("--mask_word_threshold", type=float, default=None, help="binarisation threshold of the word map / its maximum (default 0.3)")
+    add("--mask_word_draws", type=int, default=None, help="steps of the grid the word map averages over (default 8)")
+    add("--save_attention", default=None, help="write the word map / its maximum here (8-bit PNG at latent resolution)")
+    add("--save_mask", default=None, help="write the latent-resolution mask here (8-bit PNG)")
     return p
+
+
+def sampling_grid(a) -> list:
+    """the timesteps the run visits, from the scheduler SliderSampler will build (host tables only)"""
+    from . import schedulers
+    from .ddim import DDIMSchedule
+    if a.scheduler == "ddim":
+        return DDIMSchedule().make_timesteps(a.ddim_steps)
+    spacing = {} if a.timestep_spacing is None else {"timestep_spacing": a.timestep_spacing}
+    if a.scheduler == "euler":
+        sch = schedulers.EulerDiscreteScheduler(**spacing)
+    elif a.scheduler == "dpmpp_2m":
+        sch = schedulers.DPMSolverPP2MScheduler(**spacing)
+    else:
+        sch = schedulers.EulerAncestralDiscreteScheduler(**spacing) if spacing else schedulers.create(a.scheduler)
+    sch.set_timesteps(a.ddim_steps)
+    return sch.timesteps.tolist()
+
+
+def masked(a) -> bool:
+    return bool(a.mask or a.auto_mask or a.mask_word or a.mask_tokens is not None)
+
+
+def check_args(a):
+    """the scales, and every argument error of the mask options, before any model is built"""
+    from .edit import check_mask_args
+    scales = [float(v) for v in a.scales.split(",")]
+    check_mask_args(a, scales, lambda: sampling_grid(a))
+    if masked(a):
+        if a.scheduler not in ("ddim", "dpmpp_2m") and not a.fp32_latents:
+            raise SystemExit(f"--mask / --auto_mask / --mask_word / --mask_tokens with --scheduler {a.scheduler}: the bf16 tensor-op path keeps no "
+                             "trace of the scale-0 chain; add --fp32_latents (or sample with ddim)")
+        if a.no_cfg and (a.mask_word or a.mask_tokens is not None):
+            raise SystemExit("--mask_word / --mask_tokens read the cross-attention of the text half of the CFG pair: not with --no_cfg")
+    return scales
+
+
+def shares_prefix(a, scales) -> bool:
+    """An unmasked sweep that contains scale 0 and another scale, on a loop without noise draws or multistep history: the scale-0 run
+    is kept as a trace and the other scales start where the slider starts to act - the same images, bit for bit (asserted by
+    tests/test_masked_sampling_gpu.py), without the replays of the steps every scale shares"""
+    return 0.0 in scales and len(scales) > 1 and (a.scheduler == "ddim" or (a.scheduler == "euler" and a.fp32_latents))
+
+
+def traced_sweep(a, smp, scales, ctx, pooled, noise, prompt, tokenizer, suffix=""):
+    """One seed over its scale-0 trace: with mask options the mask is derived from the trace once and every scale is blended against
+    it; scale 0 is the trace's own image.  Yields (scale, uint8 image [H][W][3] on the host)."""
+    from .edit import mask_from_args
+    from .vae import VaeDecoder
+    trace = smp.base_trace(ctx, noise, a.ddim_steps, a.guidance_scale, pooled, None, a.start_noise)
+    mask = mask_from_args(a, smp, trace, a.res, prompt, tokenizer, suffix) if masked(a) else None
+    for s in scales:
+        lat = trace.final if s == 0.0 else smp.sample_latents(ctx, noise, scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,
+                                                              guidance_scale=a.guidance_scale, pooled=pooled, mask=mask, trace=trace)
+        yield s, VaeDecoder.to_uint8(smp.decoder.decode(lat))[0].cpu().numpy()
 
 
 def parse_compose(spec: str) -> Tuple[str, float]:
@@ -137,6 +209,8 @@ def main(argv=None):
     from .sampler import SliderSampler
     from .vae import VAE_SCALING, VaeDecoder, random_vae_state_dict
     a = resolve_sampling(build_parser().parse_args(argv), explicit_args(argv))
+    scales = check_args(a)
+    tokenizer = None
     dev = torch.device("cuda", a.device)
     xl = a.model == "sdxl"
     res = a.res
@@ -158,10 +232,12 @@ def main(argv=None):
         dec = VaeDecoder(load_file(os.path.join(a.model_path, "vae", "diffusion_pytorch_model.safetensors")), dev, VAE_SCALING[a.model])
         if xl:
             toks, encs = model_util.load_text_encoders_xl(a.model_path, dev, torch.bfloat16)
+            tokenizer = toks[0]
             enc_xl = [model_util.encode_prompts_xl(toks, encs, [s]) for s in prompts(a.prompt)]
             ctx, pooled = torch.cat([e for e, _ in enc_xl]), torch.cat([q for _, q in enc_xl])
         else:
             tok, enc = model_util.load_text_encoder(a.model_path, dev, torch.bfloat16)
+            tokenizer = tok
             ctx, pooled = torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in prompts(a.prompt)]), None
     store = sliders = None
     swept = torch.load(a.lora_weight, map_location="cpu") if a.lora_weight else None
@@ -180,7 +256,7 @@ def main(argv=None):
                         timestep_spacing=a.timestep_spacing, latents="fp32" if a.fp32_latents else None)
     os.makedirs(a.out, exist_ok=True)
     from PIL import Image
-    scales = [float(v) for v in a.scales.split(",")]
+    traced = masked(a) or shares_prefix(a, scales)
     if a.prompts_path:
         # the reference's evaluation set-up: one row per case, every scale from the same seed, one folder per scale
         import pandas as pd
@@ -201,6 +277,13 @@ def main(argv=None):
             else:
                 c_row, p_row = torch.cat([model_util.encode_prompts(tok, enc, [t]) for t in prompts(str(row.prompt))]), None
             for num in range(a.num_samples):
+                if traced:
+                    g = torch.Generator().manual_seed(int(row.evaluation_seed) + num)
+                    noise = torch.randn(1, 4, res // 8, res // 8, generator=g)
+                    for s, img in traced_sweep(a, smp, scales, c_row.to(dev), p_row.to(dev) if p_row is not None else None, noise.to(dev),
+                                               str(row.prompt), tokenizer, f"_{case}_{num}"):
+                        Image.fromarray(img).save(os.path.join(root, scale_folder(s), f"{case}_{num}.png"))
+                    continue
                 for s in scales:
                     g = torch.Generator().manual_seed(int(row.evaluation_seed) + num)          # the same noise for every scale
                     noise = torch.randn(1, 4, res // 8, res // 8, generator=g)
@@ -209,6 +292,12 @@ def main(argv=None):
                     Image.fromarray(img[0].cpu().numpy()).save(os.path.join(root, scale_folder(s), f"{case}_{num}.png"))
             print(f"case {case}: {a.num_samples} sample(s) x {len(scales)} scales saved under {root}")
         return root
+    if traced:
+        noise = torch.randn(1, 4, res // 8, res // 8, generator=torch.Generator().manual_seed(a.seed))
+        for s, img in traced_sweep(a, smp, scales, ctx.to(dev), pooled.to(dev) if pooled is not None else None, noise.to(dev), a.prompt, tokenizer):
+            Image.fromarray(img).save(os.path.join(a.out, f"scale_{s:g}.png"))
+            print(f"scale {s:g}: saved {os.path.join(a.out, f'scale_{s:g}.png')}")
+        return a.out
     for s in scales:
         noise = torch.randn(1, 4, res // 8, res // 8, generator=torch.Generator().manual_seed(a.seed))   # same seed per scale
         img = smp.generate(ctx.to(dev), noise.to(dev), scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,

@@ -183,6 +183,7 @@ _HOST_FNS = {
     "slh_lora_wgrad_geometry": (c_i32, [_P(WgradDesc), c_i32, _P(c_i32)]),
     "slh_transpose_heads_blocks": (c_i32, [_P(TransposeDesc)]), "slh_lora_merge_blocks": (c_i32, [_P(LoraMergeItem)]),
     "slh_sigma_step": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
+    "slh_latent_blend": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
 }
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
@@ -451,6 +452,17 @@ def sigma_step(stream: int, *, eps: int, x: int, out: int, nb: int, chw: int, ki
     dims = (c_i32 * 5)(nb, chw, len(hist), kind, int(bool(single)))
     coef = (c_f32 * 11)(p, q, sigma, a, *(c + (0.0,) * (4 - len(c))), c_n, s_next, guidance)
     check(load().slh_sigma_step(ptrs, dims, coef, c_vp(stream)), "slh_sigma_step")
+
+
+def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int, chw: int, hw: int, fp32: bool, s_next: float = 1.0,
+                 in_bf16: int = 0, in2_bf16: int = 0):
+    """slh_latent_blend (include/sliders_hip.h): one launch of a localised sampling step's blend, out = keep where the mask is 0, e where
+    it is 1, keep + m (e - keep) between.  Pointers are device addresses (0: absent); fp32: e / keep / out are fp32 and the bf16 copies
+    are rne(out * s_next) (s_next rounded to fp32 here, as the kernel reads it), else they are bf16 and the copies are out's bits."""
+    ptrs = (c_vp * 6)(e, keep, mask, out, in_bf16, in2_bf16)
+    dims = (c_i32 * 4)(nb, chw, hw, 1 if fp32 else 0)
+    coef = (c_f32 * 1)(s_next)
+    check(load().slh_latent_blend(ptrs, dims, coef, c_vp(stream)), "slh_latent_blend")
 
 
 _GRAPHS_ON = os.environ.get("SLIDERS_HIPGRAPH", "1") != "0"

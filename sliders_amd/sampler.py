@@ -18,8 +18,9 @@ eval-scripts/clip_score.py) without the diffusers pipelines.
 from __future__ import annotations
 
 from contextlib import contextmanager
+from dataclasses import dataclass
 from itertools import count
-from typing import Optional
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -31,6 +32,38 @@ from .merge import SliderSet, WeightMerger
 from .passes import Pass
 from .unet import UNetEngine
 from .vae import VaeDecoder
+
+
+@dataclass
+class SampleTrace:
+    """What a scale-0 run of the sampling loop leaves (SliderSampler.base_trace): enough to run every other scale of the same seed
+    localised to a mask - the chain's latent after every step is what a masked run keeps outside the mask - and to start those runs
+    where the slider starts to act.  Tensors live on the engine's device, latents in the loop's dtype: bf16 for ddim, fp32 for
+    latents="fp32"."""
+    timesteps: List[float]                   # the grid
+    x_start: torch.Tensor                    # [bs][4][h][w] the starting latent (noise * init_noise_sigma)
+    visited: torch.Tensor                    # [steps][bs][4][h][w] the latent after every step; visited[-1] is the final latent
+    final: torch.Tensor                      # what sample_latents(scale=0) returns: bf16
+    draws: Optional[torch.Tensor]            # [steps][bs][4][h][w] fp32, the per-call noise of euler_a / ddpm (None elsewhere)
+    input0: torch.Tensor                     # the first pass's UNet input (the sigma-space loops scale x_start)
+    s_in: Optional[List[float]]              # fp32 loops: s_in[i], i >= 1, scales visited[i - 1] to pass i's input (row i - 1's s_next)
+    ctx: torch.Tensor                        # the conditioning and guidance of the run
+    pooled: Optional[torch.Tensor]
+    time_ids: Optional[torch.Tensor]
+    guidance: float
+    single: bool                             # one UNet row per image, no guidance
+    start_noise: float                       # (sliders= with sliders held at a fixed scale merges them there, at scale 0 too)
+
+    @property
+    def steps(self) -> int:
+        return len(self.timesteps)
+
+    def unet_input(self, i: int) -> torch.Tensor:
+        """what the UNet read at step i of the chain, to the bit once rounded to bf16 (Pass.load_latents)"""
+        if i == 0:
+            return self.input0
+        v = self.visited[i - 1]
+        return v if self.s_in is None else (v * self.s_in[i]).to(torch.bfloat16)      # one fp32 product, then rne: slh_sigma_step's copy
 
 
 class SliderSampler:
@@ -86,41 +119,117 @@ class SliderSampler:
     @torch.no_grad()
     def sample_latents(self, ctx: torch.Tensor, noise: torch.Tensor, scale: float = 0.0, start_noise: int = 750,
                        ddim_steps: int = 50, guidance_scale: float = 7.5, pooled: Optional[torch.Tensor] = None,
-                       time_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                       trace: Optional[SampleTrace] = None, share_prefix: bool = True) -> torch.Tensor:
         """ctx: (2*bs, 77, D) = cat([unconditional, text]); noise: (bs, 4, h, w) UNIT noise (it is multiplied by the
         scheduler's init_noise_sigma here, generate_images_sd1.py:165); returns the final latents (bs, 4, h, w) bf16.
         LoRA multiplier per step: 0 while t > start_noise, `scale` after.
         Single branch: a ctx of bs rows (the text prompt alone; pooled and time_ids then have bs rows too) samples without
         classifier-free guidance - one UNet row per image, guidance_scale is not read - as the reference's pipelines do for
-        guidance_scale <= 1 (the distilled few-step checkpoints)."""
+        guidance_scale <= 1 (the distilled few-step checkpoints).
+        mask ([h][w], [bs][h][w] or [bs][1][h][w], values in [0, 1], 1 = the slider acts): localised sampling (docs/SAMPLING.md).
+        After every step with t <= start_noise the latent is blended against the latent the scale-0 chain had after that step
+        (trace.visited[i], one slh_latent_blend launch), so where the mask is 0 the result is trace.final bit for bit, at any scale.
+        trace: the scale-0 run (base_trace) of this noise, conditioning, grid and guidance; built here if a mask comes without one.
+        With a trace the chain starts on trace.x_start and uses its noise draws, not the scheduler generator's next ones.
+        share_prefix: ddim, euler, euler_a, ddpm (no multistep history): start at the first step with t <= start_noise from the
+        trace's latent instead of replaying the steps every scale shares - the same bits.  ddim and latents="fp32" only."""
         eng = self.eng
         bs, _, h, w = noise.shape
         if ctx.shape[0] not in (bs, 2 * bs):
             raise ValueError(f"sample_latents: ctx has {ctx.shape[0]} rows for {bs} noise rows: expected {2 * bs} (the CFG pair) or {bs}")
         single = ctx.shape[0] == bs
+        local = {}
+        if mask is not None or trace is not None:
+            self._check_localised("sample_latents with mask= or trace=")
+            if mask is not None:
+                from .edit import as_mask          # (edit imports this module)
+                mask = as_mask(mask, bs, h, w).to(eng.device)
+                if trace is None:
+                    trace = self.base_trace(ctx, noise, ddim_steps, guidance_scale, pooled, time_ids, start_noise)
+            if trace.steps != ddim_steps or tuple(trace.x_start.shape) != tuple(noise.shape) or trace.single != single:
+                raise ValueError(f"sample_latents: the trace has {trace.steps} steps of {tuple(trace.x_start.shape)} latents, "
+                                 f"{'single branch' if trace.single else 'CFG pair'}: this call has {ddim_steps} of {tuple(noise.shape)}, "
+                                 f"{'single branch' if single else 'CFG pair'}")
+            local = dict(mask=mask, trace=trace, start_noise=start_noise, share_prefix=share_prefix)
         p = eng.plan(ctx.shape[0], h, w, "on" if self.store is not None else "off")
         drv = Pass(eng, p)
         drv.load_cond(ctx, pooled, time_ids)
         with self.slider_session(scale, start_noise) as gate:
             if self.latents == "fp32":
-                return self._sample_fp32(drv, gate, noise, ddim_steps, guidance_scale, single)
+                return self._sample_fp32(drv, gate, noise, ddim_steps, guidance_scale, single, **local)
             if not self.sched.fused:
                 return self._sample_unfused(drv, gate, noise, ddim_steps, guidance_scale, single)
-            io, smp = p.io, p.io["sample"]
-            drv.load_latents(noise)
-            s = torch.cuda.current_stream().cuda_stream
-            chw = eng.cfg.out_channels * h * w
-            half = bs * chw * 2
-            # single branch: the text half is read from the one epsilon there is and the guidance passed is 0 (guidance_scale is not
-            # read), so the combine u + 0 * (u - u) hands the step u itself
-            pair = ({"out2": 0, "eps_text": io["eps"].ptr, "guidance": 0.0} if single
-                    else {"out2": smp.ptr + half, "guidance": float(guidance_scale)})
-            for i, t in enumerate(self.sched.make_timesteps(ddim_steps)):
-                drv.run(t, gate(t, i == 0), s)
-                d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, nb=bs, chw=chw, **pair,
-                                    **self.sched.step_fields(t, ddim_steps))
-                lib.call(lib.OP_CFG_DDIM, d, s)
-            return smp.tensor[:bs].clone()
+            return self._sample_ddim(drv, gate, noise, ddim_steps, guidance_scale, single, **local)
+
+    def _check_localised(self, what: str):
+        if self.latents != "fp32" and not self.sched.fused:
+            raise ValueError(f"{what}: the bf16 tensor-op path of scheduler {type(self.sched).__name__} keeps no trace; use "
+                             "latents='fp32' (--fp32_latents) or ddim")
+
+    @torch.no_grad()
+    def base_trace(self, ctx: torch.Tensor, noise: torch.Tensor, ddim_steps: int = 50, guidance_scale: float = 7.5,
+                   pooled: Optional[torch.Tensor] = None, time_ids: Optional[torch.Tensor] = None, start_noise: int = 750) -> SampleTrace:
+        """The loop sample_latents runs at scale 0 - the same launches on the same inputs, the scheduler generator advanced as one call
+        advances it - with the latent after every step kept: trace.final is what sample_latents(scale=0) returns, bit for bit.
+        start_noise matters only to sliders= with sliders held at a fixed scale (merged below it at scale 0 too)."""
+        self._check_localised("base_trace")
+        eng = self.eng
+        bs, _, h, w = noise.shape
+        if ctx.shape[0] not in (bs, 2 * bs):
+            raise ValueError(f"base_trace: ctx has {ctx.shape[0]} rows for {bs} noise rows: expected {2 * bs} (the CFG pair) or {bs}")
+        single = ctx.shape[0] == bs
+        drv = Pass(eng, eng.plan(ctx.shape[0], h, w, "on" if self.store is not None else "off"))
+        drv.load_cond(ctx, pooled, time_ids)
+        rec = {}
+        with self.slider_session(0.0, start_noise) as gate:
+            loop = self._sample_fp32 if self.latents == "fp32" else self._sample_ddim
+            final = loop(drv, gate, noise, ddim_steps, guidance_scale, single, record=rec)
+        keep = lambda v: None if v is None else v.detach().clone()
+        return SampleTrace(final=final, ctx=keep(ctx), pooled=keep(pooled), time_ids=keep(time_ids), guidance=float(guidance_scale),
+                           single=single, start_noise=float(start_noise), **rec)
+
+    @staticmethod
+    def _first_live(ts: Sequence[float], start_noise: float) -> int:
+        """index of the first step of the grid at which the slider acts (t <= start_noise); len(ts) if there is none"""
+        return next((i for i, t in enumerate(ts) if not float(t) > start_noise), len(ts))
+
+    def _sample_ddim(self, drv: Pass, gate, noise, steps, guidance_scale, single=False, mask=None, trace=None, start_noise=750,
+                     share_prefix=True, record=None):
+        """The fused DDIM loop: per step slider gate -> UNet replay -> slh_cfg_ddim in place on io["sample"] (both halves for the pair).
+        record (a dict): the scale-0 run's SampleTrace fields are left there.  trace: start on its latent - at the first live step if
+        share_prefix - and, with a mask, blend io["sample"] in place against trace.visited[i] after every live step."""
+        eng, io, smp = self.eng, drv.io, drv.io["sample"]
+        bs, _, h, w = noise.shape
+        s = torch.cuda.current_stream().cuda_stream
+        chw = eng.cfg.out_channels * h * w
+        half = bs * chw * 2
+        # single branch: the text half is read from the one epsilon there is and the guidance passed is 0 (guidance_scale is not
+        # read), so the combine u + 0 * (u - u) hands the step u itself
+        pair = ({"out2": 0, "eps_text": io["eps"].ptr, "guidance": 0.0} if single
+                else {"out2": smp.ptr + half, "guidance": float(guidance_scale)})
+        ts = self.sched.make_timesteps(steps)
+        i0 = self._first_live(ts, start_noise) if trace is not None and share_prefix else 0
+        if i0 == len(ts):            # the slider never acts: the base chain itself
+            return trace.final.clone()
+        start = noise if trace is None else trace.x_start if i0 == 0 else trace.visited[i0 - 1]
+        drv.load_latents(start)
+        if record is not None:
+            record.update(timesteps=[float(t) for t in ts], x_start=smp.tensor[:bs].clone(), draws=None, s_in=None,
+                          visited=torch.empty((steps,) + tuple(noise.shape), dtype=torch.bfloat16, device=eng.device))
+            record["input0"] = record["x_start"]
+        for i in range(i0, steps):
+            t = ts[i]
+            drv.run(t, gate(t, i == i0), s)
+            d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, nb=bs, chw=chw, **pair,
+                                **self.sched.step_fields(t, steps))
+            lib.call(lib.OP_CFG_DDIM, d, s)
+            if mask is not None and not float(t) > start_noise:
+                lib.latent_blend(s, e=smp.ptr, keep=trace.visited[i].data_ptr(), mask=mask.data_ptr(), out=smp.ptr, nb=bs, chw=chw,
+                                 hw=h * w, fp32=False, in_bf16=0 if single else smp.ptr + half)
+            if record is not None:
+                record["visited"][i].copy_(smp.tensor[:bs])
+        return smp.tensor[:bs].clone()
 
     @contextmanager
     def slider_session(self, scale: float = 0.0, start_noise: float = 750, zero_merges: bool = True):
@@ -176,34 +285,136 @@ class SliderSampler:
 
         return schedulers.denoise(sch, predict, lat, steps, steps, generator=self.sched_generator, device=eng.device)
 
-    def _sample_fp32(self, drv: Pass, gate, noise, steps, guidance_scale, single=False):
+    def _sample_fp32(self, drv: Pass, gate, noise, steps, guidance_scale, single=False, mask=None, trace=None, start_noise=750,
+                     share_prefix=True, record=None):
         """The same loop on an fp32 master latent: per step slider gate -> UNet replay -> ONE slh_sigma_step launch (the row of
         schedulers.step_row), which does the guidance combine and the scheduler's step in fp32, keeps the multistep history (a ring of
         min(order, steps) - 1 fp32 buffers owned by this call) and writes the next pass's scaled input into io["sample"], both halves
         for the pair.  The first scaled input is written ahead of the loop; inside it Pass.load_latents is not called.  euler_a / ddpm:
         the noise of all steps is one fp32 draw from sched_generator per call - seed-deterministic, and deliberately not the bf16
-        path's draws (those are bf16 tensors drawn step by step).  Returns the bf16 rounding of the final latent."""
+        path's draws (those are bf16 tensors drawn step by step).  Returns the bf16 rounding of the final latent.
+        record / trace / mask: as _sample_ddim; the draws are the trace's, the blend is on the master latent and rewrites the scaled
+        input with the row's s_next.  A scheduler with a multistep history (lms, dpmpp_2m) runs the whole grid."""
         eng, sch, io = self.eng, self.sched, drv.io
         bs = noise.shape[0]
         chw = noise[0].numel()
+        hw = noise.shape[2] * noise.shape[3]
         s = torch.cuda.current_stream().cuda_stream
         sch.set_timesteps(steps, device=eng.device)        # init_noise_sigma is the grid's
         rows = [schedulers.step_row(sch, i, steps) for i in range(steps)]
-        x = (noise.to(eng.device, torch.float32) * sch.init_noise_sigma).contiguous()
-        ring = [torch.empty_like(x) for _ in range(schedulers.history_depth(sch, steps))]
-        draws = (torch.randn((steps,) + tuple(x.shape), generator=self.sched_generator, device=eng.device, dtype=torch.float32)
-                 if any(r.c_n != 0.0 for r in rows) else None)
+        ts = sch.timesteps.tolist()
+        depth = schedulers.history_depth(sch, steps)
+        i0 = self._first_live(ts, start_noise) if trace is not None and share_prefix and depth == 0 else 0
+        if i0 == steps:              # the slider never acts: the base chain itself
+            return trace.final.clone()
+        if trace is None:
+            x = (noise.to(eng.device, torch.float32) * sch.init_noise_sigma).contiguous()
+            draws = (torch.randn((steps,) + tuple(x.shape), generator=self.sched_generator, device=eng.device, dtype=torch.float32)
+                     if any(r.c_n != 0.0 for r in rows) else None)
+            first_input = sch.scale_model_input(x, sch.timesteps[0])
+        else:
+            x = (trace.x_start if i0 == 0 else trace.visited[i0 - 1]).clone()
+            draws, first_input = trace.draws, trace.unet_input(i0)
+        ring = [torch.empty_like(x) for _ in range(depth)]
         smp = io["sample"]
-        drv.load_latents(sch.scale_model_input(x, sch.timesteps[0]))
-        for i, (t, r) in enumerate(zip(sch.timesteps.tolist(), rows)):
-            drv.run(t, gate(t, i == 0), s)
+        drv.load_latents(first_input)
+        if record is not None:
+            record.update(timesteps=ts, x_start=x.clone(), draws=draws, input0=first_input.clone(), s_in=[1.0] + [r.s_next for r in rows[:-1]],
+                          visited=torch.empty((steps,) + tuple(x.shape), dtype=torch.float32, device=eng.device))
+        in2 = 0 if single else smp.ptr + bs * chw * 2
+        for i in range(i0, steps):
+            t, r = ts[i], rows[i]
+            drv.run(t, gate(t, i == i0), s)
             lib.sigma_step(s, eps=io["eps"].ptr, x=x.data_ptr(), out=x.data_ptr(), nb=bs, chw=chw, kind=r.kind, p=r.p, q=r.q,
                            sigma=r.sigma, a=r.a, c=r.c, c_n=r.c_n, s_next=r.s_next, guidance=float(guidance_scale), single=single,
                            hist=[ring[(i - k) % len(ring)].data_ptr() for k in range(1, r.n_hist + 1)],
                            noise=draws[i].data_ptr() if draws is not None and r.c_n != 0.0 else 0,
                            hist_out=ring[i % len(ring)].data_ptr() if ring else 0,
-                           in_bf16=smp.ptr, in2_bf16=0 if single else smp.ptr + bs * chw * 2)
+                           in_bf16=smp.ptr, in2_bf16=in2)
+            if mask is not None and not float(t) > start_noise:
+                lib.latent_blend(s, e=x.data_ptr(), keep=trace.visited[i].data_ptr(), mask=mask.data_ptr(), out=x.data_ptr(), nb=bs,
+                                 chw=chw, hw=hw, fp32=True, s_next=r.s_next, in_bf16=smp.ptr, in2_bf16=in2)
+            if record is not None:
+                record["visited"][i].copy_(x)
         return x.to(torch.bfloat16)
+
+    # -----------------------------------------------------------------------------------------------------------------------------
+    # where the slider acts / where a word lives, over a source: anything with .timesteps, .unet_input(i), .ctx / .pooled / .time_ids and
+    # .guidance - a SampleTrace here, an inversion's NoiseSpace in SliderEditor (sliders_amd/edit.py, which documents both maps)
+    # -----------------------------------------------------------------------------------------------------------------------------
+    def _source_pass(self, src, attn_maps=None) -> Pass:
+        """the plan of the source's shape with its conditioning written; attn_maps: the plan of the shape that also records attention
+        maps (UNetEngine.plan)"""
+        _, _, h, w = src.unet_input(0).shape
+        drv = Pass(self.eng, self.eng.plan(src.ctx.shape[0], h, w, "on" if self.store is not None else "off", attn_maps=attn_maps))
+        drv.load_cond(src.ctx, src.pooled, src.time_ids)
+        return drv
+
+    def _footprint(self, src, scale: float, start_noise, draws: int, t_min: int) -> torch.Tensor:
+        from .edit import footprint_draws, footprint_mean          # (edit imports this module)
+        ts = src.timesteps
+        idx = footprint_draws(ts, start_noise, draws, t_min)
+        dev = self.eng.device
+        bs, ch, h, w = src.unet_input(0).shape
+        drv = self._source_pass(src)
+        io = drv.io
+        single = src.ctx.shape[0] == bs          # one epsilon row per sample: both "halves" are it and the guidance is not read
+        off = torch.empty((len(idx),) + tuple(io["eps"].tensor.shape), dtype=torch.bfloat16, device=dev)
+        A = torch.empty((len(idx), bs, h, w), dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream().cuda_stream
+        with self.slider_session(scale, start_noise, zero_merges=False) as gate:
+            def unet(n, i, multiplier):
+                """pass n of this call at step i of the grid; n and the multiplier choose the program as in the chain"""
+                drv.load_latents(src.unet_input(i))
+                drv.run(ts[i], gate(ts[i], n == 0, multiplier), s)
+
+            for j, i in enumerate(idx):
+                unet(j, i, 0.0)
+                off[j].copy_(io["eps"].tensor)
+            for j, i in enumerate(idx):
+                unet(len(idx) + j, i, scale)
+                halves = dict(eps_a_text=io["eps"].ptr, eps_b_text=off[j].data_ptr()) if single else {}
+                d = lib.EpsAbsdiffDesc(eps_a=io["eps"].ptr, eps_b=off[j].data_ptr(), out=A[j].data_ptr(), nb=bs, chw=ch * h * w, hw=h * w,
+                                       guidance=0.0 if single else float(src.guidance), **halves)
+                lib.call(lib.OP_EPS_ABSDIFF, d, s)
+        return footprint_mean(A)
+
+    def _word_map(self, src, tokens, weights, draws: int, max_factor: int) -> torch.Tensor:
+        from .edit import footprint_draws, key_weights, level_mean
+        ts = src.timesteps
+        idx = footprint_draws(ts, ts[0], draws, 0)
+        eng, dev = self.eng, self.eng.device
+        bs, _, h, w = src.unet_input(0).shape
+        wt = key_weights(bs, eng.ctx_len, tokens, weights)
+        drv = self._source_pass(src, attn_maps={"max_factor": int(max_factor)})
+        io = drv.io
+        io["xattn_wt"].tensor.copy_(wt)
+        levels = {int(k.split(".")[1]): b for k, b in io.items() if k.startswith("xattn_map.")}
+        s = torch.cuda.current_stream().cuda_stream
+        total = torch.zeros((bs, h, w), dtype=torch.float32, device=dev)
+        with self.slider_session(0.0, -1, zero_merges=False) as gate:
+            for n, i in enumerate(idx):
+                drv.load_latents(src.unet_input(i))
+                drv.run(ts[i], gate(ts[i], n == 0), s)
+                total += level_mean({f: b.tensor for f, b in levels.items()}, h, w)
+        return total / float(len(idx))
+
+    @torch.no_grad()
+    def footprint(self, trace: SampleTrace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200) -> torch.Tensor:
+        """Where the slider acts on the image of this trace: SliderEditor.footprint's map F [bs][h][w] (slh_eps_absdiff between the slider
+        at `scale` and the slider off, over `draws` noise levels with t_min <= t <= start_noise), with the scale-0 chain's own UNet
+        inputs, conditioning and guidance in place of an inversion's.  edit.footprint_mask turns it into a mask."""
+        self._check_localised("footprint")
+        return self._footprint(trace, scale, start_noise, draws, t_min)
+
+    @torch.no_grad()
+    def word_map(self, trace: SampleTrace, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None, draws: int = 8,
+                 max_factor: int = 4) -> torch.Tensor:
+        """Where words of the prompt live on the image of this trace: SliderEditor.word_map's map F [bs][h][w] (slh_xattn_map, the slider
+        off) over `draws` steps of the scale-0 chain.  The maps are those of the text half of a CFG pair: a single-branch trace is
+        refused by the plan.  edit.word_mask turns it into a mask."""
+        self._check_localised("word_map")
+        return self._word_map(trace, tokens, weights, draws, max_factor)
 
     @torch.no_grad()
     def generate(self, ctx, noise, **kw) -> torch.Tensor:
