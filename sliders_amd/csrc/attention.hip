@@ -11,8 +11,9 @@
 // exactly the k-order the B operand of the second MFMA (O^T = V^T P^T) expects - P never leaves registers.
 // V is consumed transposed (VT[d][kv], produced by slh_transpose_heads) so both LDS tiles are read with
 // conflict-free swizzled ds_read_b128 exactly like the GEMM.
-#include "common.h"
-#include "../../include/sliders_hip.h"
+#include "attention_common.h"
+
+using namespace slh_attn_detail;
 
 namespace {
 
@@ -32,23 +33,12 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & 31, lhi = lane >> 5;
-    const int frow = lane >> 3, fslot = lane & 7;
-    // XCD-aware block order (block i runs on XCD i % 8, each with its own 4 MB L2): every XCD gets a contiguous run of the
-    // (sample, head, query block) sequence with the query block fastest, so the query blocks that share one head's K / V
-    // meet in ONE L2 instead of all eight (counter pass of the round-3 tree: 103 MB fetched per T = 4096 launch for 31 MB of
-    // Q, K, V; L2 hit 52 %)
-    int vb = blockIdx.x;
-    {
-        const int nblk = gridDim.x;
-        const int qd = nblk >> 3, rm = nblk & 7;
-        const int xcd = vb & 7, idx = vb >> 3;
-        vb = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-    }
+    const int vb = xcd_virtual_block(blockIdx.x, gridDim.x);
     const int nqb = (p.Tq + 32 * NW - 1) / (32 * NW);
     const int qb = vb % nqb, hb = vb / nqb;
     const int h = hb % p.H, b = hb / p.H;
     const int q0 = qb * (32 * NW) + wave * 32;
-    const int D = p.D > 0 ? p.D : 64;
+    const int D = head_dim(p);
     const int vt_heads = p.vt_batch_heads > 0 ? p.vt_batch_heads : p.H;
 
     const __bf16* Q = (const __bf16*)p.q;
@@ -61,14 +51,7 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
     qrow = qvalid ? qrow : p.Tq - 1;
     bf16x8 qf[DT * 4];
 #pragma unroll
-    for (int ks = 0; ks < DT * 4; ++ks) {
-        const int col = ks * 16 + lhi * 8;
-        if (col < D) qf[ks] = *(const bf16x8*)(Q + ((long)b * p.Tq + qrow) * p.ldq + h * D + col);
-        else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = (__bf16)0.f;
-        }
-    }
+    for (int ks = 0; ks < DT * 4; ++ks) qf[ks] = load_row_chunk(Q + ((long)b * p.Tq + qrow) * p.ldq + h * D, ks * 16 + lhi * 8, D);
 
     const int nt = (p.Tk + 63) / 64;
     // Whole key tiles only (!TAIL): the per-lane source addresses of this wave's staging rows are computed once and advanced
@@ -81,14 +64,12 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
     if constexpr (!TAIL) {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            const int row = wave * 8 + frow;
-            const int ks = fslot ^ ((row >> 1) & 7);       // the same for rows row + 8 * NW * i
-            const int col = dt * 64 + ks * 8;
-            const bool live = col < D;
-            kp[dt] = live ? K + ((long)b * p.Tk + row) * p.ldk + h * D + col : (const __bf16*)slh_zero_page;
+            const StageRow r(wave, lane);                  // the slot is the same for rows row + 8 * NW * i
+            const bool live = r.col(dt) < D;
+            kp[dt] = live ? K + ((long)b * p.Tk + r.row) * p.ldk + h * D + r.col(dt) : (const __bf16*)slh_zero_page;
             kstep[dt] = live ? 64L * p.ldk : 0L;
             khalf[dt] = live ? (long)(8 * NW) * p.ldk : 0L;
-            vp[dt] = VT + (((long)b * vt_heads + h) * (64 * DT) + dt * 64 + row) * p.ldvt + ks * 8;
+            vp[dt] = VT + (((long)b * vt_heads + h) * (64 * DT) + dt * 64 + r.row) * p.ldvt + r.ks * 8;
         }
     }
     const unsigned sK_addr = lds_addr_of(smem), sV_addr = sK_addr + 2 * DT * 8192;
@@ -97,7 +78,7 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
         for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
             for (int i = 0; i < 8 / NW; ++i) {
-                const unsigned off = (buf * DT + dt) * 8192 + (wave + NW * i) * 1024;
+                const unsigned off = stage_off(buf * DT + dt, wave + NW * i);
                 glds16_hidden(kp[dt] + i * khalf[dt], sK_addr + off);
                 glds16_hidden(vp[dt] + (long)i * (8 * NW) * p.ldvt, sV_addr + off);
             }
@@ -111,15 +92,11 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
         for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
             for (int i = 0; i < 8 / NW; ++i) {
-                const int row = (wave + NW * i) * 8 + frow;
-                const int ks = fslot ^ ((row >> 1) & 7);
-                int kv = t * 64 + row;
-                kv = kv < p.Tk ? kv : p.Tk - 1;
-                const int col = dt * 64 + ks * 8;
-                const __bf16* ksrc = col < D ? K + ((long)b * p.Tk + kv) * p.ldk + h * D + col
-                                             : (const __bf16*)slh_zero_page;
+                const StageRow r(wave + NW * i, lane);
+                const __bf16* ksrc = r.col(dt) < D ? K + ((long)b * p.Tk + r.token(t, p.Tk)) * p.ldk + h * D + r.col(dt)
+                                                   : (const __bf16*)slh_zero_page;
                 glds16(ksrc, sK + (buf * DT + dt) * 8192 + (wave + NW * i) * 1024);
-                glds16(VT + (((long)b * vt_heads + h) * (64 * DT) + dt * 64 + row) * p.ldvt + t * 64 + ks * 8,
+                glds16(VT + (((long)b * vt_heads + h) * (64 * DT) + dt * 64 + r.row) * p.ldvt + t * 64 + r.ks * 8,
                        sV + (buf * DT + dt) * 8192 + (wave + NW * i) * 1024);
             }
         }
@@ -133,8 +110,7 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
     float m_run = -1e30f, l_run = 0.f;
     const f32x16 kZero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float c = p.scale * 1.4426950408889634f;
-    // permuted key row for the A operand of S^T (swap bits 2 and 3)
-    const int prow = (lrow & 3) | (((lrow >> 3) & 1) << 2) | (((lrow >> 2) & 1) << 3) | (lrow & 16);
+    const int prow = perm_row(lrow);
 
     stage(0, 0);
     if constexpr (!TAIL) {
@@ -172,39 +148,9 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
                     if (kv >= p.Tk) s[kt][r] = -1e30f;
                 }
         }
-        float mx = s[0][0];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        // raw v_exp_f32 (arguments <= 0; results below 2^-126 flush to 0, which is what a probability that small is
-        // worth) - the libm exp2f wraps every call in a denormal-range fixup that quadruples the VALU work here
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-        const float mc = m_new * c;
-        m_run = m_new;
         bf16x8 pb[2][2];
-        // scalar fp32 softmax arithmetic (this file is built with -fno-slp-vectorize): v_pk_fma/add/mul_f32 beside MFMAs cost more
-        // than the two plain instructions they replace (same-box A/B, T = 4096: 149.9 -> 141.0 us)
-        float ps = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r], c, -mc));
-                ps += pv;
-                pb[kt][r >> 3][r & 7] = (__bf16)pv;
-            }
-        l_run = l_run * alpha + ps;
-        // the running maximum settles after the first tiles: rescale the accumulators only when some row of the
-        // wave actually moved (alpha == 1 exactly otherwise, so skipping is bit-identical)
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.f) != 0) {
-#pragma unroll
-            for (int dd = 0; dd < 2 * DT; ++dd)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dd][r] *= alpha;
-        }
+        const float alpha = softmax_tile(s, c, m_run, l_run, pb);
+        rescale_if_moved(o, alpha);
 #pragma unroll
         for (int dd = 0; dd < 2 * DT; ++dd)
 #pragma unroll
@@ -216,19 +162,7 @@ __global__ __launch_bounds__(64 * NW, DT == 1 ? (NW == 4 ? ATTN_OCC41 : 3) : ((D
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.f / l_tot;
     if (qvalid) {
-        __bf16* O = (__bf16*)p.o + ((long)b * p.Tq + qrow) * p.ldo + h * D;
-#pragma unroll
-        for (int dd = 0; dd < 2 * DT; ++dd)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int dcol = dd * 32 + qd * 8 + lhi * 4;
-                if (dcol < D) {
-                    bf16x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (__bf16)(o[dd][qd * 4 + e] * inv);
-                    *(bf16x4*)(O + dcol) = v;
-                }
-            }
+        store_acc_row<DT>((__bf16*)p.o + ((long)b * p.Tq + qrow) * p.ldo + h * D, lhi, D, [&](int dd, int r) { return o[dd][r] * inv; });
         if (p.lse && lhi == 0) p.lse[((long)b * p.H + h) * p.Tq + qrow] = m_run * c + log2f(l_tot);
     }
 }
@@ -247,7 +181,6 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_ks_kernel(const slh_attn_desc
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = wave & 1, kh = wave >> 1;
     const int lrow = lane & 31, lhi = lane >> 5;
-    const int frow = lane >> 3, fslot = lane & 7;
     int vb = blockIdx.x;
     const int nqb = p.Tq >> 6;
     {
@@ -257,9 +190,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_ks_kernel(const slh_attn_desc
             weight_touch<8>(p.pf_ptr, p.pf_bytes, vb - nblk, (int)gridDim.x - nblk);
             return;
         }
-        const int qd = nblk >> 3, rm = nblk & 7;
-        const int xcd = vb & 7, idx = vb >> 3;
-        vb = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        vb = xcd_virtual_block(vb, nblk);
     }
     const int qb = vb % nqb, hb = vb / nqb;
     const int h = hb % p.H, b = hb / p.H;
@@ -279,11 +210,10 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_ks_kernel(const slh_attn_desc
     const __bf16* vp;
     long khalf;
     {
-        const int row = qi * 8 + frow;
-        const int ks = fslot ^ ((row >> 1) & 7);          // the same for rows row + 16 i
-        kp = K + ((long)b * p.Tk + (long)kh * nth * 64 + row) * p.ldk + h * 64 + ks * 8;
+        const StageRow r(qi, lane);                       // the slot is the same for rows row + 16 i
+        kp = K + ((long)b * p.Tk + (long)kh * nth * 64 + r.row) * p.ldk + h * 64 + r.ks * 8;
         khalf = 16L * p.ldk;
-        vp = VT + (((long)b * vt_heads + h) * 64 + row) * p.ldvt + (long)kh * nth * 64 + ks * 8;
+        vp = VT + (((long)b * vt_heads + h) * 64 + r.row) * p.ldvt + (long)kh * nth * 64 + r.ks * 8;
     }
     const unsigned base = lds_addr_of(smem) + kh * 24576;
     long kstep = 64L * p.ldk;
@@ -306,7 +236,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_ks_kernel(const slh_attn_desc
     float m_run = -1e30f, l_run = 0.f;
     const f32x16 kZero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float c = p.scale * 1.4426950408889634f;
-    const int prow = (lrow & 3) | (((lrow >> 3) & 1) << 2) | (((lrow >> 2) & 1) << 3) | (lrow & 16);
+    const int prow = perm_row(lrow);
     const char* sKh = smem + kh * 24576;
     const char* cV = sKh + 16384;
 
@@ -330,33 +260,9 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_ks_kernel(const slh_attn_desc
                 if (ks == 0) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[0], kZero16, 0, 0, 0);
                 else sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sc[kt], 0, 0, 0);
             }
-        float mx = sc[0][0];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[kt][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-        const float mc = m_new * c;
-        m_run = m_new;
         bf16x8 pb[2][2];
-        float ps = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][r], c, -mc));
-                ps += pv;
-                pb[kt][r >> 3][r & 7] = (__bf16)pv;
-            }
-        l_run = l_run * alpha + ps;
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.f) != 0) {
-#pragma unroll
-            for (int dd = 0; dd < 2; ++dd)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dd][r] *= alpha;
-        }
+        const float alpha = softmax_tile(sc, c, m_run, l_run, pb);
+        rescale_if_moved(o, alpha);
         // V^T(t): this wave's pieces have landed (the four K(t+1) pieces issued behind them may still fly), then everybody's
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -443,7 +349,7 @@ __global__ __launch_bounds__(256) void transpose_heads_batch_kernel(const slh_tr
     const int bid = blockIdx.x;
     const int lo = __builtin_amdgcn_readfirstlane(batch_find(prefix, n, bid));
     const slh_transpose_desc d = table[lo];
-    const int D = d.D > 0 ? d.D : 64;
+    const int D = d.D > 0 ? d.D : 64;      // (in place: through head_dim() hipcc emits other code for this kernel)
     const int DT = (D + 63) / 64;
     const int local = bid - prefix[lo];
     const int gx = d.ldt / 64, gy = d.H * DT;
@@ -451,44 +357,47 @@ __global__ __launch_bounds__(256) void transpose_heads_batch_kernel(const slh_tr
     transpose_heads_body(d, D, DT, bx, rest % gy, rest / gy);
 }
 
-// the key-split form can run the launch (D = 64, whole key tiles in two equal halves) / is the form launch_fwd picks for it
-static bool attn_ks_ok(const slh_attn_desc* d, int DT) {
-    return DT == 1 && (d->Tk & 63) == 0 && (d->D == 0 || d->D == 64) && d->Tq % 64 == 0 && d->Tk % 128 == 0 && d->Tk >= 256;
-}
-static bool attn_ks_form(const slh_attn_desc* d, int DT) {
-    static const int knob_ks = getenv("SLH_ATTN_KS") ? atoi(getenv("SLH_ATTN_KS")) : 1;        // A/B: 0 = never
-    const long blocks4 = (long)((d->Tq + 127) / 128) * d->H * d->B, blocks2 = (long)(d->Tq / 64) * d->H * d->B;
-    return knob_ks && attn_ks_ok(d, DT) && blocks4 < 512 && blocks2 > 128 && blocks2 <= 768;
+// The A/B knobs of the forward dispatch, read once per process
+struct attn_knobs {
+    int ks;         // SLH_ATTN_KS: 0 = never the key-split form, 1 = by the rule below (default), 2 = whenever the shape allows
+    int nw2;        // SLH_ATTN_NW2: 64-query workgroups everywhere
+};
+static const attn_knobs& attn_knob() {
+    static const attn_knobs k = {getenv("SLH_ATTN_KS") ? atoi(getenv("SLH_ATTN_KS")) : 1, getenv("SLH_ATTN_NW2") ? atoi(getenv("SLH_ATTN_NW2")) : 0};
+    return k;
 }
 
 // The one place that decides which forward kernel runs a descriptor: launch_fwd launches what this returns, slh_attn_fwd_kernel_name
-// names it through the same launch statements (common.h: slh_launch), slh_attn_fwd_carries_touch reads .ks of the default knobs.
+// names it through the same launch statements (common.h: slh_launch), slh_attn_fwd_carries_touch reads .ks_rule.
 struct attn_fwd_form {
+    bool ks_rule;   // the key-split form by the default rule (what callers plan weight touches by: knob value 2 does not move it)
     bool ks;        // attn_fwd_ks_kernel (D = 64, whole key tiles in two equal halves), else attn_fwd_kernel<nw, DT, tail>
     int nw;         // 4: 128-query workgroups, 2: 64-query workgroups
     bool tail;      // Tk is not a multiple of 64
     long blocks;    // workgroups of the launch's own (the key-split form adds the weight-touch workgroups behind them)
 };
-static attn_fwd_form attn_fwd_choose(const slh_attn_desc* d, int DT) {
-    static const int knob_nw2 = getenv("SLH_ATTN_NW2") ? atoi(getenv("SLH_ATTN_NW2")) : 0;     // A/B: 64-query workgroups everywhere
-    static const int knob_ks = getenv("SLH_ATTN_KS") ? atoi(getenv("SLH_ATTN_KS")) : 1;        // A/B: 0 = never, 2 = whenever the shape allows
-    const long blocks4 = (long)((d->Tq + 127) / 128) * d->H * d->B;
+static attn_fwd_form attn_fwd_choose(const slh_attn_desc* d) {
+    const attn_knobs& knob = attn_knob();
+    const long heads = (long)d->H * d->B;
+    const long blocks4 = (d->Tq + 127) / 128 * heads, blocks2 = d->Tq / 64 * heads;
     attn_fwd_form f;
     f.tail = (d->Tk & 63) != 0;
     // key-split form (attn_fwd_ks_kernel above): D = 64, whole key tiles in two equal halves, and a 64-query grid that neither
     // fills every SIMD twice (>= 1024 workgroups) nor is so small that one round of full-length waves is cheaper
-    f.ks = attn_ks_form(d, DT) || (knob_ks == 2 && attn_ks_ok(d, DT));
+    const bool ks_ok = d_tiles(*d) == 1 && (d->Tk & 63) == 0 && (d->D == 0 || d->D == 64) && d->Tq % 64 == 0 && d->Tk % 128 == 0 && d->Tk >= 256;
+    f.ks_rule = knob.ks && ks_ok && blocks4 < 512 && blocks2 > 128 && blocks2 <= 768;
+    f.ks = f.ks_rule || (knob.ks == 2 && ks_ok);
     // 128-query workgroups once they fill every CU twice; below that the 64-query form (same waves per SIMD at most, finer
     // placement: T = 1024 with 40 heads 31.2 -> 28.9 us, same box).  (Capping the workgroups per CU with unused dynamic LDS so
     // that the dispatcher must spread them was tried: the hardware already places them evenly, the cap only delays backfill.)
-    f.nw = (!f.ks && blocks4 >= 512 && !knob_nw2) ? 4 : 2;
-    f.blocks = f.ks ? (long)(d->Tq / 64) * d->H * d->B : f.nw == 4 ? blocks4 : (long)((d->Tq + 63) / 64) * d->H * d->B;
+    f.nw = (!f.ks && blocks4 >= 512 && !knob.nw2) ? 4 : 2;
+    f.blocks = f.ks ? blocks2 : f.nw == 4 ? blocks4 : (d->Tq + 63) / 64 * heads;
     return f;
 }
 
 template <int DT>
 int launch_fwd(const slh_attn_desc* d, hipStream_t s) {
-    const attn_fwd_form f = attn_fwd_choose(d, DT);
+    const attn_fwd_form f = attn_fwd_choose(d);
     const int grid = (int)f.blocks;
     if (f.ks) {
         // weight touch (pf_*): up to 64 workgroups behind the launch's own; with three workgroups per CU they are resident beside them
@@ -512,19 +421,18 @@ int launch_fwd(const slh_attn_desc* d, hipStream_t s) {
 
 extern "C" int slh_attn_fwd_carries_touch(const slh_attn_desc* d) {
     if (!d || d->B <= 0 || d->H <= 0 || d->Tq <= 0 || d->Tk <= 0) return 0;
-    const int D = d->D > 0 ? d->D : 64;
-    return attn_ks_form(d, (D + 63) / 64) ? 1 : 0;
+    return attn_fwd_choose(d).ks_rule ? 1 : 0;
 }
 
 extern "C" int slh_attn_fwd(const slh_attn_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->q && d->k && d->vt && d->o, "slh_attn_fwd: null pointer");
     SLH_CHECK(d->B > 0 && d->H > 0 && d->Tq > 0 && d->Tk > 0, "slh_attn_fwd: bad shape");
-    const int D = d->D > 0 ? d->D : 64;
+    const int D = head_dim(*d);
     SLH_CHECK(D % 8 == 0 && D <= 192, "slh_attn_fwd: head_dim %d unsupported (multiple of 8, <= 192)", D);
     SLH_CHECK(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldvt % 64 == 0 && d->ldo % 4 == 0, "slh_attn_fwd: alignment");
     SLH_CHECK(d->ldvt >= ((d->Tk + 63) / 64) * 64, "slh_attn_fwd: VT must be padded to a multiple of 64 keys");
     SLH_CHECK(!d->pf_ptr || (((uintptr_t)d->pf_ptr & 15) == 0 && d->pf_bytes >= 0), "slh_attn_fwd: pf_ptr must be 16-byte aligned");
-    const int DT = (D + 63) / 64;
+    const int DT = d_tiles(*d);
     hipStream_t s = (hipStream_t)stream;
     if (DT == 1) return launch_fwd<1>(d, s);
     if (DT == 2) return launch_fwd<2>(d, s);
@@ -547,15 +455,14 @@ static int transpose_check(const slh_transpose_desc* d) {
     SLH_CHECK(d && d->src && d->dst, "slh_transpose_heads: null pointer");
     SLH_CHECK(d->ld % 8 == 0 && d->ldt % 64 == 0 && d->ldt >= d->T, "slh_transpose_heads: alignment");
     SLH_CHECK(d->B > 0 && d->H > 0 && d->T > 0, "slh_transpose_heads: empty problem");
-    const int D = d->D > 0 ? d->D : 64;
+    const int D = head_dim(*d);
     SLH_CHECK(D % 8 == 0 && D <= 192, "slh_transpose_heads: head_dim %d unsupported", D);
     return 0;
 }
 
 extern "C" int slh_transpose_heads_blocks(const slh_transpose_desc* d) {
     if (transpose_check(d)) return -1;
-    const int D = d->D > 0 ? d->D : 64;
-    return (d->ldt / 64) * d->H * ((D + 63) / 64) * d->B;
+    return (d->ldt / 64) * d->H * d_tiles(*d) * d->B;
 }
 
 extern "C" int slh_transpose_heads_batch(const slh_batch_desc* d, slh_stream_t stream) {
@@ -568,8 +475,7 @@ extern "C" int slh_transpose_heads_batch(const slh_batch_desc* d, slh_stream_t s
 
 extern "C" int slh_transpose_heads(const slh_transpose_desc* d, slh_stream_t stream) {
     if (transpose_check(d)) return -1;
-    const int D = d->D > 0 ? d->D : 64;
-    const int DT = (D + 63) / 64;
+    const int D = head_dim(*d), DT = d_tiles(*d);
     dim3 grid(d->ldt / 64, d->H * DT, d->B);
     hipLaunchKernelGGL(transpose_heads_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d, D, DT);
     SLH_LAUNCH_CHECK("slh_transpose_heads");

@@ -13,21 +13,11 @@
 // As in the forward the first MFMA of each pair is issued with swapped operands and permuted rows so that the
 // probabilities land in registers in exactly the k-order the second MFMA's B operand needs.
 // Cross-attention (text K/V carry no gradient in the reference) runs the dq kernel only.
-#include "common.h"
-#include "../../include/sliders_hip.h"
+#include "attention_common.h"
+
+using namespace slh_attn_detail;
 
 namespace {
-
-__device__ __forceinline__ int perm_row(int r) {  // swap bits 2 and 3
-    return (r & 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 3) | (r & 16);
-}
-__device__ __forceinline__ bf16x8 load_row_chunk(const __bf16* base, int col, int D) {
-    if (col < D) return *(const bf16x8*)(base + col);
-    bf16x8 z;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z[e] = (__bf16)0.f;
-    return z;
-}
 
 __global__ __launch_bounds__(256) void attn_delta_kernel(const slh_attn_bwd_desc p, int D) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, q, h)
@@ -48,15 +38,6 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const slh_attn_bwd_desc
     p.delta[((long)b * p.H + h) * p.Tq + q] = s;
 }
 
-// XCD-aware block order shared by the backward kernels (see attn_fwd_kernel): virtual block id whose consecutive values
-// (same head, next 128-row block) land on the same XCD's L2
-__device__ __forceinline__ int xcd_virtual_block() {
-    const int vb = blockIdx.x, nblk = gridDim.x;
-    const int qd = nblk >> 3, rm = nblk & 7;
-    const int xcd = vb & 7, idx = vb >> 3;
-    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-}
-
 // ---- dQ ------------------------------------------------------------------------------------------------
 template <int DT>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const slh_attn_bwd_desc p) {
@@ -67,12 +48,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const slh_attn_bwd_des
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & 31, lhi = lane >> 5;
-    const int frow = lane >> 3, fslot = lane & 7;
-    const int vb = xcd_virtual_block();
+    const int vb = xcd_virtual_block(blockIdx.x, gridDim.x);      // consecutive values: same head, next 128-row block
     const int nqb = (p.Tq + 127) / 128;
     const int h = (vb / nqb) % p.H, b = vb / (nqb * p.H);
     const int q0 = (vb % nqb) * 128 + wave * 32;
-    const int D = p.D > 0 ? p.D : 64;
+    const int D = head_dim(p);
     const __bf16* K = (const __bf16*)p.k;
     const __bf16* V = (const __bf16*)p.v;
     const __bf16* KT = (const __bf16*)p.kt;
@@ -97,17 +77,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const slh_attn_bwd_des
         for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int row = (wave + 4 * i) * 8 + frow;
-                const int ks = fslot ^ ((row >> 1) & 7);
-                int kv = t * 64 + row;
-                kv = kv < p.Tk ? kv : p.Tk - 1;
-                const int col = dt * 64 + ks * 8;
+                const StageRow r(wave + 4 * i, lane);
+                const int kv = r.token(t, p.Tk), col = r.col(dt);
                 const bool ok = col < D;
                 glds16(ok ? K + ((long)b * p.Tk + kv) * p.ldk + h * D + col : (const __bf16*)slh_zero_page,
                        sK + (buf * DT + dt) * 8192 + (wave + 4 * i) * 1024);
                 glds16(ok ? V + ((long)b * p.Tk + kv) * p.ldv + h * D + col : (const __bf16*)slh_zero_page,
                        sV + (buf * DT + dt) * 8192 + (wave + 4 * i) * 1024);
-                glds16(KT + (((long)b * p.H + h) * (64 * DT) + dt * 64 + row) * p.ldkt + t * 64 + ks * 8,
+                glds16(KT + (((long)b * p.H + h) * (64 * DT) + dt * 64 + r.row) * p.ldkt + t * 64 + r.ks * 8,
                        sKT + (buf * DT + dt) * 8192 + (wave + 4 * i) * 1024);
             }
         }
@@ -156,21 +133,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const slh_attn_bwd_des
                 acc[dd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, ds[kstep >> 1][kstep & 1], acc[dd], 0, 0, 0);
             }
     }
-    if (qvalid) {
-        __bf16* O = (__bf16*)p.dq + ((long)b * p.Tq + qrow) * p.lddq + h * D;
-#pragma unroll
-        for (int dd = 0; dd < 2 * DT; ++dd)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int dcol = dd * 32 + qd * 8 + lhi * 4;
-                if (dcol < D) {
-                    bf16x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (__bf16)(acc[dd][qd * 4 + e] * p.scale);
-                    *(bf16x4*)(O + dcol) = v;
-                }
-            }
-    }
+    if (qvalid)
+        store_acc_row<DT>((__bf16*)p.dq + ((long)b * p.Tq + qrow) * p.lddq + h * D, lhi, D, [&](int dd, int r) { return acc[dd][r] * p.scale; });
 }
 
 // ---- dK, dV --------------------------------------------------------------------------------------------
@@ -185,12 +149,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & 31, lhi = lane >> 5;
-    const int frow = lane >> 3, fslot = lane & 7;
-    const int vb = xcd_virtual_block();
+    const int vb = xcd_virtual_block(blockIdx.x, gridDim.x);      // consecutive values: same head, next 128-row block
     const int nkb = (p.Tk + 127) / 128;
     const int h = (vb / nkb) % p.H, b = vb / (nkb * p.H);
     const int k0 = (vb % nkb) * 128 + wave * 32;
-    const int D = p.D > 0 ? p.D : 64;
+    const int D = head_dim(p);
     const __bf16* Q = (const __bf16*)p.q;
     const __bf16* G = (const __bf16*)p.d_o;
     const __bf16* QT = (const __bf16*)p.qt;
@@ -213,16 +176,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
         for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int row = (wave + 4 * i) * 8 + frow;
-                const int ks = fslot ^ ((row >> 1) & 7);
-                int q = t * 64 + row;
-                q = q < p.Tq ? q : p.Tq - 1;
-                const int col = dt * 64 + ks * 8;
+                const StageRow r(wave + 4 * i, lane);
+                const int q = r.token(t, p.Tq), col = r.col(dt);
                 const bool ok = col < D;
-                const int o = (buf * DT + dt) * 8192 + (wave + 4 * i) * 1024;
+                const int o = stage_off(buf * DT + dt, wave + 4 * i);
                 glds16(ok ? Q + ((long)b * p.Tq + q) * p.ldq + h * D + col : (const __bf16*)slh_zero_page, sQ + o);
                 glds16(ok ? G + ((long)b * p.Tq + q) * p.lddo + h * D + col : (const __bf16*)slh_zero_page, sG + o);
-                const long trow = (((long)b * p.H + h) * (64 * DT) + dt * 64 + row) * p.ldqt + t * 64 + ks * 8;
+                const long trow = (((long)b * p.H + h) * (64 * DT) + dt * 64 + r.row) * p.ldqt + t * 64 + r.ks * 8;
                 glds16(QT + trow, sQT + o);
                 glds16(GT + trow, sGT + o);
             }
@@ -294,6 +254,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
             }
     }
     if (kvalid) {
+        // (dK is scaled and dV is not, and their stores alternate: stated here, not two passes of store_acc_row)
         __bf16* DK = (__bf16*)p.dk + ((long)b * p.Tk + krow) * p.lddk + h * D;
         __bf16* DV = (__bf16*)p.dv + ((long)b * p.Tk + krow) * p.lddv + h * D;
 #pragma unroll
@@ -319,7 +280,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const slh_attn_bwd_de
 static int attn_bwd_check(const slh_attn_bwd_desc* d) {
     SLH_CHECK(d && d->q && d->k && d->v && d->o && d->d_o && d->lse && d->delta && d->dq && d->kt,
               "slh_attn_bwd: null pointer");
-    const int D = d->D > 0 ? d->D : 64;
+    const int D = head_dim(*d);
     SLH_CHECK(D % 8 == 0 && D <= 192, "slh_attn_bwd: head_dim %d unsupported", D);
     SLH_CHECK(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 8 == 0 && d->lddo % 8 == 0 &&
                   d->lddq % 4 == 0 && d->ldkt % 64 == 0,
@@ -336,14 +297,14 @@ static int attn_bwd_check(const slh_attn_bwd_desc* d) {
 // The one place each that picks the dq / dkv instantiation: slh_attn_bwd launches through them, slh_attn_bwd_kernel_names names
 // through them (common.h: slh_launch records the template instead of launching it while a name sink is set).
 static void launch_bwd_dq(const slh_attn_bwd_desc* d, hipStream_t s) {
-    const int D = d->D > 0 ? d->D : 64, DT = (D + 63) / 64;
+    const int DT = d_tiles(*d);
     const int gq = (int)((long)((d->Tq + 127) / 128) * d->H * d->B);
     if (DT == 1) slh_launch<attn_bwd_dq_kernel<1>>(gq, 256, s, *d, "attn_bwd_dq_kernel<1>");
     else if (DT == 2) slh_launch<attn_bwd_dq_kernel<2>>(gq, 256, s, *d, "attn_bwd_dq_kernel<2>");
     else slh_launch<attn_bwd_dq_kernel<3>>(gq, 256, s, *d, "attn_bwd_dq_kernel<3>");
 }
 static void launch_bwd_dkv(const slh_attn_bwd_desc* d, hipStream_t s) {
-    const int D = d->D > 0 ? d->D : 64, DT = (D + 63) / 64;
+    const int DT = d_tiles(*d);
     const int gk = (int)((long)((d->Tk + 127) / 128) * d->H * d->B);
     if (DT == 1) slh_launch<attn_bwd_dkv_kernel<1, 2>>(gk, 256, s, *d, "attn_bwd_dkv_kernel<1, 2>");
     else if (DT == 2) slh_launch<attn_bwd_dkv_kernel<2, 2>>(gk, 256, s, *d, "attn_bwd_dkv_kernel<2, 2>");
@@ -354,10 +315,9 @@ static void launch_bwd_dkv(const slh_attn_bwd_desc* d, hipStream_t s) {
 
 extern "C" int slh_attn_bwd(const slh_attn_bwd_desc* d, slh_stream_t stream) {
     if (attn_bwd_check(d)) return -1;
-    const int D = d->D > 0 ? d->D : 64;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)d->B * d->Tq * d->H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *d, D);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *d, head_dim(*d));
     launch_bwd_dq(d, s);
     if (d->need_dkv) launch_bwd_dkv(d, s);
     SLH_LAUNCH_CHECK("slh_attn_bwd");

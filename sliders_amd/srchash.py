@@ -32,14 +32,19 @@ def file_hashes() -> dict:
     return out
 
 
+# kernel name prefix -> its translation unit (for gemm5 / gemm7 also gemm.hip, which dispatches to them) and the project headers
+# those include, directly or through another header; kernel_files adds common.h, the public header and the tile tables
+_GEMM_H = ["gemm_common.h", "addressing.h"]
+KERNEL_UNITS = {"gemm_kernel": ["gemm.hip", "gemm_dispatch.h"] + _GEMM_H, "gemm8p": ["gemm8p.hip"] + _GEMM_H,
+                "gemm5": ["gemm5.hip", "gemm.hip", "gemm_dispatch.h"] + _GEMM_H, "gemm7": ["gemm7.hip", "gemm.hip", "gemm_dispatch.h"] + _GEMM_H,
+                "attn_fwd": ["attention.hip", "attention_common.h"], "attn_bwd": ["attention_bwd.hip", "attention_common.h"]}
+
+
 def kernel_files(kernel_name: str, all_files) -> list:
     """The files a kernel's code and its launches depend on: its translation unit, the headers it includes, the public header
     (descriptor layout) and every tuned tile table (they decide which launches run the kernel)."""
-    unit = {"gemm_kernel": ["gemm.hip", "gemm_common.h"], "gemm8p": ["gemm8p.hip", "gemm_common.h"],
-            "gemm5": ["gemm5.hip", "gemm.hip", "gemm_common.h"], "gemm7": ["gemm7.hip", "gemm.hip", "gemm_common.h"],
-            "attn_fwd": ["attention.hip"], "attn_bwd": ["attention_bwd.hip"]}
     picked = None
-    for prefix, files in unit.items():
+    for prefix, files in KERNEL_UNITS.items():
         if kernel_name.startswith(prefix):
             picked = list(files)
     if picked is None:

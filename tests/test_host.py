@@ -882,6 +882,39 @@ def test_bench_pairs_counter_traffic_only_with_identical_kernel_sources(tmp_path
     assert t is None and "re-run" in src
 
 
+def test_kernel_files_lists_what_each_unit_includes():
+    """srchash.kernel_files: for every kernel prefix the listed sources are exactly the translation units (the .hip files of the entry)
+    plus the project headers they #include, directly or through another header, read from the source text - a header a unit gains
+    or loses has to show up in the map, or bench.py would pair counter traffic with a kernel whose code has changed."""
+    from sliders_amd import srchash
+    csrc = os.path.join(ROOT, "sliders_amd", "csrc")
+
+    def closure(name, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), re.M):
+            inc = os.path.basename(inc)            # "../../include/sliders_hip.h" -> sliders_hip.h
+            if inc not in seen:
+                seen.add(inc)
+                if os.path.exists(os.path.join(csrc, inc)):
+                    closure(inc, seen)
+        return seen
+
+    here = srchash.file_hashes()
+    tables = {f for f in here if f.endswith(".json")}
+    assert tables and len(srchash.KERNEL_UNITS) >= 6
+    for prefix, listed in srchash.KERNEL_UNITS.items():
+        units = [f for f in listed if f.endswith(".hip")]
+        assert units and units[0].startswith(("gemm", "attention")), prefix
+        want = set(units)
+        for u in units:
+            want |= closure(u, set())
+        assert {"common.h", "sliders_hip.h"} <= want, prefix
+        got = set(srchash.kernel_files(prefix + "<1>", here))
+        assert got - tables == want, (prefix, sorted(got - tables), sorted(want))
+        assert got & tables == tables and got <= set(here), prefix
+    assert "attention_common.h" in srchash.kernel_files("attn_fwd_ks_kernel", here)
+    assert {"addressing.h", "gemm_dispatch.h"} <= set(srchash.kernel_files("gemm5_kernel<false, 4>", here))
+
+
 
 def test_dry_run_plans_the_program_the_real_plan_runs(monkeypatch):
     """UNetEngine sizes its arena by planning against _VirtualWeights (pointer-less).  The dry run must take the same branches as
