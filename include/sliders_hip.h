@@ -511,6 +511,37 @@ int slh_sigma_step(const void* const* ptrs, const int32_t* dims, const float* co
  * overlapping an output. */
 int slh_latent_blend(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
 
+/* Prompt-direction sampling (csrc/eps_direction.hip, docs/SAMPLING.md, "Prompt-direction sampling"): one UNet pass has produced, next
+ * to the text row t, the rows e+_k, e-_k of K <= 3 prompt pairs on the same latent.  With d_k = e+_k - e-_k (one fp32 subtraction of
+ * the widened bf16 values) and key(d) = the upper 16 bits of the fp32 bit pattern of |d|, an integer:
+ *
+ * slh_direction_threshold: thr[b][k][ch] = tau, the n_keep[k]-th largest key(d_k) among the hw pixels of channel ch of sample b, counted
+ * with multiplicity.  One workgroup per (b, k, ch), a radix select in two 8-bit passes with integer LDS counters: exact, the same in
+ * every run.  Any hw >= 1.
+ * ptrs[7]: 0..2 pos[k], 3..5 neg[k]   bf16 [nb][chw], the first K of each are read
+ *          6 thr                       int32 [nb][K][chw / hw], written
+ * dims[7]: 0 nb, 1 chw, 2 hw (chw % hw == 0), 3 K (1..3), 4..6 n_keep[k] (1..hw)
+ * coef:    not read (may be NULL)
+ *
+ * slh_eps_direction: the guided text row, per element in fp32, one rounding per operation, nothing contracted:
+ *   acc = t;   for k ascending with c[k] != 0:  d = e+_k - e-_k;  if thr is given and key(d) < thr[b][k][ch] the term is skipped;
+ *   otherwise p = c[k] * d, acc = acc + p;   out = round-to-nearest-even bf16 of acc.
+ * A term with c[k] == 0 is skipped, not multiplied: its rows are not read and may hold NaN.  With every c[k] == 0 out has t's bits.
+ * Every element with key(d) == tau is kept, so at least n_keep elements of a group are; without thr every element is, which is what
+ * n_keep = hw gives bit for bit.
+ * ptrs[9]: 0 t      bf16 [nb][chw]
+ *          1 out    bf16 [nb][chw]; must not overlap any input
+ *          2..4 pos[k], 5..7 neg[k]   bf16 [nb][chw], the first K of each
+ *          8 thr    optional int32 [nb][K][chw / hw], as slh_direction_threshold writes it
+ * dims[4]: 0 nb, 1 chw, 2 hw (chw % hw == 0), 3 K (1..3)
+ * coef[3]: c[k]
+ * 16-byte accesses where every pointer, chw and hw allow them (multiples of 8 elements), one element per thread otherwise.
+ * Both are never recorded in a program: no opcode, no descriptor struct; three host arrays, as slh_sigma_step.  Refused before the
+ * launch (slh_last_error): a null required pointer; a bf16 pointer that is not 2-byte or an int32 pointer that is not 4-byte aligned;
+ * nb < 1, chw < 1, hw < 1, chw % hw != 0; K outside 1..3; n_keep[k] outside 1..hw; a non-finite c[k]; an output overlapping an input. */
+int slh_direction_threshold(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+int slh_eps_direction(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+
 /* The edit step of a localised edit: e = mu + resid exactly as slh_ddpm_edit_step mode 1 forms it (one piece of code), then, with
  * k = keep[i] and m = mask[b*hw + i % hw] (one mask value per latent pixel, shared by the channels),
  *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          fp32, one rounding per operation, no contraction.

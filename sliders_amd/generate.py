@@ -7,6 +7,9 @@ trainscripts/textsliders/generate_images_xl.py:405-512), on the MI355X engine:
 Like the reference's consumers it reads rank / alpha / train_method from the checkpoint's FILE NAME
 (XL-sliders-inference.ipynb cell 6: 'rank4', 'alpha1', 'noxattn' / 'full' substrings), builds the network, strict-loads
 the .pt, and for every scale runs the 50-step DDIM loop with the slider switched on below `start_noise`.
+
+Without a slider, `--direction "POSITIVE|NEGATIVE[:ETA]"` / `--direction_file prompts.yaml` steer with the prompt pair a slider would be
+trained on, `--scales` sweeping its strength (sliders_amd/directions.py; docs/SAMPLING.md, "Prompt-direction sampling").
 """
 from __future__ import annotations
 
@@ -52,6 +55,7 @@ def build_parser(defaults: bool = True) -> argparse.ArgumentParser:
                    help="one more slider (.pt, any rank) held at a fixed scale in every image; repeatable.  With --compose, or when "
                         "--lora_weight is not rank 4, the sliders are merged into the weights (sliders_amd/merge.py)")
     add("--prompt", default="image of a person")
+    add("--negative_prompt", default=None, help="the unconditional row of the CFG pair is this prompt's encoding instead of the empty prompt's")
     add("--scales", default="-2,-1,0,1,2")
     add("--start_noise", type=int, default=750)
     add("--ddim_steps", type=int, default=50, help="sampling steps (default 50; 4 with --turbo)")
@@ -102,7 +106,79 @@ def build_parser(defaults: bool = True) -> argparse.ArgumentParser:
     add("--mask_word_draws", type=int, default=None, help="steps of the grid the word map averages over (default 8)")
     add("--save_attention", default=None, help="write the word map / its maximum here (8-bit PNG at latent resolution)")
     add("--save_mask", default=None, help="write the latent-resolution mask here (8-bit PNG)")
+    # prompt-direction sampling (docs/SAMPLING.md): a slider's training target as guidance, --scales sweeps its strength
+    add("--direction", action="append", default=[], metavar="POSITIVE|NEGATIVE[:ETA]",
+        help="steer with eps(POSITIVE) - eps(NEGATIVE), times ETA (default 1) times the scale; repeatable, at most 3")
+    add("--direction_file", default=None, help="the same from a prompts.yaml of the trainers: positive, unconditional, guidance_scale (ETA) "
+                                               "and action (erase: the opposite sign) of its entries")
+    add("--direction_entries", default=None, metavar="I,J,...", help="entries of --direction_file to take (default: all, at most 3)")
+    add("--direction_quantile", type=float, default=None, metavar="Q",
+        help="keep only the largest 1 - Q of each latent channel's differences (default 0: all of them)")
     return p
+
+
+def direction_specs(a) -> list:
+    """[(positive, negative, eta, sign)] of --direction / --direction_file; every error of these options is raised here"""
+    import math
+    from .directions import MAX_DIRECTIONS
+    if a.direction and a.direction_file:
+        raise SystemExit("--direction and --direction_file: give one of them")
+    if a.direction_entries is not None and not a.direction_file:
+        raise SystemExit("--direction_entries needs --direction_file")
+    specs = []
+    for spec in a.direction:
+        pos, sep, neg = spec.partition("|")
+        eta = 1.0
+        if ":" in neg:
+            neg, _, tail = neg.rpartition(":")
+            try:
+                eta = float(tail)
+            except ValueError:
+                sep = ""
+        if not sep or not pos.strip():
+            raise SystemExit(f"--direction {spec!r}: expected POSITIVE|NEGATIVE[:ETA]")
+        if not math.isfinite(eta):
+            raise SystemExit(f"--direction {spec!r}: expected a finite ETA")
+        specs.append((pos, neg, eta, 1.0))
+    if a.direction_file:
+        if not os.path.isfile(a.direction_file):
+            raise SystemExit(f"--direction_file {a.direction_file}: no such file")
+        from .prompt_util import load_prompts_from_yaml
+        entries = load_prompts_from_yaml(a.direction_file)
+        picked = list(range(len(entries)))
+        if a.direction_entries is not None:
+            try:
+                picked = [int(v) for v in a.direction_entries.split(",")]
+            except ValueError:
+                raise SystemExit(f"--direction_entries {a.direction_entries!r}: expected comma-separated entry numbers")
+            if not picked or any(not 0 <= i < len(entries) for i in picked):
+                raise SystemExit(f"--direction_entries {a.direction_entries!r}: {a.direction_file} has the entries 0 .. {len(entries) - 1}")
+        specs = [(entries[i].positive, entries[i].unconditional, float(entries[i].guidance_scale), 1.0 if entries[i].action == "enhance" else -1.0)
+                 for i in picked]
+    if len(specs) > MAX_DIRECTIONS:
+        raise SystemExit(f"{len(specs)} directions: at most {MAX_DIRECTIONS} (one UNet pass carries at most 8 row blocks); choose with "
+                         "--direction_entries")
+    return specs
+
+
+def check_direction_args(a) -> list:
+    from .directions import DirectionSet
+    specs = direction_specs(a)
+    if not specs:
+        if a.direction_quantile is not None:
+            raise SystemExit("--direction_quantile needs --direction or --direction_file")
+        return specs
+    try:
+        DirectionSet.n_keep(1, a.direction_quantile or 0.0)
+    except ValueError as e:
+        raise SystemExit(f"--direction_quantile: {e}")
+    if a.lora_weight:
+        raise SystemExit("--direction / --direction_file: --scales sweeps the direction's strength, not with --lora_weight (sliders held at a "
+                         "fixed scale go next to it with --compose)")
+    if not a.no_cfg and a.guidance_scale == 0:
+        raise SystemExit("--direction with --guidance_scale 0: the direction enters through the text row of the CFG pair, which a guidance "
+                         "of 0 does not read (or sample with --no_cfg)")
+    return specs
 
 
 def sampling_grid(a) -> list:
@@ -130,6 +206,10 @@ def check_args(a):
     """the scales, and every argument error of the mask options, before any model is built"""
     from .edit import check_mask_args
     scales = [float(v) for v in a.scales.split(",")]
+    check_direction_args(a)
+    if a.negative_prompt is not None and (a.no_cfg or a.synthetic):
+        raise SystemExit("--negative_prompt is the unconditional row's prompt: not with --no_cfg (there is no such row) and not with "
+                         "--synthetic (its rows are random draws)")
     check_mask_args(a, scales, lambda: sampling_grid(a))
     if masked(a):
         if a.scheduler not in ("ddim", "dpmpp_2m") and not a.fp32_latents:
@@ -147,16 +227,17 @@ def shares_prefix(a, scales) -> bool:
     return 0.0 in scales and len(scales) > 1 and (a.scheduler == "ddim" or (a.scheduler == "euler" and a.fp32_latents))
 
 
-def traced_sweep(a, smp, scales, ctx, pooled, noise, prompt, tokenizer, suffix=""):
+def traced_sweep(a, smp, scales, ctx, pooled, noise, prompt, tokenizer, suffix="", **steer):
     """One seed over its scale-0 trace: with mask options the mask is derived from the trace once and every scale is blended against
-    it; scale 0 is the trace's own image.  Yields (scale, uint8 image [H][W][3] on the host)."""
+    it; scale 0 is the trace's own image.  steer: directions= / direction_quantile= of the other scales.  Yields (scale, uint8 image
+    [H][W][3] on the host)."""
     from .edit import mask_from_args
     from .vae import VaeDecoder
     trace = smp.base_trace(ctx, noise, a.ddim_steps, a.guidance_scale, pooled, None, a.start_noise)
     mask = mask_from_args(a, smp, trace, a.res, prompt, tokenizer, suffix) if masked(a) else None
     for s in scales:
         lat = trace.final if s == 0.0 else smp.sample_latents(ctx, noise, scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,
-                                                              guidance_scale=a.guidance_scale, pooled=pooled, mask=mask, trace=trace)
+                                                              guidance_scale=a.guidance_scale, pooled=pooled, mask=mask, trace=trace, **steer)
         yield s, VaeDecoder.to_uint8(smp.decoder.decode(lat))[0].cpu().numpy()
 
 
@@ -214,7 +295,8 @@ def main(argv=None):
     dev = torch.device("cuda", a.device)
     xl = a.model == "sdxl"
     res = a.res
-    prompts = (lambda text: [text]) if a.no_cfg else (lambda text: ["", text])      # --no_cfg: the text prompt alone is encoded
+    prompts = (lambda text: [text]) if a.no_cfg else (lambda text: [a.negative_prompt or "", text])      # --no_cfg: the text prompt alone is encoded
+    specs = direction_specs(a)
     if a.synthetic:
         eng = synthetic_engine(a.model, dev, a.seed)
         dec = VaeDecoder(random_vae_state_dict(device=dev, seed=a.seed, decoder=True), dev, VAE_SCALING[a.model])
@@ -223,6 +305,10 @@ def main(argv=None):
         pooled = torch.randn(2, eng.cfg.pooled_dim, generator=g) if xl else None
         if a.no_cfg:         # the text row of the same draw
             ctx, pooled = ctx[1:], pooled[1:] if xl else None
+        gd = torch.Generator().manual_seed(a.seed + 1)          # the direction rows: draws of their own, the prompt rows' are unchanged
+
+        def encode(text):
+            return (torch.randn(1, 77, eng.cfg.cross_attention_dim, generator=gd), torch.randn(1, eng.cfg.pooled_dim, generator=gd) if xl else None)
     else:
         if not a.model_path:
             raise SystemExit("--model_path (diffusers-format directory) or --synthetic is required")
@@ -235,10 +321,18 @@ def main(argv=None):
             tokenizer = toks[0]
             enc_xl = [model_util.encode_prompts_xl(toks, encs, [s]) for s in prompts(a.prompt)]
             ctx, pooled = torch.cat([e for e, _ in enc_xl]), torch.cat([q for _, q in enc_xl])
+            encode = lambda text: model_util.encode_prompts_xl(toks, encs, [text])
         else:
             tok, enc = model_util.load_text_encoder(a.model_path, dev, torch.bfloat16)
             tokenizer = tok
             ctx, pooled = torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in prompts(a.prompt)]), None
+            encode = lambda text: (model_util.encode_prompts(tok, enc, [text]), None)
+    steer = {}
+    if specs:
+        from .directions import Direction, DirectionSet
+        pairs = [(encode(pos), encode(neg), eta, sign) for pos, neg, eta, sign in specs]
+        steer = dict(directions=DirectionSet([Direction(cp, cn, pp, pn, eta=eta, sign=sign) for (cp, pp), (cn, pn), eta, sign in pairs]),
+                     direction_quantile=a.direction_quantile or 0.0)
     store = sliders = None
     swept = torch.load(a.lora_weight, map_location="cpu") if a.lora_weight else None
     if a.compose or (swept is not None and slider_rank(swept) != 4):
@@ -281,27 +375,28 @@ def main(argv=None):
                     g = torch.Generator().manual_seed(int(row.evaluation_seed) + num)
                     noise = torch.randn(1, 4, res // 8, res // 8, generator=g)
                     for s, img in traced_sweep(a, smp, scales, c_row.to(dev), p_row.to(dev) if p_row is not None else None, noise.to(dev),
-                                               str(row.prompt), tokenizer, f"_{case}_{num}"):
+                                               str(row.prompt), tokenizer, f"_{case}_{num}", **steer):
                         Image.fromarray(img).save(os.path.join(root, scale_folder(s), f"{case}_{num}.png"))
                     continue
                 for s in scales:
                     g = torch.Generator().manual_seed(int(row.evaluation_seed) + num)          # the same noise for every scale
                     noise = torch.randn(1, 4, res // 8, res // 8, generator=g)
                     img = smp.generate(c_row.to(dev), noise.to(dev), scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,
-                                       guidance_scale=a.guidance_scale, pooled=p_row.to(dev) if p_row is not None else None)
+                                       guidance_scale=a.guidance_scale, pooled=p_row.to(dev) if p_row is not None else None, **steer)
                     Image.fromarray(img[0].cpu().numpy()).save(os.path.join(root, scale_folder(s), f"{case}_{num}.png"))
             print(f"case {case}: {a.num_samples} sample(s) x {len(scales)} scales saved under {root}")
         return root
     if traced:
         noise = torch.randn(1, 4, res // 8, res // 8, generator=torch.Generator().manual_seed(a.seed))
-        for s, img in traced_sweep(a, smp, scales, ctx.to(dev), pooled.to(dev) if pooled is not None else None, noise.to(dev), a.prompt, tokenizer):
+        for s, img in traced_sweep(a, smp, scales, ctx.to(dev), pooled.to(dev) if pooled is not None else None, noise.to(dev), a.prompt, tokenizer,
+                                   **steer):
             Image.fromarray(img).save(os.path.join(a.out, f"scale_{s:g}.png"))
             print(f"scale {s:g}: saved {os.path.join(a.out, f'scale_{s:g}.png')}")
         return a.out
     for s in scales:
         noise = torch.randn(1, 4, res // 8, res // 8, generator=torch.Generator().manual_seed(a.seed))   # same seed per scale
         img = smp.generate(ctx.to(dev), noise.to(dev), scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,
-                           guidance_scale=a.guidance_scale, pooled=pooled.to(dev) if pooled is not None else None)
+                           guidance_scale=a.guidance_scale, pooled=pooled.to(dev) if pooled is not None else None, **steer)
         Image.fromarray(img[0].cpu().numpy()).save(os.path.join(a.out, f"scale_{s:g}.png"))
         print(f"scale {s:g}: saved {os.path.join(a.out, f'scale_{s:g}.png')}")
     return a.out

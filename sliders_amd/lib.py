@@ -184,6 +184,8 @@ _HOST_FNS = {
     "slh_transpose_heads_blocks": (c_i32, [_P(TransposeDesc)]), "slh_lora_merge_blocks": (c_i32, [_P(LoraMergeItem)]),
     "slh_sigma_step": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
     "slh_latent_blend": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
+    "slh_direction_threshold": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
+    "slh_eps_direction": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
 }
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
@@ -463,6 +465,43 @@ def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int
     dims = (c_i32 * 4)(nb, chw, hw, 1 if fp32 else 0)
     coef = (c_f32 * 1)(s_next)
     check(load().slh_latent_blend(ptrs, dims, coef, c_vp(stream)), "slh_latent_blend")
+
+
+MAX_DIRECTIONS = 3          # prompt pairs per slh_direction_threshold / slh_eps_direction call
+
+
+def _direction_rows(what: str, pos, neg):
+    pos, neg = tuple(pos), tuple(neg)
+    if len(pos) != len(neg) or len(pos) > MAX_DIRECTIONS:
+        raise SlidersHipError(f"{what}: {len(pos)} pos and {len(neg)} neg rows: the same number of each, at most {MAX_DIRECTIONS}")
+    pad = (0,) * (MAX_DIRECTIONS - len(pos))
+    return pos + pad, neg + pad, len(pos)
+
+
+def direction_threshold(stream: int, *, pos, neg, thr: int, n_keep, nb: int, chw: int, hw: int):
+    """slh_direction_threshold (include/sliders_hip.h): thr[b][k][ch] (int32, [nb][K][chw / hw]) = the n_keep[k]-th largest key of
+    e+_k - e-_k over the hw pixels of channel ch of sample b.  pos, neg: K device addresses each (bf16 [nb][chw]); n_keep: K counts."""
+    pos, neg, K = _direction_rows("slh_direction_threshold", pos, neg)
+    n_keep = tuple(int(v) for v in n_keep)
+    if len(n_keep) != K:
+        raise SlidersHipError(f"slh_direction_threshold: {len(n_keep)} n_keep values for {K} directions")
+    ptrs = (c_vp * 7)(*pos, *neg, thr)
+    dims = (c_i32 * 7)(nb, chw, hw, K, *(n_keep + (0,) * (MAX_DIRECTIONS - K)))
+    check(load().slh_direction_threshold(ptrs, dims, None, c_vp(stream)), "slh_direction_threshold")
+
+
+def eps_direction(stream: int, *, t: int, out: int, pos, neg, c, nb: int, chw: int, hw: int, thr: int = 0):
+    """slh_eps_direction (include/sliders_hip.h): out = rne_bf16(t + sum_k c[k] keep_k (e+_k - e-_k)), the guided text row a step kernel
+    reads through eps_text.  pos, neg: K device addresses each; c: K coefficients (rounded to fp32 here, as the kernel reads them; a
+    zero skips its term); thr: what slh_direction_threshold wrote, 0: every element is kept."""
+    pos, neg, K = _direction_rows("slh_eps_direction", pos, neg)
+    c = tuple(float(v) for v in c)
+    if len(c) != K:
+        raise SlidersHipError(f"slh_eps_direction: {len(c)} coefficients for {K} directions")
+    ptrs = (c_vp * 9)(t, out, *pos, *neg, thr)
+    dims = (c_i32 * 4)(nb, chw, hw, K)
+    coef = (c_f32 * 3)(*(c + (0.0,) * (MAX_DIRECTIONS - K)))
+    check(load().slh_eps_direction(ptrs, dims, coef, c_vp(stream)), "slh_eps_direction")
 
 
 _GRAPHS_ON = os.environ.get("SLIDERS_HIPGRAPH", "1") != "0"

@@ -27,6 +27,7 @@ import torch
 from . import lib
 from . import schedulers
 from .ddim import DDIMSchedule
+from .directions import DirectionGuide, DirectionSet
 from .lora_store import LoraStore
 from .merge import SliderSet, WeightMerger
 from .passes import Pass
@@ -120,7 +121,8 @@ class SliderSampler:
     def sample_latents(self, ctx: torch.Tensor, noise: torch.Tensor, scale: float = 0.0, start_noise: int = 750,
                        ddim_steps: int = 50, guidance_scale: float = 7.5, pooled: Optional[torch.Tensor] = None,
                        time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-                       trace: Optional[SampleTrace] = None, share_prefix: bool = True) -> torch.Tensor:
+                       trace: Optional[SampleTrace] = None, share_prefix: bool = True, directions: Optional[DirectionSet] = None,
+                       direction_quantile: float = 0.0) -> torch.Tensor:
         """ctx: (2*bs, 77, D) = cat([unconditional, text]); noise: (bs, 4, h, w) UNIT noise (it is multiplied by the
         scheduler's init_noise_sigma here, generate_images_sd1.py:165); returns the final latents (bs, 4, h, w) bf16.
         LoRA multiplier per step: 0 while t > start_noise, `scale` after.
@@ -133,7 +135,13 @@ class SliderSampler:
         trace: the scale-0 run (base_trace) of this noise, conditioning, grid and guidance; built here if a mask comes without one.
         With a trace the chain starts on trace.x_start and uses its noise draws, not the scheduler generator's next ones.
         share_prefix: ddim, euler, euler_a, ddpm (no multistep history): start at the first step with t <= start_noise from the
-        trace's latent instead of replaying the steps every scale shares - the same bits.  ddim and latents="fp32" only."""
+        trace's latent instead of replaying the steps every scale shares - the same bits.  ddim and latents="fp32" only.
+        directions (sliders_amd/directions.py, docs/SAMPLING.md "Prompt-direction sampling"): prompt pairs that steer the run at `scale`
+        the way a slider trained on them would be taught to: on every step with t <= start_noise the pass also carries each pair's
+        positive and unconditional prompt (the wide plan, 2 more row blocks per pair), slh_eps_direction adds the scaled differences to
+        the text row and the step reads that row.  direction_quantile q in [0, 1): only the largest 1 - q of each latent channel's
+        differences act (slh_direction_threshold).  Steps above start_noise, and a call whose coefficients are all zero, run plain
+        sampling's launches on the plain plan.  store= / sliders= act on every row of the pass."""
         eng = self.eng
         bs, _, h, w = noise.shape
         if ctx.shape[0] not in (bs, 2 * bs):
@@ -152,15 +160,31 @@ class SliderSampler:
                                  f"{'single branch' if trace.single else 'CFG pair'}: this call has {ddim_steps} of {tuple(noise.shape)}, "
                                  f"{'single branch' if single else 'CFG pair'}")
             local = dict(mask=mask, trace=trace, start_noise=start_noise, share_prefix=share_prefix)
-        p = eng.plan(ctx.shape[0], h, w, "on" if self.store is not None else "off")
+        mode = "on" if self.store is not None else "off"
+        guide = None
+        if directions is not None:
+            DirectionSet.n_keep(h * w, direction_quantile)          # (an argument error, whether or not the directions act)
+            coef = directions.coefficients(scale, guidance_scale, single)
+            if any(c != 0.0 for c in coef):
+                guide = DirectionGuide(eng, directions, coef, direction_quantile, mode, bs, h, w, single, ctx, pooled, time_ids, start_noise)
+        p = eng.plan(ctx.shape[0], h, w, mode)
         drv = Pass(eng, p)
         drv.load_cond(ctx, pooled, time_ids)
         with self.slider_session(scale, start_noise) as gate:
             if self.latents == "fp32":
-                return self._sample_fp32(drv, gate, noise, ddim_steps, guidance_scale, single, **local)
+                return self._sample_fp32(drv, gate, noise, ddim_steps, guidance_scale, single, guide=guide, **local)
             if not self.sched.fused:
-                return self._sample_unfused(drv, gate, noise, ddim_steps, guidance_scale, single)
-            return self._sample_ddim(drv, gate, noise, ddim_steps, guidance_scale, single, **local)
+                return self._sample_unfused(drv, gate, noise, ddim_steps, guidance_scale, single, guide=guide)
+            return self._sample_ddim(drv, gate, noise, ddim_steps, guidance_scale, single, guide=guide, **local)
+
+    @staticmethod
+    def _widen(guide: DirectionGuide, latent: torch.Tensor) -> Pass:
+        """Crossing start_noise with directions: the latent the next pass reads moves from the plain plan's input buffer into every row
+        block of the wide plan's (a copy first: the two plans share the arena)"""
+        x = latent.clone()
+        drv = guide.enter()
+        drv.load_latents(x)
+        return drv
 
     def _check_localised(self, what: str):
         if self.latents != "fp32" and not self.sched.fused:
@@ -195,10 +219,12 @@ class SliderSampler:
         return next((i for i, t in enumerate(ts) if not float(t) > start_noise), len(ts))
 
     def _sample_ddim(self, drv: Pass, gate, noise, steps, guidance_scale, single=False, mask=None, trace=None, start_noise=750,
-                     share_prefix=True, record=None):
+                     share_prefix=True, record=None, guide=None):
         """The fused DDIM loop: per step slider gate -> UNet replay -> slh_cfg_ddim in place on io["sample"] (both halves for the pair).
         record (a dict): the scale-0 run's SampleTrace fields are left there.  trace: start on its latent - at the first live step if
-        share_prefix - and, with a mask, blend io["sample"] in place against trace.visited[i] after every live step."""
+        share_prefix - and, with a mask, blend io["sample"] in place against trace.visited[i] after every live step.
+        guide (DirectionGuide): from the first step with t <= start_noise on, the wide plan; the step reads the guided text row and one
+        copy spreads its result over the direction rows' blocks."""
         eng, io, smp = self.eng, drv.io, drv.io["sample"]
         bs, _, h, w = noise.shape
         s = torch.cuda.current_stream().cuda_stream
@@ -206,8 +232,9 @@ class SliderSampler:
         half = bs * chw * 2
         # single branch: the text half is read from the one epsilon there is and the guidance passed is 0 (guidance_scale is not
         # read), so the combine u + 0 * (u - u) hands the step u itself
-        pair = ({"out2": 0, "eps_text": io["eps"].ptr, "guidance": 0.0} if single
-                else {"out2": smp.ptr + half, "guidance": float(guidance_scale)})
+        # with directions both read the guided row `text` where the text row was read
+        pair = lambda text: ({"eps": text or io["eps"].ptr, "out2": 0, "eps_text": text or io["eps"].ptr, "guidance": 0.0} if single
+                             else {"eps": io["eps"].ptr, "out2": smp.ptr + half, "eps_text": text, "guidance": float(guidance_scale)})
         ts = self.sched.make_timesteps(steps)
         i0 = self._first_live(ts, start_noise) if trace is not None and share_prefix else 0
         if i0 == len(ts):            # the slider never acts: the base chain itself
@@ -219,14 +246,20 @@ class SliderSampler:
                           visited=torch.empty((steps,) + tuple(noise.shape), dtype=torch.bfloat16, device=eng.device))
             record["input0"] = record["x_start"]
         for i in range(i0, steps):
-            t = ts[i]
-            drv.run(t, gate(t, i == i0), s)
-            d = lib.CfgDdimDesc(eps=io["eps"].ptr, x=smp.ptr, out=smp.ptr, nb=bs, chw=chw, **pair,
+            t, first = ts[i], i == i0
+            wide = guide is not None and guide.live(t)
+            if wide and not guide.entered:
+                drv, first = self._widen(guide, smp.tensor[:bs]), True
+                io, smp = drv.io, drv.io["sample"]
+            drv.run(t, gate(t, first), s)
+            d = lib.CfgDdimDesc(x=smp.ptr, out=smp.ptr, nb=bs, chw=chw, **pair(guide.guide(s) if wide else 0),
                                 **self.sched.step_fields(t, steps))
             lib.call(lib.OP_CFG_DDIM, d, s)
             if mask is not None and not float(t) > start_noise:
                 lib.latent_blend(s, e=smp.ptr, keep=trace.visited[i].data_ptr(), mask=mask.data_ptr(), out=smp.ptr, nb=bs, chw=chw,
                                  hw=h * w, fp32=False, in_bf16=0 if single else smp.ptr + half)
+            if wide:
+                guide.spread()
             if record is not None:
                 record["visited"][i].copy_(smp.tensor[:bs])
         return smp.tensor[:bs].clone()
@@ -261,11 +294,13 @@ class SliderSampler:
             if self.store is not None:
                 eng.set_lora(False)
 
-    def _sample_unfused(self, drv: Pass, gate, noise, steps, guidance_scale, single=False):
+    def _sample_unfused(self, drv: Pass, gate, noise, steps, guidance_scale, single=False, guide=None):
         """generate_images_sd1.py:160-185 with a tensor-op scheduler: schedulers.denoise over the whole grid (scale_model_input ->
         prediction -> scheduler.step on the device latents), the prediction being slider gate -> UNet replay -> guidance combine
         (slh_cfg_ddim, do_step = 0).  single: one epsilon row per sample and nothing to combine; the step reads the plan's epsilon as
-        it is (it returns new tensors, so the next replay may overwrite it)"""
+        it is (it returns new tensors, so the next replay may overwrite it).  guide (DirectionGuide): from the first step with
+        t <= start_noise on the pass is the wide plan's and the prediction reads the guided text row - for the single branch it is that
+        row"""
         eng, sch, io = self.eng, self.sched, drv.io
         bs = noise.shape[0]
         s = torch.cuda.current_stream().cuda_stream
@@ -277,8 +312,17 @@ class SliderSampler:
         step = count()
 
         def predict(x, t):
+            nonlocal drv
+            first = next(step) == 0
+            wide = guide is not None and guide.live(t)
+            if wide and not guide.entered:
+                drv, first = guide.enter(), True
             drv.load_latents(x)
-            drv.run(t, gate(t, next(step) == 0), s)
+            drv.run(t, gate(t, first), s)
+            if wide:
+                combine.eps, combine.eps_text = drv.io["eps"].ptr, guide.guide(s)
+                if single:
+                    return guide.guided.view_as(lat)
             if not single:
                 lib.call(lib.OP_CFG_DDIM, combine, s)
             return eps
@@ -286,7 +330,7 @@ class SliderSampler:
         return schedulers.denoise(sch, predict, lat, steps, steps, generator=self.sched_generator, device=eng.device)
 
     def _sample_fp32(self, drv: Pass, gate, noise, steps, guidance_scale, single=False, mask=None, trace=None, start_noise=750,
-                     share_prefix=True, record=None):
+                     share_prefix=True, record=None, guide=None):
         """The same loop on an fp32 master latent: per step slider gate -> UNet replay -> ONE slh_sigma_step launch (the row of
         schedulers.step_row), which does the guidance combine and the scheduler's step in fp32, keeps the multistep history (a ring of
         min(order, steps) - 1 fp32 buffers owned by this call) and writes the next pass's scaled input into io["sample"], both halves
@@ -294,7 +338,9 @@ class SliderSampler:
         the noise of all steps is one fp32 draw from sched_generator per call - seed-deterministic, and deliberately not the bf16
         path's draws (those are bf16 tensors drawn step by step).  Returns the bf16 rounding of the final latent.
         record / trace / mask: as _sample_ddim; the draws are the trace's, the blend is on the master latent and rewrites the scaled
-        input with the row's s_next.  A scheduler with a multistep history (lms, dpmpp_2m) runs the whole grid."""
+        input with the row's s_next.  A scheduler with a multistep history (lms, dpmpp_2m) runs the whole grid.
+        guide (DirectionGuide): as _sample_ddim; the scaled input written for the first live step moves to the wide plan's buffer, and the
+        step writes the following ones there."""
         eng, sch, io = self.eng, self.sched, drv.io
         bs = noise.shape[0]
         chw = noise[0].numel()
@@ -323,9 +369,16 @@ class SliderSampler:
                           visited=torch.empty((steps,) + tuple(x.shape), dtype=torch.float32, device=eng.device))
         in2 = 0 if single else smp.ptr + bs * chw * 2
         for i in range(i0, steps):
-            t, r = ts[i], rows[i]
-            drv.run(t, gate(t, i == i0), s)
-            lib.sigma_step(s, eps=io["eps"].ptr, x=x.data_ptr(), out=x.data_ptr(), nb=bs, chw=chw, kind=r.kind, p=r.p, q=r.q,
+            t, r, first = ts[i], rows[i], i == i0
+            wide = guide is not None and guide.live(t)
+            if wide and not guide.entered:
+                drv, first = self._widen(guide, smp.tensor[:bs]), True
+                io, smp = drv.io, drv.io["sample"]
+                in2 = 0 if single else smp.ptr + bs * chw * 2
+            drv.run(t, gate(t, first), s)
+            text = guide.guide(s) if wide else 0          # the guided text row: the single branch's only row
+            lib.sigma_step(s, eps=text if wide and single else io["eps"].ptr, eps_text=0 if single else text, x=x.data_ptr(),
+                           out=x.data_ptr(), nb=bs, chw=chw, kind=r.kind, p=r.p, q=r.q,
                            sigma=r.sigma, a=r.a, c=r.c, c_n=r.c_n, s_next=r.s_next, guidance=float(guidance_scale), single=single,
                            hist=[ring[(i - k) % len(ring)].data_ptr() for k in range(1, r.n_hist + 1)],
                            noise=draws[i].data_ptr() if draws is not None and r.c_n != 0.0 else 0,
@@ -334,6 +387,8 @@ class SliderSampler:
             if mask is not None and not float(t) > start_noise:
                 lib.latent_blend(s, e=x.data_ptr(), keep=trace.visited[i].data_ptr(), mask=mask.data_ptr(), out=x.data_ptr(), nb=bs,
                                  chw=chw, hw=hw, fp32=True, s_next=r.s_next, in_bf16=smp.ptr, in2_bf16=in2)
+            if wide:
+                guide.spread()
             if record is not None:
                 record["visited"][i].copy_(x)
         return x.to(torch.bfloat16)
