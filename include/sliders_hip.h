@@ -542,6 +542,28 @@ int slh_latent_blend(const void* const* ptrs, const int32_t* dims, const float* 
 int slh_direction_threshold(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
 int slh_eps_direction(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
 
+/* slh_eps_direction with SEGA's momentum term (docs/SAMPLING.md, "Prompt-direction sampling"): nu, an fp32 state per element, carries
+ * the guidance the directions gave on the earlier passes into this one, and is updated from what they give now.  Per element, fp32,
+ * one rounding per operation, nothing contracted; keep is slh_eps_direction's rule (key(d) >= thr[b][k][ch], every tie kept, all kept
+ * without thr):
+ *   acc = t;  g = +0
+ *   for k ascending with c[k] != 0, where kept:   d = e+_k - e-_k;  p = c[k] * d;  acc = acc + p;  g = g + p
+ *   q = s_m * nu;   acc = acc + q;   gm = g + q
+ *   a = beta * nu;  b = omb * gm;    nu' = a + b
+ *   out = round-to-nearest-even bf16 of acc;   mom_out = nu'
+ * A term with c[k] == 0 is skipped as in slh_eps_direction: its rows are not read.  s_m == 0 is refused: momentum off is
+ * slh_eps_direction, whose acc keeps the sign of a -0 that an added +0 would lose.
+ * ptrs[11]: 0..8 as slh_eps_direction (t, out, pos[3], neg[3], optional thr)
+ *           9  mom_in   fp32 [nb][chw], nu
+ *           10 mom_out  fp32 [nb][chw], nu'; may be mom_in itself (every thread reads all it needs before it writes)
+ * dims[4]:  as slh_eps_direction
+ * coef[6]:  0..2 c[k], 3 s_m, 4 beta, 5 omb (the caller's 1 - beta, formed in double and rounded once)
+ * 16-byte accesses where every pointer, chw and hw allow them (eight elements per thread: one bf16 vector, two fp32 ones), one element
+ * per thread otherwise; any chw >= 1.  Never recorded in a program.  Refused before the launch: everything slh_eps_direction refuses; a
+ * null mom_in / mom_out, or one that is not 4-byte aligned; a non-finite s_m, beta or omb; s_m == 0; mom_out or out overlapping any
+ * input (mom_out == mom_in excepted); out overlapping mom_out. */
+int slh_eps_direction_momentum(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+
 /* The edit step of a localised edit: e = mu + resid exactly as slh_ddpm_edit_step mode 1 forms it (one piece of code), then, with
  * k = keep[i] and m = mask[b*hw + i % hw] (one mask value per latent pixel, shared by the channels),
  *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          fp32, one rounding per operation, no contraction.

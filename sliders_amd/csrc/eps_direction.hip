@@ -1,4 +1,4 @@
-// slh_direction_threshold, slh_eps_direction: prompt-direction sampling (sliders_amd/directions.py, docs/SAMPLING.md, "Prompt-direction
+// slh_direction_threshold, slh_eps_direction, slh_eps_direction_momentum: prompt-direction sampling (sliders_amd/directions.py, docs/SAMPLING.md, "Prompt-direction
 // sampling").  One UNet pass has produced, next to the text row t, the rows e+_k, e-_k of up to three prompt pairs on the same latent;
 // the guided text row the step kernels then read through their eps_text input is
 //
@@ -10,7 +10,8 @@
 //
 // fp32 throughout, one rounding per operation and nothing contracted, as csrc/sigma_step.hip and csrc/latent_blend.hip: the
 // restatement in tests/eps_direction_ref.py (same operations, same order) describes the kernel.  A term with c_k == 0 is dropped on the
-// host: its rows are never read, so NaN there never reaches out.
+// host: its rows are never read, so NaN there never reaches out.  slh_eps_direction_momentum is the same combine with SEGA's momentum
+// term, an fp32 state per element carried from pass to pass (its kernel below; tests/eps_momentum_ref.py restates it).
 //
 // slh_direction_threshold: one workgroup per (sample, direction, channel).  A radix select over the 16-bit key in two 8-bit passes:
 // count the keys by their high byte, find the bin that holds the n_keep-th largest, count that bin's keys by their low byte, find the
@@ -118,23 +119,22 @@ struct eps_direction_args {
     long n;                                                      // nb * chw
 };
 
-// VEC: eight elements per thread, n a multiple of 8 (and hw, where thr is given)
-template <bool VEC>
-__global__ __launch_bounds__(256) void eps_direction_kernel(const eps_direction_args d) {
+// acc[e] = t, then acc[e] = acc[e] + c_j * d_j over the kept terms, for the V elements from g on (thread i of the launch); SUM: g_sum[e],
+// the same products summed from +0 in the same order.  The one combine body of both kernels below.
+template <bool VEC, bool SUM>
+__device__ __forceinline__ void direction_combine(const eps_direction_args& d, const long i, const long g, float* acc, float* g_sum) {
 #pragma clang fp contract(off)
     constexpr int V = VEC ? 8 : 1;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d.n / V) return;
-    const long g = i * V;                           // the thread's first element
     const long b = g / d.chw;
     const int ch = (int)(g - b * d.chw) / d.hw;
-    float acc[V];
     if constexpr (VEC) {
         const bf16x8 tv = ((const bf16x8*)d.t)[i];
         for (int e = 0; e < 8; ++e) acc[e] = (float)tv[e];
     } else {
         acc[0] = (float)d.t[g];
     }
+    if constexpr (SUM)
+        for (int e = 0; e < V; ++e) g_sum[e] = 0.0f;
 #pragma unroll
     for (int j = 0; j < DIR_MAX; ++j) {
         if (j >= d.terms) break;
@@ -154,14 +154,76 @@ __global__ __launch_bounds__(256) void eps_direction_kernel(const eps_direction_
             const float prod = d.c[j] * diff;
             const float sum = acc[e] + prod;
             acc[e] = key >= tau ? sum : acc[e];      // a select on the key: a term that is not kept leaves acc's bits
+            if constexpr (SUM) {
+                const float gs = g_sum[e] + prod;
+                g_sum[e] = key >= tau ? gs : g_sum[e];
+            }
         }
     }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void direction_store(__bf16* out, const long i, const long g, const float* acc) {
     if constexpr (VEC) {
         bf16x8 ov;
         for (int e = 0; e < 8; ++e) ov[e] = (__bf16)acc[e];      // round to nearest even
-        ((bf16x8*)d.out)[i] = ov;
+        ((bf16x8*)out)[i] = ov;
     } else {
-        d.out[g] = (__bf16)acc[0];
+        out[g] = (__bf16)acc[0];
+    }
+}
+
+// VEC: eight elements per thread, n a multiple of 8 (and hw, where thr is given)
+template <bool VEC>
+__global__ __launch_bounds__(256) void eps_direction_kernel(const eps_direction_args d) {
+    constexpr int V = VEC ? 8 : 1;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d.n / V) return;
+    float acc[V];
+    direction_combine<VEC, false>(d, i, i * V, acc, nullptr);
+    direction_store<VEC>(d.out, i, i * V, acc);
+}
+
+// slh_eps_direction_momentum: the combine above with SEGA's momentum, nu the fp32 state between two passes:
+//   acc, g  as above (g: the kept products summed from +0)
+//   q = s_m * nu;  acc = acc + q;  gm = g + q;  a = beta * nu;  b = omb * gm;  nu' = a + b;  out = rne_bf16(acc);  mom_out = nu'
+// mom_out may be mom_in: a thread reads its elements of nu before it writes them, and no other thread touches them.
+struct eps_momentum_args {
+    eps_direction_args e;
+    const float* mom_in; float* mom_out;                         // fp32 [nb][chw]
+    float s_m, beta, omb;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void eps_direction_momentum_kernel(const eps_momentum_args d) {
+#pragma clang fp contract(off)
+    constexpr int V = VEC ? 8 : 1;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d.e.n / V) return;
+    const long g = i * V;
+    float acc[V], gm[V], nu[V];
+    if constexpr (VEC) {
+        const f32x4 lo = ((const f32x4*)d.mom_in)[2 * i], hi = ((const f32x4*)d.mom_in)[2 * i + 1];
+        for (int e = 0; e < 4; ++e) { nu[e] = lo[e]; nu[4 + e] = hi[e]; }
+    } else {
+        nu[0] = d.mom_in[g];
+    }
+    direction_combine<VEC, true>(d.e, i, g, acc, gm);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        const float q = d.s_m * nu[e];
+        acc[e] = acc[e] + q;
+        gm[e] = gm[e] + q;
+        const float a = d.beta * nu[e];
+        const float b = d.omb * gm[e];
+        nu[e] = a + b;
+    }
+    direction_store<VEC>(d.e.out, i, g, acc);
+    if constexpr (VEC) {
+        ((f32x4*)d.mom_out)[2 * i] = f32x4{nu[0], nu[1], nu[2], nu[3]};
+        ((f32x4*)d.mom_out)[2 * i + 1] = f32x4{nu[4], nu[5], nu[6], nu[7]};
+    } else {
+        d.mom_out[g] = nu[0];
     }
 }
 
@@ -212,34 +274,37 @@ extern "C" int slh_direction_threshold(const void* const* ptrs, const int32_t* d
     return 0;
 }
 
-extern "C" int slh_eps_direction(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream) {
-    SLH_CHECK(ptrs && dims && coef, "slh_eps_direction: null ptrs / dims / coef");
+// What slh_eps_direction and slh_eps_direction_momentum share: every check of the former, and its launch arguments.  vec: 16-byte
+// accesses are possible as far as these pointers and shapes go.
+static int direction_fill(const char* name, const void* const* ptrs, const int32_t* dims, const float* coef, eps_direction_args& d, bool& vec) {
+    SLH_CHECK(ptrs && dims && coef, "%s: null ptrs / dims / coef", name);
     const int nb = dims[0], chw = dims[1], hw = dims[2], K = dims[3];
-    DIR_SHAPE_CHECKS("slh_eps_direction");
-    eps_direction_args d;
+    SLH_CHECK(nb >= 1 && chw >= 1 && hw >= 1, "%s: nb = %d, chw = %d, hw = %d", name, nb, chw, hw);
+    SLH_CHECK(chw % hw == 0, "%s: chw = %d is not a multiple of hw = %d", name, chw, hw);
+    SLH_CHECK(K >= 1 && K <= DIR_MAX, "%s: K = %d directions (1..%d)", name, K, DIR_MAX);
     d.t = (const __bf16*)ptrs[0];
     d.out = (__bf16*)ptrs[1];
     d.thr = (const int*)ptrs[8];
-    SLH_CHECK(d.t && d.out, "slh_eps_direction: null t / out");
-    SLH_CHECK(aligned(d.thr, 4), "slh_eps_direction: the thr pointer (%p) is not 4-byte aligned", (const void*)d.thr);
+    SLH_CHECK(d.t && d.out, "%s: null t / out", name);
+    SLH_CHECK(aligned(d.thr, 4), "%s: the thr pointer (%p) is not 4-byte aligned", name, (const void*)d.thr);
     const long n = (long)nb * chw, groups = (long)nb * K * (chw / hw);
-    bool vec = chw % 8 == 0 && (!d.thr || hw % 8 == 0);
+    vec = chw % 8 == 0 && (!d.thr || hw % 8 == 0);
     for (const void* p : {(const void*)d.t, (const void*)d.out}) {
-        SLH_CHECK(aligned(p, 2), "slh_eps_direction: a bf16 pointer (%p) is not 2-byte aligned", p);
+        SLH_CHECK(aligned(p, 2), "%s: a bf16 pointer (%p) is not 2-byte aligned", name, p);
         vec = vec && aligned(p, 16);
     }
-    SLH_CHECK(!overlaps(d.out, n * 2, d.t, n * 2), "slh_eps_direction: out overlaps t");
-    SLH_CHECK(!overlaps(d.out, n * 2, d.thr, groups * 4), "slh_eps_direction: out overlaps thr");
+    SLH_CHECK(!overlaps(d.out, n * 2, d.t, n * 2), "%s: out overlaps t", name);
+    SLH_CHECK(!overlaps(d.out, n * 2, d.thr, groups * 4), "%s: out overlaps thr", name);
     d.terms = 0;
     for (int k = 0; k < DIR_MAX; ++k) d.pos[k] = d.neg[k] = nullptr, d.c[k] = 0.0f, d.slot[k] = 0;
     for (int k = 0; k < K; ++k) {
         const void* pos = ptrs[2 + k];
         const void* neg = ptrs[2 + DIR_MAX + k];
-        SLH_CHECK(pos && neg, "slh_eps_direction: null pos[%d] / neg[%d]", k, k);
-        SLH_CHECK(std::isfinite(coef[k]), "slh_eps_direction: c[%d] = %f is not finite", k, (double)coef[k]);
+        SLH_CHECK(pos && neg, "%s: null pos[%d] / neg[%d]", name, k, k);
+        SLH_CHECK(std::isfinite(coef[k]), "%s: c[%d] = %f is not finite", name, k, (double)coef[k]);
         for (const void* p : {pos, neg}) {
-            SLH_CHECK(aligned(p, 2), "slh_eps_direction: a bf16 pointer (%p) is not 2-byte aligned", p);
-            SLH_CHECK(!overlaps(d.out, n * 2, p, n * 2), "slh_eps_direction: out overlaps pos[%d] / neg[%d]", k, k);
+            SLH_CHECK(aligned(p, 2), "%s: a bf16 pointer (%p) is not 2-byte aligned", name, p);
+            SLH_CHECK(!overlaps(d.out, n * 2, p, n * 2), "%s: out overlaps pos[%d] / neg[%d]", name, k, k);
         }
         if (coef[k] == 0.0f) continue;             // skipped, not multiplied: its rows are not read
         vec = vec && aligned(pos, 16) && aligned(neg, 16);
@@ -248,11 +313,53 @@ extern "C" int slh_eps_direction(const void* const* ptrs, const int32_t* dims, c
         ++d.terms;
     }
     d.K = K; d.C = chw / hw; d.hw = hw; d.chw = chw; d.n = n;
-    const long threads = vec ? n / 8 : n;
-    SLH_CHECK((threads + 255) / 256 < (1L << 31), "slh_eps_direction: nb * chw = %ld is too large for one launch", n);
+    return 0;
+}
+
+extern "C" int slh_eps_direction(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream) {
+    eps_direction_args d;
+    bool vec;
+    if (const int rc = direction_fill("slh_eps_direction", ptrs, dims, coef, d, vec)) return rc;
+    const long threads = vec ? d.n / 8 : d.n;
+    SLH_CHECK((threads + 255) / 256 < (1L << 31), "slh_eps_direction: nb * chw = %ld is too large for one launch", d.n);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (vec) hipLaunchKernelGGL(eps_direction_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d);
     else hipLaunchKernelGGL(eps_direction_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d);
     SLH_LAUNCH_CHECK("slh_eps_direction");
+    return 0;
+}
+
+extern "C" int slh_eps_direction_momentum(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream) {
+    static const char* const name = "slh_eps_direction_momentum";
+    eps_momentum_args m;
+    eps_direction_args& d = m.e;
+    bool vec;
+    if (const int rc = direction_fill(name, ptrs, dims, coef, d, vec)) return rc;
+    m.mom_in = (const float*)ptrs[9];
+    m.mom_out = (float*)ptrs[10];
+    m.s_m = coef[3]; m.beta = coef[4]; m.omb = coef[5];
+    SLH_CHECK(m.mom_in && m.mom_out, "%s: null mom_in / mom_out", name);
+    for (const void* p : {(const void*)m.mom_in, (const void*)m.mom_out}) {
+        SLH_CHECK(aligned(p, 4), "%s: an fp32 pointer (%p) is not 4-byte aligned", name, p);
+        vec = vec && aligned(p, 16);
+    }
+    SLH_CHECK(std::isfinite(m.s_m) && std::isfinite(m.beta) && std::isfinite(m.omb), "%s: s_m = %f, beta = %f, omb = %f: not finite", name,
+              (double)m.s_m, (double)m.beta, (double)m.omb);
+    SLH_CHECK(m.s_m != 0.0f, "%s: s_m == 0: without momentum call slh_eps_direction (adding a zero would turn a -0 of acc into +0)", name);
+    const long n = d.n, groups = (long)dims[0] * d.K * d.C;
+    SLH_CHECK(m.mom_out == m.mom_in || !overlaps(m.mom_out, n * 4, m.mom_in, n * 4), "%s: mom_out overlaps mom_in without being it", name);
+    SLH_CHECK(!overlaps(d.out, n * 2, m.mom_in, n * 4), "%s: out overlaps mom_in", name);
+    SLH_CHECK(!overlaps(d.out, n * 2, m.mom_out, n * 4), "%s: out overlaps mom_out", name);
+    SLH_CHECK(!overlaps(m.mom_out, n * 4, d.t, n * 2), "%s: mom_out overlaps t", name);
+    SLH_CHECK(!overlaps(m.mom_out, n * 4, d.thr, groups * 4), "%s: mom_out overlaps thr", name);
+    for (int k = 0; k < d.K; ++k)
+        for (const void* p : {ptrs[2 + k], ptrs[2 + DIR_MAX + k]})
+            SLH_CHECK(!overlaps(m.mom_out, n * 4, p, n * 2), "%s: mom_out overlaps pos[%d] / neg[%d]", name, k, k);
+    const long threads = vec ? n / 8 : n;
+    SLH_CHECK((threads + 255) / 256 < (1L << 31), "%s: nb * chw = %ld is too large for one launch", name, n);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (vec) hipLaunchKernelGGL(eps_direction_momentum_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    else hipLaunchKernelGGL(eps_direction_momentum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    SLH_LAUNCH_CHECK(name);
     return 0;
 }

@@ -12,9 +12,14 @@ runs, the `positive` and `unconditional` prompts of up to three prompts.yaml ent
 sign + for `enhance`, - for `erase`; eta the entry's guidance_scale; keep_k the sparsifier of slh_direction_threshold (the largest
 entries of each latent channel).  slh_eps_direction writes the guided text row t' = rne_bf16(t + sum_k c_k keep_k d_k) that the step
 kernels read through their eps_text input: c_k = w_k / g for the CFG pair, w_k for the single branch.
+
+Momentum (SEGA's second half; momentum=(s_m, beta)): an fp32 state nu per latent element, zero when a call first acts, is added to the
+guided row at strength s_m and then moved towards what the directions (and it) just gave: slh_eps_direction_momentum,
+t' = rne_bf16(t + G), G = sum_k c_k keep_k d_k + s_m nu, nu <- beta nu + (1 - beta) G.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -107,12 +112,33 @@ class DirectionSet:
         return ctx, torch.cat([fit(v) for d in self.directions for v in (d.pooled_pos, d.pooled_neg)])
 
 
+def check_momentum(momentum) -> Optional[Tuple[float, float]]:
+    """momentum=(s_m, beta) as DirectionGuide takes it -> (s_m, beta), or None where there is no momentum: None, or an s_m whose fp32
+    value is 0 (the launches are then slh_eps_direction's, bit for bit).  s_m finite, 0 <= beta < 1, else a ValueError."""
+    if momentum is None:
+        return None
+    try:
+        s_m, beta = (float(v) for v in momentum)
+    except (TypeError, ValueError):
+        raise ValueError(f"direction_momentum {momentum!r}: expected (s_m, beta)")
+    if not math.isfinite(s_m) or not 0.0 <= beta < 1.0:
+        raise ValueError(f"direction_momentum {momentum!r}: expected a finite s_m and 0 <= beta < 1")
+    if not math.isfinite(ctypes.c_float(s_m).value):
+        raise ValueError(f"direction_momentum {momentum!r}: s_m is not finite in fp32")
+    return None if ctypes.c_float(s_m).value == 0.0 else (s_m, beta)
+
+
 class DirectionGuide:
     """The wide pass of one sampling call: the plan of R = (1 or 2) + 2 J row blocks, entered at the first step the directions act on,
-    and the launches between its replay and the step.  Row blocks of bs rows: [u, t, e+_1, e-_1, ...] (single branch: [t, e+_1, ...])."""
+    and the launches between its replay and the step.  Row blocks of bs rows: [u, t, e+_1, e-_1, ...] (single branch: [t, e+_1, ...]).
+    momentum=(s_m, beta): the combine is slh_eps_direction_momentum on a state this guide owns, zero when the plan is entered; None or
+    s_m == 0: slh_eps_direction."""
 
     def __init__(self, eng, dirs: DirectionSet, coef: Sequence[float], quantile: float, mode: str, bs: int, h: int, w: int, single: bool,
-                 ctx: torch.Tensor, pooled: Optional[torch.Tensor], time_ids: Optional[torch.Tensor], start_noise: float):
+                 ctx: torch.Tensor, pooled: Optional[torch.Tensor], time_ids: Optional[torch.Tensor], start_noise: float,
+                 momentum: Optional[Tuple[float, float]] = None):
+        self.momentum = check_momentum(momentum)
+        self.mom = None
         self.eng, self.dirs, self.coef, self.mode = eng, dirs, [float(c) for c in coef], mode
         self.bs, self.h, self.w, self.single, self.start_noise = bs, h, w, single, float(start_noise)
         self.base = 1 if single else 2                   # row blocks of plain sampling
@@ -147,6 +173,8 @@ class DirectionGuide:
         self.guided = torch.empty((bs,) + tuple(self.drv.io["eps"].tensor.shape[1:]), dtype=torch.bfloat16, device=eng.device)
         if self.keep < self.hw:
             self.thr = torch.empty((bs, len(self.dirs), self.chw // self.hw), dtype=torch.int32, device=eng.device)
+        if self.momentum is not None:
+            self.mom = torch.zeros((bs, self.chw), dtype=torch.float32, device=eng.device)
         return self.drv
 
     def block(self, name: str, j: int) -> int:
@@ -155,15 +183,21 @@ class DirectionGuide:
         return b.ptr + j * (b.nbytes // self.blocks)
 
     def guide(self, stream: int) -> int:
-        """after the wide replay: the threshold launch (a quantile > 0 only) and the combine -> the address of the guided text row"""
+        """after the wide replay: the threshold launch (a quantile > 0 only) and the combine (with momentum: which also moves the state)
+        -> the address of the guided text row"""
         J = len(self.dirs)
         pos = [self.block("eps", self.base + 2 * k) for k in range(J)]
         neg = [self.block("eps", self.base + 2 * k + 1) for k in range(J)]
         shape = dict(nb=self.bs, chw=self.chw, hw=self.hw)
         if self.thr is not None:
             lib.direction_threshold(stream, pos=pos, neg=neg, thr=self.thr.data_ptr(), n_keep=[self.keep] * J, **shape)
-        lib.eps_direction(stream, t=self.block("eps", self.base - 1), out=self.guided.data_ptr(), pos=pos, neg=neg, c=self.coef,
-                          thr=0 if self.thr is None else self.thr.data_ptr(), **shape)
+        rows = dict(t=self.block("eps", self.base - 1), out=self.guided.data_ptr(), pos=pos, neg=neg, c=self.coef,
+                    thr=0 if self.thr is None else self.thr.data_ptr(), **shape)
+        if self.mom is None:
+            lib.eps_direction(stream, **rows)
+        else:                            # the state is updated in place
+            lib.eps_direction_momentum(stream, mom_in=self.mom.data_ptr(), mom_out=self.mom.data_ptr(), s_m=self.momentum[0],
+                                       beta=self.momentum[1], **rows)
         return self.guided.data_ptr()
 
     def spread(self):

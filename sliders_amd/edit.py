@@ -28,6 +28,10 @@ comes from a file (`load_mask`, `feather_mask`) or from where the slider changes
 (`SliderEditor.footprint`, slh_eps_absdiff; `footprint_mask`), or from where a word of the prompt lives in the UNet's cross-attention
 (`SliderEditor.word_map`, slh_xattn_map; `word_mask`, `word_token_indices`).  `blend_reference` restates the blend as the other
 references do.
+
+Prompt-direction edits (directions=, --direction; docs/EDIT.md "Prompt-direction edits"): below start_noise the pass also carries the
+positive and unconditional prompt of up to three pairs (sliders_amd/directions.py), and the step reads the text row with their scaled
+differences added (slh_eps_direction, or slh_eps_direction_momentum with direction_momentum=) through its eps_text input.
 """
 from __future__ import annotations
 
@@ -41,6 +45,7 @@ import torch
 
 from . import lib
 from .ddim import DDIMSchedule
+from .directions import DirectionGuide, DirectionSet, check_momentum
 from .passes import Pass
 from .sampler import SliderSampler
 from .vae import VaeDecoder
@@ -446,13 +451,14 @@ class SliderEditor(SliderSampler):
         drv.load_cond(ctx, pooled, time_ids)
         return drv
 
-    def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None):
+    def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None, eps_text=0):
         """The step's one element-wise launch after the UNet pass, src -> dst (fp32, may be one tensor) and the bf16 halves of `sample`:
         slh_ddpm_edit_step - mode 0 with a target (resid_i written), else mode 1 (resid_i read) - or, with a mask, slh_ddpm_edit_blend
-        against keep"""
+        against keep.  eps_text: the address of a text row to read in place of the one behind the unconditional half (a direction
+        step's guided row; p is then the wide plan, whose first two row blocks are the pair's)"""
         io, bs, chw = p.io, src.shape[0], src[0].numel()
         smp = io["sample"]
-        common = dict(eps=io["eps"].ptr, x=src.data_ptr(), resid=resid_i.data_ptr(), out=dst.data_ptr(), out_bf16=smp.ptr,
+        common = dict(eps=io["eps"].ptr, eps_text=eps_text, x=src.data_ptr(), resid=resid_i.data_ptr(), out=dst.data_ptr(), out_bf16=smp.ptr,
                       out2_bf16=smp.ptr + bs * chw * 2, nb=bs, chw=chw, guidance=float(guidance),
                       v_prediction=1 if self.sched.prediction_type == "v_prediction" else 0,
                       **fp32_coefficients(ddpm_step_coefficients(self.sched, t, steps, eta)))
@@ -465,21 +471,33 @@ class SliderEditor(SliderSampler):
             lib.call(lib.OP_DDPM_EDIT_BLEND, d, s)
 
     def _chain(self, drv: Pass, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None, record=None, keep=None,
-               mask=None):
+               mask=None, guide=None):
         """x (fp32) through the grid; returns the final latent.  path given = invert (resid written), else edit (resid read).
         record None: x is updated in place.  record [len(ts)][bs][4][h][w]: the same launches, but step i reads record[i - 1] (x for
         i = 0) and writes record[i], so the chain's latents are kept (the inversion, `trajectory`).
         mask [bs][1][h][w] with keep = the inversion's latents: every step is blended against keep[i] (in place).
         The slider is the sampler's (slider_session), except that a multiplier of 0 means the inversion's pass: at scale 0 nothing is
-        merged, sliders held at a fixed scale included (they belong to the edit, and scale 0 is the reconstruction)."""
+        merged, sliders held at a fixed scale included (they belong to the edit, and scale 0 is the reconstruction).
+        guide (DirectionGuide, an edit only): the steps with t > start_noise are the launches above; at the first live step the pass
+        moves to the wide plan - the bf16 rounding of the fp32 master, which is what the step before wrote as the plain plan's input,
+        into every row block, and the full program, since the direction rows' cross-attention K/V were never projected - and from
+        there on every step is wide replay -> guide.guide -> the same step launch reading the guided text row and writing the wide
+        plan's first two row blocks -> guide.spread."""
         drv.load_latents(x)
         s = torch.cuda.current_stream().cuda_stream
         with self.slider_session(scale, start_noise, zero_merges=False) as gate:
             for i, t in enumerate(ts):
-                drv.run(t, gate(t, i == 0), s)
                 src, dst = (x, x) if record is None else (x if i == 0 else record[i - 1], record[i])
+                first, wide = i == 0, guide is not None and guide.live(t)
+                if wide and not guide.entered:
+                    drv, first = guide.enter(), True
+                    drv.load_latents(src)
+                drv.run(t, gate(t, first), s)
                 target = None if path is None else (path[i + 1] if i + 1 < len(ts) else x0)
-                self._launch_step(drv.p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask)
+                self._launch_step(drv.p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask,
+                                  eps_text=guide.guide(s) if wide else 0)
+                if wide:
+                    guide.spread()
         return x if record is None else record[-1].clone()
 
     @torch.no_grad()
@@ -537,11 +555,16 @@ class SliderEditor(SliderSampler):
     @torch.no_grad()
     def edit_latents(self, space: NoiseSpace, ctx: Optional[torch.Tensor] = None, scale: float = 0.0, start_noise: int = 750,
                      guidance_scale: Optional[float] = None, pooled: Optional[torch.Tensor] = None,
-                     time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     directions: Optional[DirectionSet] = None, direction_quantile: float = 0.0,
+                     direction_momentum: Optional[Tuple[float, float]] = None) -> torch.Tensor:
         """-> the edited latents (bs, 4, h, w) fp32.  ctx / guidance_scale None: the inversion's own - then scale 0 returns
         space.recon bit for bit.  Another prompt or guidance is an edit of its own; no reconstruction claim applies.
         mask ([h][w], [bs][h][w] or [bs][1][h][w], values in [0, 1], 1 = edit): every step is blended against the inversion's latent
-        after that step, so where the mask is 0 the result is space.recon bit for bit - at any scale, prompt or guidance."""
+        after that step, so where the mask is 0 the result is space.recon bit for bit - at any scale, prompt or guidance.
+        directions / direction_quantile / direction_momentum: as SliderSampler.sample_latents, with the coefficients of the CFG pair at
+        this edit's guidance; `scale` drives them and store= / sliders= alike.  Where they do not act - scale 0, or no step of the grid
+        with t <= start_noise - nothing of them is built or launched: the chain is the one without them."""
         self._check_prediction(space)
         if ctx is None:
             self._check_conditioning(space, "edit_latents without ctx")
@@ -556,22 +579,37 @@ class SliderEditor(SliderSampler):
         if mask is not None:
             mask = as_mask(mask, bs, h, w).to(dev)
             visited = self.trajectory(space).visited.to(dev, torch.float32).contiguous()
-        drv = self._pass(bs, h, w, ctx, pooled, time_ids)
         g = space.guidance if guidance_scale is None else guidance_scale
-        return self._chain(drv, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask)
+        guide = None
+        if directions is not None:
+            DirectionSet.n_keep(h * w, direction_quantile)          # (argument errors, whether or not the directions act)
+            check_momentum(direction_momentum)
+            coef = directions.coefficients(scale, g, single=False)
+            if any(c != 0.0 for c in coef) and any(not float(t) > start_noise for t in space.timesteps):
+                guide = DirectionGuide(self.eng, directions, coef, direction_quantile, "on" if self.store is not None else "off", bs, h, w,
+                                       False, ctx, pooled, time_ids, start_noise, momentum=direction_momentum)
+        elif direction_momentum is not None:
+            raise ValueError("edit_latents: direction_momentum without directions")
+        drv = self._pass(bs, h, w, ctx, pooled, time_ids)
+        return self._chain(drv, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask, guide=guide)
 
     @torch.no_grad()
-    def footprint(self, space: NoiseSpace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200) -> torch.Tensor:
+    def footprint(self, space: NoiseSpace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200,
+                  directions: Optional[DirectionSet] = None, direction_quantile: float = 0.0, guidance_scale: Optional[float] = None) -> torch.Tensor:
         """Where the slider acts on this image: F [bs][h][w] fp32 = the mean over `draws` noise levels of
         sum_c |eps(slider at `scale`) - eps(slider off)| (slh_eps_absdiff), each draw divided by its mean over the pixels - DiffEdit's
         contrast (Couairon et al. 2022) with the slider in place of the second prompt.  The UNet inputs are the inversion's own at
         those levels (x_start / visited[i - 1]: the image under independent noise draws), conditioning and guidance the inversion's.
         All slider-off passes run first, then the slider is switched on once (store=: the multiplier; sliders=: one merge, full
-        program on the first pass after it) for the slider-on passes: 2 * len(draws) UNet passes."""
+        program on the first pass after it) for the slider-on passes: 2 * len(draws) UNet passes.
+        directions (with direction_quantile; guidance_scale None: the inversion's): where the prompt directions act instead.  One wide
+        pass per draw gives u, t and the pairs' rows; with t' the guided text row of a direction step at `scale` (no momentum: a draw
+        is not a chain) the map is slh_eps_absdiff of (u, t') against (u, t) = sum_c |g (t' - t)|, what the step would see differently:
+        len(draws) UNet passes."""
         self._check_prediction(space)
         self._check_conditioning(space, "footprint")
         footprint_draws(space.timesteps, start_noise, draws, t_min)          # the grid's errors before the trajectory is replayed
-        return self._footprint(_SpaceSource(self, space), scale, start_noise, draws, t_min)
+        return self._footprint(_SpaceSource(self, space), scale, start_noise, draws, t_min, directions, direction_quantile, guidance_scale)
 
     @torch.no_grad()
     def word_map(self, space: NoiseSpace, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None, draws: int = 8,
@@ -640,6 +678,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mask_word_draws", type=int, default=None, help="steps of the grid the word map averages over (default 8)")
     p.add_argument("--save_attention", default=None, help="write the word map / its maximum here (8-bit PNG at latent resolution)")
     p.add_argument("--save_mask", default=None, help="write the latent-resolution mask here (8-bit PNG)")
+    # prompt-direction edits (docs/EDIT.md): the options of sliders_amd.generate, --scales sweeps the direction's strength
+    p.add_argument("--direction", action="append", default=[], metavar="POSITIVE|NEGATIVE[:ETA]",
+                   help="edit along eps(POSITIVE) - eps(NEGATIVE), times ETA (default 1) times the scale; repeatable, at most 3")
+    p.add_argument("--direction_file", default=None, help="the same from a prompts.yaml of the trainers: positive, unconditional, guidance_scale "
+                                                          "(ETA) and action (erase: the opposite sign) of its entries")
+    p.add_argument("--direction_entries", default=None, metavar="I,J,...", help="entries of --direction_file to take (default: all, at most 3)")
+    p.add_argument("--direction_quantile", type=float, default=None, metavar="Q",
+                   help="keep only the largest 1 - Q of each latent channel's differences (default 0: all of them)")
+    p.add_argument("--direction_momentum", default=None, metavar="S_M[:BETA]",
+                   help="SEGA's momentum on the direction: strength S_M, decay BETA (default 0.4); 0: none")
     return p
 
 
@@ -662,6 +710,10 @@ def check_args(a):
         scales = [float(v) for v in a.scales.split(",")]
     except ValueError:
         raise SystemExit(f"--scales {a.scales!r}: expected comma-separated numbers")
+    from .generate import check_direction_args
+    g = a.guidance_scale if a.edit_guidance_scale is None else a.edit_guidance_scale
+    check_direction_args(a, no_cfg=False, guidance_scale=g, guidance_option="--edit_guidance_scale" if a.edit_guidance_scale is not None
+                         else "--guidance_scale")
     check_mask_args(a, scales, lambda: edit_timesteps(DDIMSchedule(), a.steps, skip))
     return scales
 
@@ -698,7 +750,7 @@ def check_mask_args(a, scales: List[float], grid: Callable[[], List]):
     if given and not a.auto_mask:
         raise SystemExit("--auto_mask_" + given[0] + " needs --auto_mask")
     if a.auto_mask:
-        if not a.lora_weight and not a.compose:
+        if not a.lora_weight and not a.compose and not (getattr(a, "direction", None) or getattr(a, "direction_file", None)):
             raise SystemExit("--auto_mask is the slider's footprint: it needs --lora_weight (or --compose)")
         if a.auto_mask_scale is None:
             a.auto_mask_scale = max(scales, key=abs)
@@ -721,10 +773,11 @@ def _suffixed(path: str, suffix: str) -> str:
     return root + suffix + ext
 
 
-def mask_from_args(a, ed, src, res: int, prompt: str, tokenizer, suffix: str = ""):
+def mask_from_args(a, ed, src, res: int, prompt: str, tokenizer, suffix: str = "", **steer):
     """The mask the command line asks for, or None: from the file (--mask), from the slider's footprint (--auto_mask: ed.footprint over
-    src) or from the prompt's words (--mask_word / --mask_tokens: ed.word_map over src); --save_attention and --save_mask are written
-    here (suffix: put in front of their extensions).  ed / src: a SliderEditor and its NoiseSpace, or a SliderSampler and a SampleTrace.
+    src; steer: directions= / direction_quantile= / guidance_scale= - the footprint is then the directions') or from the prompt's words
+    (--mask_word / --mask_tokens: ed.word_map over src); --save_attention and --save_mask are written here (suffix: put in front of
+    their extensions).  ed / src: a SliderEditor and its NoiseSpace, or a SliderSampler and a SampleTrace.
     res: the image size the latents decode to."""
     from PIL import Image
     mask = None
@@ -732,7 +785,7 @@ def mask_from_args(a, ed, src, res: int, prompt: str, tokenizer, suffix: str = "
         mask = feather_mask(load_mask(a.mask, res, a.mask_invert), a.mask_feather or 0.0)
     elif a.auto_mask:
         try:          # (check_args tried the grid of the command line; a saved inversion brings its own)
-            F = ed.footprint(src, a.auto_mask_scale, start_noise=a.start_noise, draws=a.auto_mask_draws or 8)
+            F = ed.footprint(src, a.auto_mask_scale, start_noise=a.start_noise, draws=a.auto_mask_draws or 8, **steer)
             mask = footprint_mask(F.cpu(), threshold=0.5 if a.auto_mask_threshold is None else a.auto_mask_threshold,
                                   dilate=1 if a.auto_mask_dilate is None else a.auto_mask_dilate,
                                   feather=1.0 if a.mask_feather is None else a.mask_feather)
@@ -775,6 +828,8 @@ def main(argv=None):
     xl = a.model == "sdxl"
     res = a.res or (1024 if xl else 512)
     prompts = [a.prompt] + ([a.edit_prompt] if a.edit_prompt is not None else [])
+    from .generate import direction_set, direction_specs
+    specs = direction_specs(a)
     if a.synthetic:
         eng = synthetic_engine(a.model, dev, a.seed)
         vae_sd = random_vae_state_dict(device=dev, seed=a.seed, decoder=True)
@@ -783,6 +838,7 @@ def main(argv=None):
         for _ in prompts:            # a prompt is a draw: the first is the image's, the second the edit's
             cond.append((torch.randn(2, 77, eng.cfg.cross_attention_dim, generator=g),
                          torch.randn(2, eng.cfg.pooled_dim, generator=g) if xl else None))
+        encode = None
     else:
         from safetensors.torch import load_file
         from . import model_util
@@ -795,11 +851,14 @@ def main(argv=None):
             for pr in prompts:
                 (e_u, p_u), (e_t, p_t) = (model_util.encode_prompts_xl(toks, encs, [s]) for s in ("", pr))
                 cond.append((torch.cat([e_u, e_t]), torch.cat([p_u, p_t])))
+            encode = lambda text: model_util.encode_prompts_xl(toks, encs, [text])
         else:
             tok, enc = model_util.load_text_encoder(a.model_path, dev, torch.bfloat16)
             tokenizer = tok
             for pr in prompts:
                 cond.append((torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in ("", pr)]), None))
+            encode = lambda text: (model_util.encode_prompts(tok, enc, [text]), None)
+    steer = direction_set(a, specs, encode, eng.cfg, xl)
     dec = VaeDecoder(vae_sd, dev, VAE_SCALING[a.model])
     store = sliders = None
     swept = torch.load(a.lora_weight, map_location="cpu") if a.lora_weight else None
@@ -830,8 +889,11 @@ def main(argv=None):
             print(f"inversion saved to {a.save_inversion}")
     os.makedirs(a.out, exist_ok=True)
     Image.fromarray(VaeDecoder.to_uint8(dec.decode(space.recon))[0].cpu().numpy()).save(os.path.join(a.out, "recon.png"))
-    kw = dict(start_noise=a.start_noise, guidance_scale=a.edit_guidance_scale)
-    mask = mask_from_args(a, ed, space, 8 * space.x0.shape[-1], a.prompt, tokenizer)    # a saved inversion: its size
+    kw = dict(start_noise=a.start_noise, guidance_scale=a.edit_guidance_scale, **steer)
+    foot = {k: v for k, v in steer.items() if k != "direction_momentum"}
+    if foot:
+        foot["guidance_scale"] = a.edit_guidance_scale
+    mask = mask_from_args(a, ed, space, 8 * space.x0.shape[-1], a.prompt, tokenizer, **foot)    # a saved inversion: its size
     if mask is not None:
         kw["mask"] = mask
     if a.edit_prompt is not None:

@@ -114,6 +114,8 @@ def build_parser(defaults: bool = True) -> argparse.ArgumentParser:
     add("--direction_entries", default=None, metavar="I,J,...", help="entries of --direction_file to take (default: all, at most 3)")
     add("--direction_quantile", type=float, default=None, metavar="Q",
         help="keep only the largest 1 - Q of each latent channel's differences (default 0: all of them)")
+    add("--direction_momentum", default=None, metavar="S_M[:BETA]",
+        help="SEGA's momentum on the direction: strength S_M, decay BETA (default 0.4); 0: none")
     return p
 
 
@@ -161,12 +163,39 @@ def direction_specs(a) -> list:
     return specs
 
 
-def check_direction_args(a) -> list:
+DEFAULT_MOMENTUM_BETA = 0.4
+
+
+def direction_momentum(a):
+    """--direction_momentum S_M[:BETA] -> (s_m, beta), or None where the option is not given; every error of the option is raised here"""
+    from .directions import check_momentum
+    if a.direction_momentum is None:
+        return None
+    head, sep, tail = a.direction_momentum.partition(":")
+    try:
+        pair = (float(head), float(tail) if sep else DEFAULT_MOMENTUM_BETA)
+    except ValueError:
+        raise SystemExit(f"--direction_momentum {a.direction_momentum!r}: expected S_M[:BETA]")
+    try:
+        check_momentum(pair)
+    except ValueError as e:
+        raise SystemExit(f"--direction_momentum {a.direction_momentum!r}: {e}")
+    return pair
+
+
+def check_direction_args(a, no_cfg=None, guidance_scale=None, guidance_option: str = "--guidance_scale") -> list:
+    """every argument error of the direction options (shared with sliders_amd.edit, which has no --no_cfg and may name another
+    guidance option: the arguments in their place)"""
     from .directions import DirectionSet
+    no_cfg = a.no_cfg if no_cfg is None else no_cfg
+    guidance_scale = a.guidance_scale if guidance_scale is None else guidance_scale
     specs = direction_specs(a)
+    momentum = direction_momentum(a)
     if not specs:
         if a.direction_quantile is not None:
             raise SystemExit("--direction_quantile needs --direction or --direction_file")
+        if momentum is not None:
+            raise SystemExit("--direction_momentum needs --direction or --direction_file")
         return specs
     try:
         DirectionSet.n_keep(1, a.direction_quantile or 0.0)
@@ -175,10 +204,31 @@ def check_direction_args(a) -> list:
     if a.lora_weight:
         raise SystemExit("--direction / --direction_file: --scales sweeps the direction's strength, not with --lora_weight (sliders held at a "
                          "fixed scale go next to it with --compose)")
-    if not a.no_cfg and a.guidance_scale == 0:
-        raise SystemExit("--direction with --guidance_scale 0: the direction enters through the text row of the CFG pair, which a guidance "
-                         "of 0 does not read (or sample with --no_cfg)")
+    if not no_cfg and guidance_scale == 0:
+        raise SystemExit(f"--direction with {guidance_option} 0: the direction enters through the text row of the CFG pair, which a guidance "
+                         "of 0 does not read" + (" (or sample with --no_cfg)" if hasattr(a, "no_cfg") else ""))
     return specs
+
+
+def direction_set(a, specs, encode, cfg, xl: bool) -> dict:
+    """The directions= / direction_quantile= / direction_momentum= of a run, from direction_specs' pairs ({}: there are none).
+    encode(text) -> (ctx (1, 77, D), pooled (1, P) or None).  --synthetic: the direction rows are draws of their own (seed + 1), so
+    the prompt rows' draws are what they are without the options."""
+    if not specs:
+        return {}
+    from .directions import Direction, DirectionSet
+    if a.synthetic:
+        gd = torch.Generator().manual_seed(a.seed + 1)
+
+        def encode(text):
+            return (torch.randn(1, 77, cfg.cross_attention_dim, generator=gd), torch.randn(1, cfg.pooled_dim, generator=gd) if xl else None)
+    pairs = [(encode(pos), encode(neg), eta, sign) for pos, neg, eta, sign in specs]
+    steer = dict(directions=DirectionSet([Direction(cp, cn, pp, pn, eta=eta, sign=sign) for (cp, pp), (cn, pn), eta, sign in pairs]),
+                 direction_quantile=a.direction_quantile or 0.0)
+    momentum = direction_momentum(a)
+    if momentum is not None:
+        steer["direction_momentum"] = momentum
+    return steer
 
 
 def sampling_grid(a) -> list:
@@ -229,12 +279,13 @@ def shares_prefix(a, scales) -> bool:
 
 def traced_sweep(a, smp, scales, ctx, pooled, noise, prompt, tokenizer, suffix="", **steer):
     """One seed over its scale-0 trace: with mask options the mask is derived from the trace once and every scale is blended against
-    it; scale 0 is the trace's own image.  steer: directions= / direction_quantile= of the other scales.  Yields (scale, uint8 image
+    it; scale 0 is the trace's own image.  steer: directions= / direction_quantile= / direction_momentum= of the other scales.  Yields (scale, uint8 image
     [H][W][3] on the host)."""
     from .edit import mask_from_args
     from .vae import VaeDecoder
     trace = smp.base_trace(ctx, noise, a.ddim_steps, a.guidance_scale, pooled, None, a.start_noise)
-    mask = mask_from_args(a, smp, trace, a.res, prompt, tokenizer, suffix) if masked(a) else None
+    foot = {k: v for k, v in steer.items() if k != "direction_momentum"}          # --auto_mask: the directions' footprint
+    mask = mask_from_args(a, smp, trace, a.res, prompt, tokenizer, suffix, **foot) if masked(a) else None
     for s in scales:
         lat = trace.final if s == 0.0 else smp.sample_latents(ctx, noise, scale=s, start_noise=a.start_noise, ddim_steps=a.ddim_steps,
                                                               guidance_scale=a.guidance_scale, pooled=pooled, mask=mask, trace=trace, **steer)
@@ -305,10 +356,7 @@ def main(argv=None):
         pooled = torch.randn(2, eng.cfg.pooled_dim, generator=g) if xl else None
         if a.no_cfg:         # the text row of the same draw
             ctx, pooled = ctx[1:], pooled[1:] if xl else None
-        gd = torch.Generator().manual_seed(a.seed + 1)          # the direction rows: draws of their own, the prompt rows' are unchanged
-
-        def encode(text):
-            return (torch.randn(1, 77, eng.cfg.cross_attention_dim, generator=gd), torch.randn(1, eng.cfg.pooled_dim, generator=gd) if xl else None)
+        encode = None            # (direction_set draws the direction rows)
     else:
         if not a.model_path:
             raise SystemExit("--model_path (diffusers-format directory) or --synthetic is required")
@@ -327,12 +375,7 @@ def main(argv=None):
             tokenizer = tok
             ctx, pooled = torch.cat([model_util.encode_prompts(tok, enc, [s]) for s in prompts(a.prompt)]), None
             encode = lambda text: (model_util.encode_prompts(tok, enc, [text]), None)
-    steer = {}
-    if specs:
-        from .directions import Direction, DirectionSet
-        pairs = [(encode(pos), encode(neg), eta, sign) for pos, neg, eta, sign in specs]
-        steer = dict(directions=DirectionSet([Direction(cp, cn, pp, pn, eta=eta, sign=sign) for (cp, pp), (cn, pn), eta, sign in pairs]),
-                     direction_quantile=a.direction_quantile or 0.0)
+    steer = direction_set(a, specs, encode, eng.cfg, xl)
     store = sliders = None
     swept = torch.load(a.lora_weight, map_location="cpu") if a.lora_weight else None
     if a.compose or (swept is not None and slider_rank(swept) != 4):

@@ -186,6 +186,7 @@ _HOST_FNS = {
     "slh_latent_blend": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
     "slh_direction_threshold": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
     "slh_eps_direction": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
+    "slh_eps_direction_momentum": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
 }
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
@@ -467,7 +468,7 @@ def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int
     check(load().slh_latent_blend(ptrs, dims, coef, c_vp(stream)), "slh_latent_blend")
 
 
-MAX_DIRECTIONS = 3          # prompt pairs per slh_direction_threshold / slh_eps_direction call
+MAX_DIRECTIONS = 3          # prompt pairs per slh_direction_threshold / slh_eps_direction[_momentum] call
 
 
 def _direction_rows(what: str, pos, neg):
@@ -502,6 +503,26 @@ def eps_direction(stream: int, *, t: int, out: int, pos, neg, c, nb: int, chw: i
     dims = (c_i32 * 4)(nb, chw, hw, K)
     coef = (c_f32 * 3)(*(c + (0.0,) * (MAX_DIRECTIONS - K)))
     check(load().slh_eps_direction(ptrs, dims, coef, c_vp(stream)), "slh_eps_direction")
+
+
+def eps_direction_momentum(stream: int, *, t: int, out: int, pos, neg, c, mom_in: int, mom_out: int, s_m: float, beta: float, nb: int,
+                           chw: int, hw: int, thr: int = 0):
+    """slh_eps_direction_momentum (include/sliders_hip.h): slh_eps_direction with the momentum state nu (fp32 [nb][chw]) read from mom_in:
+    out = rne_bf16(t + sum_k c[k] keep_k d_k + s_m nu), mom_out = beta nu + (1 - beta) (sum_k c[k] keep_k d_k + s_m nu).  mom_out may be
+    mom_in.  1 - beta is formed here in double and rounded once to fp32, as the kernel reads it; s_m == 0 is refused (eps_direction)."""
+    pos, neg, K = _direction_rows("slh_eps_direction_momentum", pos, neg)
+    c = tuple(float(v) for v in c)
+    if len(c) != K:
+        raise SlidersHipError(f"slh_eps_direction_momentum: {len(c)} coefficients for {K} directions")
+    ptrs = (c_vp * 11)(t, out, *pos, *neg, thr, mom_in, mom_out)
+    dims = (c_i32 * 4)(nb, chw, hw, K)
+    coef = (c_f32 * 6)(*(c + (0.0,) * (MAX_DIRECTIONS - K)), s_m, beta, one_minus(beta))
+    check(load().slh_eps_direction_momentum(ptrs, dims, coef, c_vp(stream)), "slh_eps_direction_momentum")
+
+
+def one_minus(beta: float) -> float:
+    """omb of slh_eps_direction_momentum: 1 - beta in double (beta as given, not its fp32 rounding); ctypes rounds it once to fp32"""
+    return 1.0 - float(beta)
 
 
 _GRAPHS_ON = os.environ.get("SLIDERS_HIPGRAPH", "1") != "0"

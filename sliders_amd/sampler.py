@@ -20,14 +20,14 @@ from __future__ import annotations
 from contextlib import contextmanager
 from dataclasses import dataclass
 from itertools import count
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import lib
 from . import schedulers
 from .ddim import DDIMSchedule
-from .directions import DirectionGuide, DirectionSet
+from .directions import DirectionGuide, DirectionSet, check_momentum
 from .lora_store import LoraStore
 from .merge import SliderSet, WeightMerger
 from .passes import Pass
@@ -122,7 +122,7 @@ class SliderSampler:
                        ddim_steps: int = 50, guidance_scale: float = 7.5, pooled: Optional[torch.Tensor] = None,
                        time_ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                        trace: Optional[SampleTrace] = None, share_prefix: bool = True, directions: Optional[DirectionSet] = None,
-                       direction_quantile: float = 0.0) -> torch.Tensor:
+                       direction_quantile: float = 0.0, direction_momentum: Optional[Tuple[float, float]] = None) -> torch.Tensor:
         """ctx: (2*bs, 77, D) = cat([unconditional, text]); noise: (bs, 4, h, w) UNIT noise (it is multiplied by the
         scheduler's init_noise_sigma here, generate_images_sd1.py:165); returns the final latents (bs, 4, h, w) bf16.
         LoRA multiplier per step: 0 while t > start_noise, `scale` after.
@@ -141,7 +141,9 @@ class SliderSampler:
         positive and unconditional prompt (the wide plan, 2 more row blocks per pair), slh_eps_direction adds the scaled differences to
         the text row and the step reads that row.  direction_quantile q in [0, 1): only the largest 1 - q of each latent channel's
         differences act (slh_direction_threshold).  Steps above start_noise, and a call whose coefficients are all zero, run plain
-        sampling's launches on the plain plan.  store= / sliders= act on every row of the pass."""
+        sampling's launches on the plain plan.  store= / sliders= act on every row of the pass.
+        direction_momentum = (s_m, beta): SEGA's momentum on the directions' guidance (slh_eps_direction_momentum; the state is zero at
+        the first live step of this call); None or s_m = 0: none, the launches above."""
         eng = self.eng
         bs, _, h, w = noise.shape
         if ctx.shape[0] not in (bs, 2 * bs):
@@ -164,9 +166,13 @@ class SliderSampler:
         guide = None
         if directions is not None:
             DirectionSet.n_keep(h * w, direction_quantile)          # (an argument error, whether or not the directions act)
+            check_momentum(direction_momentum)
             coef = directions.coefficients(scale, guidance_scale, single)
             if any(c != 0.0 for c in coef):
-                guide = DirectionGuide(eng, directions, coef, direction_quantile, mode, bs, h, w, single, ctx, pooled, time_ids, start_noise)
+                guide = DirectionGuide(eng, directions, coef, direction_quantile, mode, bs, h, w, single, ctx, pooled, time_ids, start_noise,
+                                       momentum=direction_momentum)
+        elif direction_momentum is not None:
+            raise ValueError("sample_latents: direction_momentum without directions")
         p = eng.plan(ctx.shape[0], h, w, mode)
         drv = Pass(eng, p)
         drv.load_cond(ctx, pooled, time_ids)
@@ -405,12 +411,16 @@ class SliderSampler:
         drv.load_cond(src.ctx, src.pooled, src.time_ids)
         return drv
 
-    def _footprint(self, src, scale: float, start_noise, draws: int, t_min: int) -> torch.Tensor:
+    def _footprint(self, src, scale: float, start_noise, draws: int, t_min: int, directions: Optional[DirectionSet] = None,
+                   direction_quantile: float = 0.0, guidance: Optional[float] = None) -> torch.Tensor:
         from .edit import footprint_draws, footprint_mean          # (edit imports this module)
         ts = src.timesteps
         idx = footprint_draws(ts, start_noise, draws, t_min)
         dev = self.eng.device
         bs, ch, h, w = src.unet_input(0).shape
+        if directions is not None:
+            return footprint_mean(self._direction_footprint(src, idx, scale, start_noise, directions, direction_quantile,
+                                                            src.guidance if guidance is None else guidance))
         drv = self._source_pass(src)
         io = drv.io
         single = src.ctx.shape[0] == bs          # one epsilon row per sample: both "halves" are it and the guidance is not read
@@ -434,6 +444,30 @@ class SliderSampler:
                 lib.call(lib.OP_EPS_ABSDIFF, d, s)
         return footprint_mean(A)
 
+    def _direction_footprint(self, src, idx, scale: float, start_noise, directions: DirectionSet, quantile: float, guidance: float) -> torch.Tensor:
+        """A [len(idx)][bs][h][w]: per draw ONE wide pass (the rows of a direction step at this scale and guidance), the guided text row
+        t' of DirectionGuide.guide, and slh_eps_absdiff of the pair (u, t') against the pair (u, t) - sum_c |g (t' - t)|, what the step
+        would see differently.  No momentum: a draw is not a chain."""
+        eng, ts = self.eng, src.timesteps
+        bs, ch, h, w = src.unet_input(0).shape
+        single = src.ctx.shape[0] == bs
+        DirectionSet.n_keep(h * w, quantile)
+        guide = DirectionGuide(eng, directions, directions.coefficients(scale, guidance, single), quantile,
+                               "on" if self.store is not None else "off", bs, h, w, single, src.ctx, src.pooled, src.time_ids, start_noise)
+        drv = guide.enter()
+        A = torch.empty((len(idx), bs, h, w), dtype=torch.float32, device=eng.device)
+        s = torch.cuda.current_stream().cuda_stream
+        with self.slider_session(scale, start_noise, zero_merges=False) as gate:
+            for n, i in enumerate(idx):
+                drv.load_latents(src.unet_input(i))
+                drv.run(ts[i], gate(ts[i], n == 0, scale), s)
+                guided, text = guide.guide(s), guide.block("eps", guide.base - 1)
+                u = text if single else drv.io["eps"].ptr          # single branch: both "halves" are the one row, the guidance is not read
+                d = lib.EpsAbsdiffDesc(eps_a=guided if single else u, eps_a_text=guided, eps_b=u, eps_b_text=text, out=A[n].data_ptr(), nb=bs,
+                                       chw=ch * h * w, hw=h * w, guidance=0.0 if single else float(guidance))
+                lib.call(lib.OP_EPS_ABSDIFF, d, s)
+        return A
+
     def _word_map(self, src, tokens, weights, draws: int, max_factor: int) -> torch.Tensor:
         from .edit import footprint_draws, key_weights, level_mean
         ts = src.timesteps
@@ -455,12 +489,14 @@ class SliderSampler:
         return total / float(len(idx))
 
     @torch.no_grad()
-    def footprint(self, trace: SampleTrace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200) -> torch.Tensor:
+    def footprint(self, trace: SampleTrace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200,
+                  directions: Optional[DirectionSet] = None, direction_quantile: float = 0.0, guidance_scale: Optional[float] = None) -> torch.Tensor:
         """Where the slider acts on the image of this trace: SliderEditor.footprint's map F [bs][h][w] (slh_eps_absdiff between the slider
         at `scale` and the slider off, over `draws` noise levels with t_min <= t <= start_noise), with the scale-0 chain's own UNet
-        inputs, conditioning and guidance in place of an inversion's.  edit.footprint_mask turns it into a mask."""
+        inputs, conditioning and guidance in place of an inversion's.  edit.footprint_mask turns it into a mask.
+        directions: where the prompt directions act instead (SliderEditor.footprint), len(draws) wide passes."""
         self._check_localised("footprint")
-        return self._footprint(trace, scale, start_noise, draws, t_min)
+        return self._footprint(trace, scale, start_noise, draws, t_min, directions, direction_quantile, guidance_scale)
 
     @torch.no_grad()
     def word_map(self, trace: SampleTrace, tokens: Optional[Sequence[int]] = None, weights: Optional[torch.Tensor] = None, draws: int = 8,
