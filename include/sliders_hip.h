@@ -789,17 +789,23 @@ typedef struct slh_sgemm_desc {
     int32_t ldx, ldw, ldr, ldc;
     int32_t M, N, K;
     int32_t mode;           /* 0 dense, 1 implicit 3x3 (K = 9*cin) */
-    int32_t cin, batch, hs, ws, ho, wo, stride, pad;   /* pad 1: symmetric; pad 0 with stride 2: zero pad right/bottom (Downsample2D(padding=0)) */
+    int32_t cin, batch, hs, ws, ho, wo, stride, pad;   /* stride 1 | 2; pad 1: one zero row / column on every side; pad 0: one below
+                               and to the right only (Downsample2D(padding=0) with stride 2).  The output size is checked:
+                               ho = (he + pad - 2) / stride + 1 with he = hs (2*hs with upsample), wo likewise; M = batch*ho*wo */
     int32_t bias_per_row;
     float alpha;            /* C = alpha * (X W^T) + bias + residual */
-    int32_t upsample;       /* conv: 1 = the source is read through a nearest-2x upsample (Upsample2D), ho = 2*hs */
+    int32_t upsample;       /* conv, stride 1 only: 1 = the source is read through a nearest-2x upsample (Upsample2D), ho = 2*hs
+                               with pad 1.  Must be 0 in mode 0 */
     int32_t split_bf16;     /* 0: exact fp32 products (v_mfma_f32_32x32x2_f32).  1: every operand split into two bf16 halves,
                                x.w ~= hi.hi + hi.lo + lo.hi on the bf16 matrix pipe with fp32 accumulation (16 mantissa bits per
-                               operand, ~5x fewer matrix cycles); needs K % 32 == 0 (and Cin % 32 == 0), else exact.  Bits 1-3 are
-                               profiling ablations (scripts/probe_sgemm.py): 2 skip the LDS staging, 4 skip the MFMAs, 8 skip the
-                               global loads after the prologue */
+                               operand, ~5x fewer matrix cycles); needs K % 32 == 0 (and Cin % 32 == 0), else exact.  Any other
+                               value is refused */
 } slh_sgemm_desc;
 int slh_sgemm(const slh_sgemm_desc* d, slh_stream_t stream);
+/* the kernel form slh_sgemm would launch for d (its own selection runs, nothing is launched, no device needed); negative, with
+ * slh_last_error set, for a descriptor slh_sgemm refuses */
+enum { SLH_SGEMM_EXACT = 0, SLH_SGEMM_SPLIT64 = 1, SLH_SGEMM_SPLIT128 = 2 };   /* sgemm_kernel, sgemm_bf16x3_kernel<64>, <128> */
+int slh_sgemm_form(const slh_sgemm_desc* d);
 
 typedef struct slh_gn32_desc {
     const void* x; const void* gamma; const void* beta;   /* fp32 */

@@ -8,7 +8,7 @@
 //   slh_sgemm         every 3x3 / 1x1 convolution and Linear of the encoder as ONE fp32 implicit-GEMM kernel on the
 //                     exact-fp32 matrix instruction v_mfma_f32_32x32x2_f32 (157 TFLOP/s peak = the fp32 vector rate; a
 //                     VALU kernel reaches about a third of it), pixel-major fp32 activations [B*H*W][C]
-//   slh_gn32_*        GroupNorm(32, eps 1e-6) (+SiLU) in fp32, statistics by fp32 atomics like the bf16 kernels
+//   slh_gn32_*        GroupNorm(32, eps 1e-6) (+SiLU) in fp32, statistics by the fixed-order two-level reduction of the bf16 kernels
 //   slh_softmax32     row softmax of the 4096 x 4096 mid-block attention scores (one head of 512 channels)
 //   slh_vae_conv_in   3 -> 128 channels 3x3 (K = 27 is not a GEMM)
 //   slh_vae_moments   conv_out 512 -> 8 (3x3) fused with quant_conv 8 -> 8 (1x1): one wave per latent pixel
@@ -16,6 +16,7 @@
 // The encoder runs twice per image-slider iteration (~1.1 TFLOP per 512x512 image): far from the hot loop's cost,
 // so these kernels are written for exact fp32 arithmetic first and MFMA-bound simplicity second.
 #include "common.h"
+#include <string.h>
 #include <type_traits>
 #include "../../include/sliders_hip.h"
 
@@ -312,13 +313,12 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    if (d.split_bf16 & 4) { asm volatile("" ::"v"(wl[j]), "v"(xh[i]), "v"(wh[j]), "v"(xl[i])); continue; }
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[j], xh[i], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[j], xl[i], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[j], xh[i], acc[i][j], 0, 0, 0);
                 }
         }
-        if (k + 1 < nk && !(d.split_bf16 & 2)) store_stage(next_c, cur ^ 1);      // the other buffer: last read before the previous barrier
+        if (k + 1 < nk) store_stage(next_c, cur ^ 1);      // the other buffer: last read before the previous barrier
         __syncthreads();
         cur ^= 1;
     };
@@ -563,29 +563,64 @@ extern "C" int slh_vae_post_quant(const slh_vae_conv_desc* d, slh_stream_t strea
     return 0;
 }
 
+// The one place that decides which kernel runs a descriptor: slh_sgemm launches what this returns and slh_sgemm_form reports it
+// through the same launch statements.  Split form: only where every K step of 32 lies inside one tap (K, Cin multiples of 32), else the
+// exact kernel; 128-row tiles from 256 of them on (a full round of the chip), 64-row tiles below (the 64 x 64-pixel layers).
+struct sgemm_choice { int form, grid; };
+static sgemm_choice sgemm_choose(const slh_sgemm_desc* d) {
+    const int tiles_n = (d->N + SBN - 1) / SBN;
+    const int tiles = ((d->M + SBM - 1) / SBM) * tiles_n;
+    if (!(d->split_bf16 == 1 && d->K % TBK == 0 && (d->mode == 0 || d->cin % TBK == 0))) return {SLH_SGEMM_EXACT, tiles};
+    if (tiles >= 256) return {SLH_SGEMM_SPLIT128, tiles};
+    return {SLH_SGEMM_SPLIT64, ((d->M + 63) / 64) * tiles_n};
+}
+
 extern "C" int slh_sgemm(const slh_sgemm_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->x && d->w && d->c, "slh_sgemm: null pointer");
     SLH_CHECK(d->M > 0 && d->N > 0 && d->K > 0 && d->K % 16 == 0 && d->N % 4 == 0, "slh_sgemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
     SLH_CHECK(d->ldx % 4 == 0 && d->ldw % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0), "slh_sgemm: leading dims");
+    SLH_CHECK(d->split_bf16 == 0 || d->split_bf16 == 1, "slh_sgemm: split_bf16 = %d (0: exact products, 1: bf16 hi/lo split)", d->split_bf16);
     if (d->mode == 1) {
         SLH_CHECK(d->cin > 0 && d->cin % 16 == 0 && d->K == 9 * d->cin, "slh_sgemm: conv needs Cin %% 16 == 0 and K = 9*Cin");
         SLH_CHECK((d->stride == 1 || d->stride == 2) && (d->pad == 0 || d->pad == 1), "slh_sgemm: stride / pad");
+        SLH_CHECK(d->upsample == 0 || (d->upsample == 1 && d->stride == 1), "slh_sgemm: upsample = %d with stride %d (0, or 1 with stride 1)",
+                  d->upsample, d->stride);
+        // the window of output pixel o covers rows o*stride - pad .. + 2 of the (upsampled) source, which is padded by `pad` rows above
+        // and by one row below (pad 0: Downsample2D's (0, 1, 0, 1)): the kernel reads what lies outside as zero and trusts ho / wo
+        const int he = d->hs << d->upsample, we = d->ws << d->upsample;
+        SLH_CHECK(d->batch > 0 && d->hs > 0 && d->ws > 0 && he + d->pad >= 2 && we + d->pad >= 2 &&
+                      d->ho == (he + d->pad - 2) / d->stride + 1 && d->wo == (we + d->pad - 2) / d->stride + 1,
+                  "slh_sgemm: conv output %d x %d does not follow from source %d x %d, stride %d, pad %d, upsample %d", d->ho, d->wo, d->hs,
+                  d->ws, d->stride, d->pad, d->upsample);
         SLH_CHECK(d->M == d->batch * d->ho * d->wo, "slh_sgemm: conv M mismatch");
     } else {
         SLH_CHECK(d->mode == 0, "slh_sgemm: bad mode");
+        SLH_CHECK(d->upsample == 0, "slh_sgemm: upsample is a conv-mode read");
     }
-    const int tiles = ((d->M + SBM - 1) / SBM) * ((d->N + SBN - 1) / SBN);
-    if ((d->split_bf16 & 1) && d->K % TBK == 0 && (d->mode == 0 || d->cin % TBK == 0)) {
-        if (tiles >= 256)
-            hipLaunchKernelGGL(sgemm_bf16x3_kernel<128>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, *d);
-        else        // few 128-row tiles (the 64 x 64-pixel layers): 64-row tiles fill the chip
-            hipLaunchKernelGGL(sgemm_bf16x3_kernel<64>, dim3(((d->M + 63) / 64) * ((d->N + SBN - 1) / SBN)), dim3(256), 0,
-                               (hipStream_t)stream, *d);
-    } else {
-        hipLaunchKernelGGL(sgemm_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, *d);
+    const sgemm_choice f = sgemm_choose(d);
+    hipStream_t s = (hipStream_t)stream;
+    switch (f.form) {
+        case SLH_SGEMM_SPLIT128: slh_launch<sgemm_bf16x3_kernel<128>>(f.grid, 256, s, *d, "split<%d>", 128); break;
+        case SLH_SGEMM_SPLIT64: slh_launch<sgemm_bf16x3_kernel<64>>(f.grid, 256, s, *d, "split<%d>", 64); break;
+        default: slh_launch<sgemm_kernel>(f.grid, 256, s, *d, "exact"); break;
     }
     SLH_LAUNCH_CHECK("slh_sgemm");
     return 0;
+}
+
+// the form slh_sgemm would launch for d: the whole of slh_sgemm runs - descriptor checks, sgemm_choose - with the launch replaced by a
+// record of the selected kernel.  No device needed, nothing launched.
+extern "C" int slh_sgemm_form(const slh_sgemm_desc* d) {
+    char buf[32];
+    slh_name_sink_set(buf, sizeof(buf));
+    const int rc = slh_sgemm(d, nullptr);
+    slh_name_sink_set(nullptr, 0);
+    if (rc != 0) return rc;
+    if (!strcmp(buf, "exact")) return SLH_SGEMM_EXACT;
+    if (!strcmp(buf, "split<64>")) return SLH_SGEMM_SPLIT64;
+    if (!strcmp(buf, "split<128>")) return SLH_SGEMM_SPLIT128;
+    slh_set_error("slh_sgemm_form: internal: no launch site recorded a form");
+    return -3;
 }
 
 static int gn32_check(const slh_gn32_desc* d, const char* who) {

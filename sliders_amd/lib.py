@@ -174,7 +174,7 @@ _HOST_FNS = {
     "slh_gemm_kernel_name": (c_i32, [_P(GemmDesc), _str, c_i32]),
     "slh_gemm_launch_query": (c_i32, [_P(GemmDesc), _str, c_i32, _P(c_i32), _P(c_i32), _P(C.c_uint64)]),
     "slh_gemm_tile_ok": (c_i32, [_P(GemmDesc)]), "slh_gemm_ln_chunk_cols": (c_i32, [_P(GemmDesc)]),
-    "slh_skinny_kernel_name": (c_i32, [_P(SkinnyDesc), _str, c_i32]),
+    "slh_skinny_kernel_name": (c_i32, [_P(SkinnyDesc), _str, c_i32]), "slh_sgemm_form": (c_i32, [_P(SgemmDesc)]),
     "slh_attn_fwd_carries_touch": (c_i32, [_P(AttnDesc)]), "slh_attn_fwd_kernel_name": (c_i32, [_P(AttnDesc), _str, c_i32]),
     "slh_attn_bwd_kernel_names": (c_i32, [_P(AttnBwdDesc), _str, _str, c_i32]),
     "slh_gn_row_blocks": (c_i32, [c_i32, c_i32, c_i32]), "slh_gn_clusters": (c_i32, [c_i32]), "slh_gn32_row_blocks": (c_i32, [c_i32]),
@@ -396,6 +396,19 @@ def skinny_kernel_name(desc) -> str:
     """slh_skinny_kernel_name: the instantiation slh_skinny would launch for this descriptor ('skinny<12,16>': accumulator rows, lanes
     per output row), named by the selection function slh_skinny launches through; raises for a descriptor slh_skinny refuses."""
     return _kernel_names("slh_skinny_kernel_name", desc, 64)[0]
+
+
+SGEMM_FORMS = ("exact", "split<64>", "split<128>")      # SLH_SGEMM_EXACT / _SPLIT64 / _SPLIT128
+
+
+def sgemm_form(desc) -> str:
+    """slh_sgemm_form: the kernel slh_sgemm would launch for this descriptor - 'exact' (sgemm_kernel), 'split<64>' or 'split<128>'
+    (sgemm_bf16x3_kernel<TM>) - as the selection function slh_sgemm launches through decides it; raises for a descriptor slh_sgemm
+    refuses.  Shape fields only, no device needed."""
+    rc = load().slh_sgemm_form(C.byref(desc))
+    if not 0 <= rc < len(SGEMM_FORMS):
+        raise SlidersHipError(f"slh_sgemm_form failed ({rc}): {last_error()}")
+    return SGEMM_FORMS[rc]
 
 
 def attn_carries_touch(desc) -> bool:

@@ -1863,3 +1863,222 @@ def test_lora_matrix_is_not_hollow():
     assert {lm.has_atomics(c) for c in cs} == {True, False}
     for key, c in lm.mutant_cases().items():
         assert c in lm.CASES, key
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fp32 image-path kernels element by element (tests/vae_matrix.py, tests/test_vae_matrix_gpu.py, docs/VAE_MATRIX.md)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _vae_check(vm, c, mutant=None):
+    """{label: (worst ratio, b) or the failure text} of the stand-in of case c (mutant: with one defect) against reference and bound"""
+    from tests.util import check_elementwise
+    K = vm.KINDS[c.kind]
+    L = K["inputs"](c, torch.device("cpu"), 1)
+    got = K["standin"](c, L, mutant=mutant)
+    out = {}
+    for label, (buf, r, bound) in K["reference"](c, L, got).items():
+        try:
+            if bound is None:
+                assert torch.equal(got[buf], r), f"{c.id} [{label}]: not bit-exact"
+                out[label] = (0.0, None)
+            else:
+                w, _, b = check_elementwise(f"{c.id} [{label}]", got[buf], r, bound)
+                out[label] = (w, b)
+        except AssertionError as e:
+            out[label] = str(e)
+    return out
+
+
+def test_sgemm_form_comes_from_the_library_and_bad_descriptors_are_refused():
+    """slh_sgemm_form runs slh_sgemm's own checks and selection (no device, fake pointers).  Refused on the host, before any launch:
+    split_bf16 outside {0, 1} (the former profiling bits), upsample with stride 2 or in dense mode, and a conv output size that does not
+    follow from the source, stride, pad and upsample.  The encoder's and decoder's calls pass."""
+    one = 0x1000
+
+    def conv(**kw):
+        base = dict(x=one, w=one, c=one, ldx=32, ldw=288, ldc=8, M=2 * 8 * 6, N=8, K=288, mode=1, cin=32, batch=2, hs=8, ws=6, ho=8, wo=6, stride=1,
+                    pad=1, alpha=1.0, split_bf16=1)
+        base.update(kw)
+        return lib.SgemmDesc(**base)
+
+    def dense(**kw):
+        base = dict(x=one, w=one, c=one, ldx=64, ldw=64, ldc=8, M=100, N=8, K=64, mode=0, alpha=1.0, split_bf16=1)
+        base.update(kw)
+        return lib.SgemmDesc(**base)
+
+    assert lib.sgemm_form(conv()) == "split<64>" and lib.sgemm_form(dense()) == "split<64>" and lib.sgemm_form(dense(split_bf16=0)) == "exact"
+    assert lib.sgemm_form(dense(M=32768)) == "split<128>"
+    # what sliders_amd/vae.py records: 3 x 3 pad 1, the downsampler (stride 2, pad 0, (h - 2) // 2 + 1), the upsampler (ho = 2 hs)
+    for h in (64, 33, 8):
+        assert lib.sgemm_form(conv(hs=h, ws=h, ho=h, wo=h, M=2 * h * h))
+        ho = (h - 2) // 2 + 1
+        assert lib.sgemm_form(conv(hs=h, ws=h, ho=ho, wo=ho, M=2 * ho * ho, stride=2, pad=0))
+        assert lib.sgemm_form(conv(hs=h, ws=h, ho=2 * h, wo=2 * h, M=8 * h * h, upsample=1))
+    bad = {
+        "split_bf16": [dense(split_bf16=3), dense(split_bf16=5), dense(split_bf16=9), dense(split_bf16=2), conv(split_bf16=-1)],
+        "upsample": [conv(upsample=1, stride=2, ho=8, wo=6), conv(upsample=2, ho=16, wo=12, M=2 * 16 * 12), dense(upsample=1)],
+        "does not follow": [conv(ho=7, wo=6, M=2 * 7 * 6), conv(upsample=1), conv(stride=2, pad=0, ho=8, wo=6), conv(stride=2, pad=0, ho=3, wo=3, M=18),
+                            conv(pad=0), conv(hs=1, ws=1, ho=1, wo=1, M=2, pad=0), conv(batch=0, M=0)],
+    }
+    for what, ds in bad.items():
+        for d in ds:
+            with pytest.raises(lib.SlidersHipError, match="slh_sgemm"):
+                lib.sgemm_form(d)
+            # the pointers are made up: lib.call below is safe only because slh_sgemm refuses d before any launch, which the assertion
+            # above has just established with the same checks (slh_sgemm_form runs slh_sgemm).  Keep this order.
+            if d.M > 0:
+                with pytest.raises(lib.SlidersHipError, match=what):
+                    lib.call(lib.OP_SGEMM, d, 0)
+    assert lib.sgemm_form(conv(stride=2, pad=0, ho=4, wo=3, M=24)) == "split<64>"
+
+
+def test_vae_bounds_admit_the_standins():
+    """Every case of the matrix: the stand-in - fp32 arithmetic, for the split form the explicit bf16 halves - meets every bound; the
+    evaluated dropped-product term of every split case stays below 3 * 2^-18 |alpha| sum |x||w| (the figure for operands spread over
+    their binades) - the bound asks no less than that; the sample case that takes the rounding statistic has the elements for it."""
+    from tests import vae_matrix as vm
+    from tests.util import STAT_LIMIT, STAT_MIN_ABS, STAT_MIN_COUNT
+    worst, split_ratio = {}, 0.0
+    for c in vm.CASES:
+        res = _vae_check(vm, c)
+        assert all(isinstance(r, tuple) for r in res.values()), (c.id, res)
+        assert all(w <= 1.0 and (b is None or abs(b) <= STAT_LIMIT) for w, b in res.values())
+        for label, (w, _) in res.items():
+            f = vm.form_of(c, label)
+            worst[f] = max(worst.get(f, 0.0), w)
+        if c.kind == "sgemm" and vm.sgemm_form(c) != "exact":
+            extra, spread = vm.sgemm_split_terms(c, vm.sgemm_inputs(c, torch.device("cpu"), 1))
+            r = float((extra / spread).max())
+            assert r <= 1.0, (c.id, r)
+            split_ratio = max(split_ratio, r)
+    assert set(worst) == set(vm.FORMS)
+    for f, w in sorted(worst.items()):
+        print(f"[parity] vae stand-in {f}: worst |got - ref| / bound = {w:.3f}")
+    print(f"[parity] vae split forms: dropped-product term at most {split_ratio:.3f} x 3 * 2^-18 |alpha| sum |x||w|")
+    big = vm._find("sample", B=2, hw=2500)
+    ref = vm.sample_reference(big, vm.sample_inputs(big, torch.device("cpu"), 1))["noisy_bf16"][1]
+    assert ref.numel() == 20000 and int((ref.abs() > STAT_MIN_ABS).sum()) >= STAT_MIN_COUNT
+    res = _vae_check(vm, big)
+    assert res["noisy_bf16"][1] is not None and res["noisy_bf16 == bf16(noisy_f32)"] == (0.0, None)
+
+
+def test_vae_bounds_reject_the_mutants():
+    """Each mutant of a stand-in leaves the bound of the case vae_matrix.mutant_cases() names for it - a case of the GPU list - and the
+    honest stand-in of that same case passes.  Remarks on reach, also in docs/VAE_MATRIX.md: a split kernel that skips its last K step
+    when nk % 3 == 1 computes the same function at nk = 2, 3, 5 (shown); a conv that checks its taps against hs instead of hs << 1
+    computes the same function without upsample (shown); a softmax that sums only its first 1024 columns is the same function up to
+    cols = 1024 (shown)."""
+    from tests import vae_matrix as vm
+    cases = vm.mutant_cases()
+    assert set(cases) == {f"{k}/{m}" for k, ms in vm.MUTANTS.items() for m in ms}
+    for key, c in cases.items():
+        kind, mutant = key.split("/")
+        assert c.kind == kind and c in vm.CASES
+        good, bad = _vae_check(vm, c), _vae_check(vm, c, mutant)
+        assert all(isinstance(r, tuple) for r in good.values()), (key, good)
+        caught = [r for r in bad.values() if isinstance(r, str)]
+        assert caught, f"{key} passed every check of {c.id}: {bad}"
+        print(f"[parity] vae mutant {key} ({c.id}): caught - {caught[0][:150]}")
+    # a wrong statistic fails the statistics check, not the apply check (y is referred to the kernel's own statistics), and vice versa
+    bad = _vae_check(vm, cases["gn32/first_cluster_only"], "first_cluster_only")
+    assert isinstance(bad["stats"], str) and isinstance(bad["y"], tuple)
+    # the equivalences claimed above
+    cpu = torch.device("cpu")
+    for c in vm.CASES:
+        if c.kind == "sgemm" and vm.sgemm_form(c) != "exact" and (vm._sg_geo(c)[4] // 32) % 3 != 1 and vm._sg_geo(c)[2] < 2000:
+            L = vm.sgemm_inputs(c, cpu, 1)
+            assert torch.equal(vm.sgemm_standin(c, L)["c"], vm.sgemm_standin(c, L, "split_skips_last_step_nk_mod3_1")["c"]), c.id
+    c = vm._find("sgemm", conv=(3, 7, 5), stride=1, pad=1, up=0, split=0)
+    L = vm.sgemm_inputs(c, cpu, 1)
+    assert torch.equal(vm.sgemm_standin(c, L)["c"], vm.sgemm_standin(c, L, "upsample_bounds_hs")["c"])
+    # stride 2 / pad 0 on the odd image: no window reaches row hs (ho = 3, the last row read is 6), so the unmasked bottom tap is the same
+    # function there; and with ho == hs (stride 1 / pad 1) so is the sample offset taken from ho
+    c = vm._find("sgemm", conv=(3, 7, 5), stride=2, pad=0, cin=32, split=1)
+    L = vm.sgemm_inputs(c, cpu, 1)
+    assert torch.equal(vm.sgemm_standin(c, L)["c"], vm.sgemm_standin(c, L, "bottom_tap_unmasked_stride2")["c"])
+    c = vm._find("sgemm", conv=(3, 8, 6), stride=1, pad=1, cin=32, split=1)
+    L = vm.sgemm_inputs(c, cpu, 1)
+    assert torch.equal(vm.sgemm_standin(c, L)["c"], vm.sgemm_standin(c, L, "sample_offset_uses_ho")["c"])
+    for key in ("sgemm/sample_offset_uses_ho", "sgemm/bottom_tap_unmasked_stride2"):
+        assert vm.sgemm_form(cases[key]) == "split<64>" and cases[key].conv[0] == 3
+    c = vm._find("softmax", cols=1024, cls="n")
+    L = vm.softmax_inputs(c, cpu, 1)
+    assert torch.equal(vm.softmax_standin(c, L)["x"], vm.softmax_standin(c, L, "sum_first_1024")["x"])
+
+
+def test_vae_matrix_is_not_hollow():
+    """Every form has a case; every edge the matrix claims is in the list, asked of the library where the library decides it."""
+    from tests import vae_matrix as vm
+    ids = [c.id for c in vm.CASES]
+    assert len(ids) == len(set(ids))
+    forms = {}
+    for c in vm.CASES:
+        for label in (("stats", "y") if c.kind == "gn32" else ("",)):
+            forms.setdefault(vm.form_of(c, label), []).append(c)
+    assert set(forms) == set(vm.FORMS), set(forms) ^ set(vm.FORMS)
+    sg = [c for c in vm.CASES if c.kind == "sgemm"]
+    form, geo = vm.sgemm_form, vm._sg_geo
+    dense, conv = [c for c in sg if not c.conv], [c for c in sg if c.conv]
+    # dense: every M, N, K in both requests; the split form at nk = 1 .. 5 and 7; K = 16, 48 fall back - as the library says
+    for split in (0, 1):
+        sub = [c for c in dense if c.split == split]
+        assert {c.M for c in sub} >= {1, 63, 64, 65, 127, 128, 129, 300} and {c.N for c in sub} >= {4, 124, 128, 132, 260}
+        assert {c.K for c in sub} >= {16, 32, 48, 64, 96, 128, 160, 224}
+    assert all(form(c) == "exact" for c in dense if c.split == 0)
+    assert {c.K // 32 for c in dense if form(c) == "split<64>"} >= {1, 2, 3, 4, 5, 7}
+    assert {c.K for c in dense if c.split == 1 and form(c) == "exact"} == {16, 48}, "the K % 32 edge moved: move the cases with it"
+    assert all(form(c) != "exact" for c in dense if c.split == 1 and c.K % 32 == 0)
+    for f in ("exact", "split<64>"):
+        sub = [c for c in dense if form(c) == f]
+        assert {c.alpha for c in sub} == {1.0, 0.37} and {c.bias for c in sub} == {0, 1, 2} and {c.res for c in sub} == {0, 1}, f
+        assert all(any(c.pads[i] for c in sub) for i in range(4)) and any(c.res and c.pads[2] for c in sub), f
+    # conv: images, stride / pad pairs, cin, Cout, batch, residual; cin = 16, 48 fall back - as the library says
+    pairs = {(c.stride, c.pad) for c in conv if not c.up}
+    assert pairs == {(1, 1), (2, 0), (1, 0), (2, 1)}
+    for sp in pairs:
+        assert {c.conv[1:] for c in conv if (c.stride, c.pad) == sp and not c.up} >= {(7, 5), (8, 6)}, sp
+    assert {(c.stride, c.pad) for c in conv if c.conv[1:] == (1, 1) and not c.up} == {(1, 1), (2, 1)}
+    assert {c.cin for c in conv if c.split == 1 and form(c) == "exact"} == {16, 48}, "the cin % 32 edge moved: move the cases with it"
+    assert {c.cin for c in conv if form(c) == "split<64>"} >= {32, 64} and {c.cin for c in conv if c.split == 0} >= {32, 64}
+    assert {c.N for c in conv} >= {4, 132}
+    # batch and residual per kernel form (as the library reports it) and per stride / pad pair: a second sample behind the image is what
+    # shows a tap that escapes its mask or a wrong sample offset - in the split kernel's load_x as much as in the exact kernel's
+    for f in ("exact", "split<64>"):
+        for sp in pairs:
+            sub = [c for c in conv if form(c) == f and (c.stride, c.pad) == sp and not c.up]
+            assert {c.conv[0] for c in sub} >= {1, 3} and {c.res for c in sub} == {0, 1}, (f, sp)
+            assert {c.conv[1:] for c in sub if c.conv[0] == 3} >= {(7, 5), (8, 6)}, (f, sp)
+    ups = [c for c in conv if c.up]
+    assert {form(c) for c in ups} >= {"exact", "split<64>", "split<128>"} and {c.conv[1:] for c in ups} >= {(7, 5), (1, 1)}
+    assert all(c.stride == 1 and c.pad == 1 and geo(c)[5] == 2 * c.conv[1] for c in ups) and any(c.conv[0] == 3 for c in ups)
+    # the 128-row form: either side of the tile-count threshold, wherever the library puts it
+    lo, hi = vm._find("sgemm", M=32640, N=4, K=32), vm._find("sgemm", M=32763, N=4, K=32)
+    assert (form(lo), form(hi)) == ("split<64>", "split<128>"), "the 255 / 256 tile edge moved: move the cases with it"
+    big = [c for c in sg if form(c) == "split<128>"]
+    assert any(c.conv and not c.up for c in big) and any(c.up for c in big) and any(not c.conv and c.N == 132 and c.K == 96 for c in big)
+    # gn32
+    gn = [c for c in vm.CASES if c.kind == "gn32"]
+    assert {(c.C, c.groups) for c in gn} == {(32, 8), (128, 32), (256, 32), (256, 64), (512, 32), (1024, 32)}
+    for C, g in {(c.C, c.groups) for c in gn}:
+        sub = [c for c in gn if (c.C, c.groups) == (C, g)]
+        assert {c.hw for c in sub} >= {1, 63, 64, 65, 1024, 1025, 1093} and {c.B for c in sub} == {1, 3} and {c.act for c in sub} == {0, 1}, (C, g)
+        assert {c.off for c in sub} == {0.5, 300.0} and any(c.pads[0] and c.pads[1] for c in sub), (C, g)
+    clusters = lambda hw: lib.gn32_workspace(hw)[1] - 1
+    assert clusters(1024) == 1 and clusters(1025) == 2, "the one / two cluster edge moved away from 1024 / 1025: move the cases with it"
+    assert clusters(1093) == 2 and clusters(1) == 1
+    sm = [c for c in vm.CASES if c.kind == "softmax"]
+    for cls in "ns":
+        assert {(c.rows, c.cols, c.ld) for c in sm if c.cls == cls} == {(1, 4, 4), (3, 1024, 1024), (3, 1028, 1040), (5, 4096, 4096)}
+    ci = [c for c in vm.CASES if c.kind == "conv_in"]
+    assert {(c.cin, c.cout, c.geo) for c in ci} == {(a, b, g) for a in (3, 4) for b in (4, 128) for g in ((1, 1, 1), (2, 3, 5), (3, 9, 7))}
+    mo = [c for c in vm.CASES if c.kind == "moments"]
+    assert {c.C for c in mo} == {4, 128, 256, 260, 512} and {c.geo for c in mo} == {(1, 1, 1), (2, 3, 5), (3, 3, 3)}
+    assert len(mo) == 15 and any((c.geo[0] * c.geo[1] * c.geo[2]) % 4 for c in mo)
+    sa = [c for c in vm.CASES if c.kind == "sample"]
+    assert {c.hw for c in sa} == {1, 15, 300, 2500} and {c.B for c in sa} == {1, 2} and len({c.outs for c in sa}) == 7
+    L = vm.sample_inputs(sa[0].__class__("sample", B=2, hw=15), torch.device("cpu"), 1)
+    assert {float(v) for v in L["moments"][:, 4:].reshape(-1)[::5][:4]} == {-40.0, -30.0, 20.0, 25.0}
+    pq = [c for c in vm.CASES if c.kind == "post_quant"]
+    for zbf in (0, 1):
+        assert {c.hw for c in pq if c.zbf == zbf} == {1, 15, 300} and {c.B for c in pq if c.zbf == zbf} == {1, 3}
+    for key, c in vm.mutant_cases().items():
+        assert c in vm.CASES, key
