@@ -493,7 +493,7 @@ int slh_sigma_step(const void* const* ptrs, const int32_t* dims, const float* co
  * a step just produced against the latent the scale-0 chain of the same seed had after the same step, under a mask with one value per
  * latent pixel.  Never recorded in a program: no opcode, no descriptor struct; three host arrays, as slh_sigma_step.  Per element,
  * with k = keep, m = mask, fp32 throughout (bf16 inputs widen exactly), one rounding per operation, nothing contracted:
- *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          the select-then-lerp of slh_ddpm_edit_blend
+ *   out = m == 0 ? k : m == 1 ? e : k + m * (e - k)          the select-then-lerp of slh_ddpm_edit_blend (csrc/step_common.h)
  * A NaN in e does not reach a pixel with m = 0, nor a NaN in keep a pixel with m = 1.  Mask values outside [0, 1] are the caller's error.
  * ptrs[6]: 0 e        the latent the step just produced   [nb][chw]
  *          1 keep     the base chain's latent after the same step   [nb][chw]

@@ -20,12 +20,14 @@
 // 256 counts.  Integer arithmetic only, so tau and with it the kept set are exact and the same in every run; no floating-point
 // atomics, nothing waits on another workgroup.  Any hw >= 1: the loops stride over the group.
 // 16-byte accesses (eight bf16 elements per thread) where every pointer, chw and hw allow them; hw a multiple of 8 means a vector
-// never straddles a channel.  Otherwise one element per thread.
+// never straddles a channel.  Otherwise one element per thread (load_vec / store_vec, step_common.h).
 #include <cmath>
-#include "common.h"
+#include "step_common.h"
 #include "../../include/sliders_hip.h"
 
 namespace {
+
+using namespace slh_step_detail;
 
 constexpr int DIR_MAX = 3;         // prompt pairs per call
 constexpr int HIST_COPIES = 32;    // LDS counters per bin
@@ -74,6 +76,7 @@ __device__ __forceinline__ void hist_select(const int* hist, int* scan, int* res
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void direction_threshold_kernel(const direction_threshold_args d) {
+    constexpr int V = VEC ? 8 : 1;
     __shared__ int hist[256 * HIST_COPIES];
     __shared__ int scan[512];
     __shared__ int result[2];
@@ -86,19 +89,13 @@ __global__ __launch_bounds__(256) void direction_threshold_kernel(const directio
     int hi = 0, lo = 0, need = k == 0 ? d.n_keep[0] : k == 1 ? d.n_keep[1] : d.n_keep[2];
     for (int pass = 0; pass < 2; ++pass) {
         hist_clear(hist);
-        if constexpr (VEC) {
-            for (int i = threadIdx.x; i < d.hw / 8; i += 256) {
-                const bf16x8 p = ((const bf16x8*)pos)[i], n = ((const bf16x8*)neg)[i];
+        for (int i = threadIdx.x; i < d.hw / V; i += 256) {
+            float p[V], n[V];
+            load_vec<V>(pos, (long)i * V, p);
+            load_vec<V>(neg, (long)i * V, n);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned key = direction_key((float)p[e], (float)n[e]);
-                    if (pass == 0) hist_count(hist, key >> 8);
-                    else if ((int)(key >> 8) == hi) hist_count(hist, key & 255u);
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < d.hw; i += 256) {
-                const unsigned key = direction_key((float)pos[i], (float)neg[i]);
+            for (int e = 0; e < V; ++e) {
+                const unsigned key = direction_key(p[e], n[e]);
                 if (pass == 0) hist_count(hist, key >> 8);
                 else if ((int)(key >> 8) == hi) hist_count(hist, key & 255u);
             }
@@ -119,20 +116,14 @@ struct eps_direction_args {
     long n;                                                      // nb * chw
 };
 
-// acc[e] = t, then acc[e] = acc[e] + c_j * d_j over the kept terms, for the V elements from g on (thread i of the launch); SUM: g_sum[e],
-// the same products summed from +0 in the same order.  The one combine body of both kernels below.
-template <bool VEC, bool SUM>
-__device__ __forceinline__ void direction_combine(const eps_direction_args& d, const long i, const long g, float* acc, float* g_sum) {
+// acc[e] = t, then acc[e] = acc[e] + c_j * d_j over the kept terms, for the V elements from g on; SUM: g_sum[e], the same products
+// summed from +0 in the same order.  The one combine body of both kernels below.
+template <int V, bool SUM>
+__device__ __forceinline__ void direction_combine(const eps_direction_args& d, const long g, float* acc, float* g_sum) {
 #pragma clang fp contract(off)
-    constexpr int V = VEC ? 8 : 1;
     const long b = g / d.chw;
     const int ch = (int)(g - b * d.chw) / d.hw;
-    if constexpr (VEC) {
-        const bf16x8 tv = ((const bf16x8*)d.t)[i];
-        for (int e = 0; e < 8; ++e) acc[e] = (float)tv[e];
-    } else {
-        acc[0] = (float)d.t[g];
-    }
+    load_vec<V>(d.t, g, acc);
     if constexpr (SUM)
         for (int e = 0; e < V; ++e) g_sum[e] = 0.0f;
 #pragma unroll
@@ -140,13 +131,8 @@ __device__ __forceinline__ void direction_combine(const eps_direction_args& d, c
         if (j >= d.terms) break;
         const unsigned tau = d.thr ? (unsigned)d.thr[(b * d.K + d.slot[j]) * d.C + ch] : 0u;
         float p[V], m[V];
-        if constexpr (VEC) {
-            const bf16x8 pv = ((const bf16x8*)d.pos[j])[i], nv = ((const bf16x8*)d.neg[j])[i];
-            for (int e = 0; e < 8; ++e) { p[e] = (float)pv[e]; m[e] = (float)nv[e]; }
-        } else {
-            p[0] = (float)d.pos[j][g];
-            m[0] = (float)d.neg[j][g];
-        }
+        load_vec<V>(d.pos[j], g, p);
+        load_vec<V>(d.neg[j], g, m);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             const float diff = p[e] - m[e];
@@ -162,17 +148,6 @@ __device__ __forceinline__ void direction_combine(const eps_direction_args& d, c
     }
 }
 
-template <bool VEC>
-__device__ __forceinline__ void direction_store(__bf16* out, const long i, const long g, const float* acc) {
-    if constexpr (VEC) {
-        bf16x8 ov;
-        for (int e = 0; e < 8; ++e) ov[e] = (__bf16)acc[e];      // round to nearest even
-        ((bf16x8*)out)[i] = ov;
-    } else {
-        out[g] = (__bf16)acc[0];
-    }
-}
-
 // VEC: eight elements per thread, n a multiple of 8 (and hw, where thr is given)
 template <bool VEC>
 __global__ __launch_bounds__(256) void eps_direction_kernel(const eps_direction_args d) {
@@ -180,8 +155,8 @@ __global__ __launch_bounds__(256) void eps_direction_kernel(const eps_direction_
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n / V) return;
     float acc[V];
-    direction_combine<VEC, false>(d, i, i * V, acc, nullptr);
-    direction_store<VEC>(d.out, i, i * V, acc);
+    direction_combine<V, false>(d, i * V, acc, nullptr);
+    store_vec<V>(d.out, i * V, acc);
 }
 
 // slh_eps_direction_momentum: the combine above with SEGA's momentum, nu the fp32 state between two passes:
@@ -202,13 +177,8 @@ __global__ __launch_bounds__(256) void eps_direction_momentum_kernel(const eps_m
     if (i >= d.e.n / V) return;
     const long g = i * V;
     float acc[V], gm[V], nu[V];
-    if constexpr (VEC) {
-        const f32x4 lo = ((const f32x4*)d.mom_in)[2 * i], hi = ((const f32x4*)d.mom_in)[2 * i + 1];
-        for (int e = 0; e < 4; ++e) { nu[e] = lo[e]; nu[4 + e] = hi[e]; }
-    } else {
-        nu[0] = d.mom_in[g];
-    }
-    direction_combine<VEC, true>(d.e, i, g, acc, gm);
+    load_vec<V>(d.mom_in, g, nu);
+    direction_combine<V, true>(d.e, g, acc, gm);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
         const float q = d.s_m * nu[e];
@@ -218,34 +188,23 @@ __global__ __launch_bounds__(256) void eps_direction_momentum_kernel(const eps_m
         const float b = d.omb * gm[e];
         nu[e] = a + b;
     }
-    direction_store<VEC>(d.e.out, i, g, acc);
-    if constexpr (VEC) {
-        ((f32x4*)d.mom_out)[2 * i] = f32x4{nu[0], nu[1], nu[2], nu[3]};
-        ((f32x4*)d.mom_out)[2 * i + 1] = f32x4{nu[4], nu[5], nu[6], nu[7]};
-    } else {
-        d.mom_out[g] = nu[0];
-    }
+    store_vec<V>(d.e.out, g, acc);
+    store_vec<V>(d.mom_out, g, nu);
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// [a, a + na) and [b, b + nb) bytes share an address (a null b: no)
-inline bool overlaps(const void* a, long na, const void* b, long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return b && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+// the shape every entry point below takes: nb, chw, hw and K directions
+inline int direction_shape_check(const char* name, int nb, int chw, int hw, int K) {
+    if (const int rc = shape_check(name, nb, chw, hw)) return rc;
+    SLH_CHECK(K >= 1 && K <= DIR_MAX, "%s: K = %d directions (1..%d)", name, K, DIR_MAX);
+    return 0;
 }
 
 }  // namespace
 
-#define DIR_SHAPE_CHECKS(name)                                                                                                  \
-    SLH_CHECK(nb >= 1 && chw >= 1 && hw >= 1, name ": nb = %d, chw = %d, hw = %d", nb, chw, hw);                                \
-    SLH_CHECK(chw % hw == 0, name ": chw = %d is not a multiple of hw = %d", chw, hw);                                          \
-    SLH_CHECK(K >= 1 && K <= DIR_MAX, name ": K = %d directions (1..%d)", K, DIR_MAX)
-
 extern "C" int slh_direction_threshold(const void* const* ptrs, const int32_t* dims, const float*, slh_stream_t stream) {
     SLH_CHECK(ptrs && dims, "slh_direction_threshold: null ptrs / dims");
     const int nb = dims[0], chw = dims[1], hw = dims[2], K = dims[3];
-    DIR_SHAPE_CHECKS("slh_direction_threshold");
+    if (const int rc = direction_shape_check("slh_direction_threshold", nb, chw, hw, K)) return rc;
     direction_threshold_args d;
     d.thr = (int*)ptrs[6];
     SLH_CHECK(d.thr, "slh_direction_threshold: null thr");
@@ -279,9 +238,7 @@ extern "C" int slh_direction_threshold(const void* const* ptrs, const int32_t* d
 static int direction_fill(const char* name, const void* const* ptrs, const int32_t* dims, const float* coef, eps_direction_args& d, bool& vec) {
     SLH_CHECK(ptrs && dims && coef, "%s: null ptrs / dims / coef", name);
     const int nb = dims[0], chw = dims[1], hw = dims[2], K = dims[3];
-    SLH_CHECK(nb >= 1 && chw >= 1 && hw >= 1, "%s: nb = %d, chw = %d, hw = %d", name, nb, chw, hw);
-    SLH_CHECK(chw % hw == 0, "%s: chw = %d is not a multiple of hw = %d", name, chw, hw);
-    SLH_CHECK(K >= 1 && K <= DIR_MAX, "%s: K = %d directions (1..%d)", name, K, DIR_MAX);
+    if (const int rc = direction_shape_check(name, nb, chw, hw, K)) return rc;
     d.t = (const __bf16*)ptrs[0];
     d.out = (__bf16*)ptrs[1];
     d.thr = (const int*)ptrs[8];
@@ -320,9 +277,8 @@ extern "C" int slh_eps_direction(const void* const* ptrs, const int32_t* dims, c
     eps_direction_args d;
     bool vec;
     if (const int rc = direction_fill("slh_eps_direction", ptrs, dims, coef, d, vec)) return rc;
-    const long threads = vec ? d.n / 8 : d.n;
-    SLH_CHECK((threads + 255) / 256 < (1L << 31), "slh_eps_direction: nb * chw = %ld is too large for one launch", d.n);
-    const dim3 grid((unsigned)((threads + 255) / 256));
+    dim3 grid;
+    if (const int rc = launch_grid("slh_eps_direction", vec ? d.n / 8 : d.n, d.n, grid)) return rc;
     if (vec) hipLaunchKernelGGL(eps_direction_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d);
     else hipLaunchKernelGGL(eps_direction_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d);
     SLH_LAUNCH_CHECK("slh_eps_direction");
@@ -355,9 +311,8 @@ extern "C" int slh_eps_direction_momentum(const void* const* ptrs, const int32_t
     for (int k = 0; k < d.K; ++k)
         for (const void* p : {ptrs[2 + k], ptrs[2 + DIR_MAX + k]})
             SLH_CHECK(!overlaps(m.mom_out, n * 4, p, n * 2), "%s: mom_out overlaps pos[%d] / neg[%d]", name, k, k);
-    const long threads = vec ? n / 8 : n;
-    SLH_CHECK((threads + 255) / 256 < (1L << 31), "%s: nb * chw = %ld is too large for one launch", name, n);
-    const dim3 grid((unsigned)((threads + 255) / 256));
+    dim3 grid;
+    if (const int rc = launch_grid(name, vec ? n / 8 : n, n, grid)) return rc;
     if (vec) hipLaunchKernelGGL(eps_direction_momentum_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, m);
     else hipLaunchKernelGGL(eps_direction_momentum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, m);
     SLH_LAUNCH_CHECK(name);

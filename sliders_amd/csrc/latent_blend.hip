@@ -3,7 +3,7 @@
 // the same step (SampleTrace.visited), and the mask has one value per latent pixel, shared by the channels:
 //
 //   m   = mask[b * hw + i % hw]
-//   out = m == 0 ? keep : m == 1 ? e : keep + m (e - keep)           the select-then-lerp of slh_ddpm_edit_blend (csrc/edit.hip)
+//   out = m == 0 ? keep : m == 1 ? e : keep + m (e - keep)           blend_one (step_common.h), as slh_ddpm_edit_blend (csrc/edit.hip)
 //   dtype 1 (fp32 master latent):  in_bf16 = in2_bf16 = rne(out * s_next)      as slh_sigma_step writes the next pass's input
 //   dtype 0 (bf16 latent):         out = rne(the fp32 result);  in_bf16 = in2_bf16 = out's bits
 //
@@ -14,12 +14,14 @@
 // Every thread reads all it needs of its elements before it writes any of them, and no thread touches another's, so out may alias
 // e.  16-byte accesses (four fp32 / eight bf16 elements per thread) where every pointer, chw and hw allow them: hw a multiple of
 // the vector means a vector never straddles a channel, so its mask values are consecutive and are read as vectors too.  Otherwise
-// one element per thread.  Plain loads and stores; no atomics, nothing waits on another workgroup.
+// one element per thread (load_vec / store_vec, step_common.h).  Plain loads and stores; no atomics, nothing waits on another workgroup.
 #include <cmath>
-#include "common.h"
+#include "step_common.h"
 #include "../../include/sliders_hip.h"
 
 namespace {
+
+using namespace slh_step_detail;
 
 struct latent_blend_args {
     const void* e; const void* keep; const float* mask;
@@ -28,13 +30,6 @@ struct latent_blend_args {
     int chw, hw;
     float s_next;
 };
-
-__device__ __forceinline__ float blend_one(float e, float k, float m) {
-#pragma clang fp contract(off)
-    // three roundings where 0 < m < 1: e - k, m *, k +
-    const float o = k + m * (e - k);
-    return m == 0.0f ? k : m == 1.0f ? e : o;
-}
 
 // T: the type of e / keep / out (float: dtype 1, __bf16: dtype 0).  VEC: 16 / sizeof(T) elements per thread, n is a multiple of it
 template <typename T, bool VEC>
@@ -47,56 +42,19 @@ __global__ __launch_bounds__(256) void latent_blend_kernel(const latent_blend_ar
     const long g = i * V;                           // the thread's first element
     const long b = g / d.chw;
     const int pix = (int)(g - b * d.chw) % d.hw;    // chw is a multiple of hw
-    const float* mp = d.mask + b * d.hw + pix;
     float e[V], k[V], m[V], o[V];
-    if constexpr (!VEC) {
-        e[0] = (float)((const T*)d.e)[g];
-        k[0] = (float)((const T*)d.keep)[g];
-        m[0] = mp[0];
-    } else if constexpr (F32) {
-        const f32x4 ev = ((const f32x4*)d.e)[i], kv = ((const f32x4*)d.keep)[i], mv = *(const f32x4*)mp;
-        for (int c = 0; c < 4; ++c) { e[c] = ev[c]; k[c] = kv[c]; m[c] = mv[c]; }
-    } else {
-        const bf16x8 ev = ((const bf16x8*)d.e)[i], kv = ((const bf16x8*)d.keep)[i];
-        const f32x4 m0 = ((const f32x4*)mp)[0], m1 = ((const f32x4*)mp)[1];
-        for (int c = 0; c < 8; ++c) { e[c] = (float)ev[c]; k[c] = (float)kv[c]; m[c] = c < 4 ? m0[c] : m1[c - 4]; }
-    }
+    load_vec<V>((const T*)d.e, g, e);
+    load_vec<V>((const T*)d.keep, g, k);
+    load_vec<V>(d.mask, b * d.hw + pix, m);
 #pragma unroll
     for (int c = 0; c < V; ++c) o[c] = blend_one(e[c], k[c], m[c]);
     // everything is read; now the stores
-    if constexpr (!VEC) {
-        __bf16 ob;
-        if constexpr (F32) {
-            ((float*)d.out)[g] = o[0];
-            ob = (__bf16)(o[0] * d.s_next);         // round to nearest even
-        } else {
-            ob = (__bf16)o[0];
-            ((__bf16*)d.out)[g] = ob;
-        }
-        if (d.in_bf16) d.in_bf16[g] = ob;
-        if (d.in2_bf16) d.in2_bf16[g] = ob;
-    } else if constexpr (F32) {
-        f32x4 ov;
-        bf16x4 ob;
-        for (int c = 0; c < 4; ++c) { ov[c] = o[c]; ob[c] = (__bf16)(o[c] * d.s_next); }
-        ((f32x4*)d.out)[i] = ov;
-        if (d.in_bf16) ((bf16x4*)d.in_bf16)[i] = ob;
-        if (d.in2_bf16) ((bf16x4*)d.in2_bf16)[i] = ob;
-    } else {
-        bf16x8 ob;
-        for (int c = 0; c < 8; ++c) ob[c] = (__bf16)o[c];
-        ((bf16x8*)d.out)[i] = ob;
-        if (d.in_bf16) ((bf16x8*)d.in_bf16)[i] = ob;
-        if (d.in2_bf16) ((bf16x8*)d.in2_bf16)[i] = ob;
+    store_vec<V>((T*)d.out, g, o);
+    if constexpr (F32) {
+#pragma unroll
+        for (int c = 0; c < V; ++c) o[c] = o[c] * d.s_next;
     }
-}
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// [a, a + na) and [b, b + nb) bytes share an address (a null b: no)
-inline bool overlaps(const void* a, long na, const void* b, long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return b && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+    store_bf16_copies<V>(d.in_bf16, d.in2_bf16, g, o);      // bf16 latents: out's bits again
 }
 
 }  // namespace
@@ -105,8 +63,7 @@ extern "C" int slh_latent_blend(const void* const* ptrs, const int32_t* dims, co
     SLH_CHECK(ptrs && dims, "slh_latent_blend: null ptrs / dims");
     const int nb = dims[0], chw = dims[1], hw = dims[2], dtype = dims[3];
     SLH_CHECK(dtype == 0 || dtype == 1, "slh_latent_blend: dtype %d (0 bf16, 1 fp32)", dtype);
-    SLH_CHECK(nb >= 1 && chw >= 1 && hw >= 1, "slh_latent_blend: nb = %d, chw = %d, hw = %d", nb, chw, hw);
-    SLH_CHECK(chw % hw == 0, "slh_latent_blend: chw = %d is not a multiple of hw = %d", chw, hw);
+    if (const int rc = shape_check("slh_latent_blend", nb, chw, hw)) return rc;
     SLH_CHECK(ptrs[0] && ptrs[1] && ptrs[2] && ptrs[3], "slh_latent_blend: null e / keep / mask / out");
     SLH_CHECK(dtype == 0 || coef, "slh_latent_blend: dtype 1 needs coef (s_next)");
     SLH_CHECK(dtype == 0 || std::isfinite(coef[0]), "slh_latent_blend: s_next = %f is not finite", (double)coef[0]);
@@ -135,9 +92,8 @@ extern "C" int slh_latent_blend(const void* const* ptrs, const int32_t* dims, co
         SLH_CHECK(!overlaps(d.keep, n * esz, o.p, o.bytes), "slh_latent_blend: keep overlaps %s", o.name);
         SLH_CHECK(!overlaps(d.mask, (long)nb * hw * 4, o.p, o.bytes), "slh_latent_blend: mask overlaps %s", o.name);
     }
-    const long threads = vec ? n / V : n;
-    SLH_CHECK((threads + 255) / 256 < (1L << 31), "slh_latent_blend: nb * chw = %ld is too large for one launch", n);
-    const dim3 grid((unsigned)((threads + 255) / 256));
+    dim3 grid;
+    if (const int rc = launch_grid("slh_latent_blend", vec ? n / V : n, n, grid)) return rc;
     const hipStream_t s = (hipStream_t)stream;
     if (dtype == 1) {
         if (vec) hipLaunchKernelGGL((latent_blend_kernel<float, true>), grid, dim3(256), 0, s, d);

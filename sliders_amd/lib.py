@@ -182,12 +182,10 @@ _HOST_FNS = {
     "slh_lora_wgrad_blocks": (c_i32, [_P(WgradDesc)]), "slh_lora_wgrad_single_blocks": (c_i32, [_P(WgradDesc)]),
     "slh_lora_wgrad_geometry": (c_i32, [_P(WgradDesc), c_i32, _P(c_i32)]),
     "slh_transpose_heads_blocks": (c_i32, [_P(TransposeDesc)]), "slh_lora_merge_blocks": (c_i32, [_P(LoraMergeItem)]),
-    "slh_sigma_step": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
-    "slh_latent_blend": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
-    "slh_direction_threshold": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
-    "slh_eps_direction": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
-    "slh_eps_direction_momentum": (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp]),
 }
+# the step entry points that take (ptrs, dims, coef, stream): three flat arrays instead of a descriptor (_three_arrays calls them)
+_HOST_FNS.update((name, (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp])) for name in (
+    "slh_sigma_step", "slh_latent_blend", "slh_direction_threshold", "slh_eps_direction", "slh_eps_direction_momentum"))
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
 
@@ -455,6 +453,13 @@ def call(opcode: int, desc, stream: int):
     check(getattr(lib, name)(C.byref(desc), c_vp(stream)), name)
 
 
+def _three_arrays(name: str, stream: int, ptrs, dims, coef=()):
+    """One (ptrs, dims, coef, stream) entry point: device addresses, int32 dimensions, fp32 coefficients (rounded to fp32 here, as the
+    kernels read them; none: NULL)."""
+    coef = (c_f32 * len(coef))(*coef) if coef else None
+    check(getattr(load(), name)((c_vp * len(ptrs))(*ptrs), (c_i32 * len(dims))(*dims), coef, c_vp(stream)), name)
+
+
 def sigma_step(stream: int, *, eps: int, x: int, out: int, nb: int, chw: int, kind: int, p: float, q: float, sigma: float = 0.0,
                a: float = 1.0, c=(0.0,), c_n: float = 0.0, s_next: float = 1.0, guidance: float = 0.0, single: bool = False,
                eps_text: int = 0, hist=(), noise: int = 0, hist_out: int = 0, in_bf16: int = 0, in2_bf16: int = 0):
@@ -464,10 +469,8 @@ def sigma_step(stream: int, *, eps: int, x: int, out: int, nb: int, chw: int, ki
     hist, c = tuple(hist), tuple(c)
     if len(hist) > 3 or len(c) > 4:
         raise SlidersHipError(f"slh_sigma_step: {len(hist)} history buffers, {len(c)} coefficients: at most 3 and 4")
-    ptrs = (c_vp * 11)(eps, eps_text, x, *(hist + (0,) * (3 - len(hist))), noise, out, hist_out, in_bf16, in2_bf16)
-    dims = (c_i32 * 5)(nb, chw, len(hist), kind, int(bool(single)))
-    coef = (c_f32 * 11)(p, q, sigma, a, *(c + (0.0,) * (4 - len(c))), c_n, s_next, guidance)
-    check(load().slh_sigma_step(ptrs, dims, coef, c_vp(stream)), "slh_sigma_step")
+    _three_arrays("slh_sigma_step", stream, (eps, eps_text, x, *hist, *(0,) * (3 - len(hist)), noise, out, hist_out, in_bf16, in2_bf16),
+                  (nb, chw, len(hist), kind, int(bool(single))), (p, q, sigma, a, *c, *(0.0,) * (4 - len(c)), c_n, s_next, guidance))
 
 
 def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int, chw: int, hw: int, fp32: bool, s_next: float = 1.0,
@@ -475,47 +478,38 @@ def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int
     """slh_latent_blend (include/sliders_hip.h): one launch of a localised sampling step's blend, out = keep where the mask is 0, e where
     it is 1, keep + m (e - keep) between.  Pointers are device addresses (0: absent); fp32: e / keep / out are fp32 and the bf16 copies
     are rne(out * s_next) (s_next rounded to fp32 here, as the kernel reads it), else they are bf16 and the copies are out's bits."""
-    ptrs = (c_vp * 6)(e, keep, mask, out, in_bf16, in2_bf16)
-    dims = (c_i32 * 4)(nb, chw, hw, 1 if fp32 else 0)
-    coef = (c_f32 * 1)(s_next)
-    check(load().slh_latent_blend(ptrs, dims, coef, c_vp(stream)), "slh_latent_blend")
+    _three_arrays("slh_latent_blend", stream, (e, keep, mask, out, in_bf16, in2_bf16), (nb, chw, hw, 1 if fp32 else 0), (s_next,))
 
 
 MAX_DIRECTIONS = 3          # prompt pairs per slh_direction_threshold / slh_eps_direction[_momentum] call
 
 
-def _direction_rows(what: str, pos, neg):
-    pos, neg = tuple(pos), tuple(neg)
-    if len(pos) != len(neg) or len(pos) > MAX_DIRECTIONS:
-        raise SlidersHipError(f"{what}: {len(pos)} pos and {len(neg)} neg rows: the same number of each, at most {MAX_DIRECTIONS}")
-    pad = (0,) * (MAX_DIRECTIONS - len(pos))
-    return pos + pad, neg + pad, len(pos)
+def _direction_rows(what: str, pos, neg, per_direction, counted: str, cast):
+    """(pos, neg, per_direction, K), each of the three padded with zeros to MAX_DIRECTIONS; per_direction: K n_keep values (cast: int) or
+    K coefficients (float)"""
+    pos, neg, per_direction = tuple(pos), tuple(neg), tuple(cast(v) for v in per_direction)
+    K = len(pos)
+    if len(neg) != K or K > MAX_DIRECTIONS:
+        raise SlidersHipError(f"{what}: {K} pos and {len(neg)} neg rows: the same number of each, at most {MAX_DIRECTIONS}")
+    if len(per_direction) != K:
+        raise SlidersHipError(f"{what}: {len(per_direction)} {counted} for {K} directions")
+    pad = MAX_DIRECTIONS - K
+    return pos + (0,) * pad, neg + (0,) * pad, per_direction + (cast(),) * pad, K
 
 
 def direction_threshold(stream: int, *, pos, neg, thr: int, n_keep, nb: int, chw: int, hw: int):
     """slh_direction_threshold (include/sliders_hip.h): thr[b][k][ch] (int32, [nb][K][chw / hw]) = the n_keep[k]-th largest key of
     e+_k - e-_k over the hw pixels of channel ch of sample b.  pos, neg: K device addresses each (bf16 [nb][chw]); n_keep: K counts."""
-    pos, neg, K = _direction_rows("slh_direction_threshold", pos, neg)
-    n_keep = tuple(int(v) for v in n_keep)
-    if len(n_keep) != K:
-        raise SlidersHipError(f"slh_direction_threshold: {len(n_keep)} n_keep values for {K} directions")
-    ptrs = (c_vp * 7)(*pos, *neg, thr)
-    dims = (c_i32 * 7)(nb, chw, hw, K, *(n_keep + (0,) * (MAX_DIRECTIONS - K)))
-    check(load().slh_direction_threshold(ptrs, dims, None, c_vp(stream)), "slh_direction_threshold")
+    pos, neg, n_keep, K = _direction_rows("slh_direction_threshold", pos, neg, n_keep, "n_keep values", int)
+    _three_arrays("slh_direction_threshold", stream, (*pos, *neg, thr), (nb, chw, hw, K, *n_keep))
 
 
 def eps_direction(stream: int, *, t: int, out: int, pos, neg, c, nb: int, chw: int, hw: int, thr: int = 0):
     """slh_eps_direction (include/sliders_hip.h): out = rne_bf16(t + sum_k c[k] keep_k (e+_k - e-_k)), the guided text row a step kernel
     reads through eps_text.  pos, neg: K device addresses each; c: K coefficients (rounded to fp32 here, as the kernel reads them; a
     zero skips its term); thr: what slh_direction_threshold wrote, 0: every element is kept."""
-    pos, neg, K = _direction_rows("slh_eps_direction", pos, neg)
-    c = tuple(float(v) for v in c)
-    if len(c) != K:
-        raise SlidersHipError(f"slh_eps_direction: {len(c)} coefficients for {K} directions")
-    ptrs = (c_vp * 9)(t, out, *pos, *neg, thr)
-    dims = (c_i32 * 4)(nb, chw, hw, K)
-    coef = (c_f32 * 3)(*(c + (0.0,) * (MAX_DIRECTIONS - K)))
-    check(load().slh_eps_direction(ptrs, dims, coef, c_vp(stream)), "slh_eps_direction")
+    pos, neg, c, K = _direction_rows("slh_eps_direction", pos, neg, c, "coefficients", float)
+    _three_arrays("slh_eps_direction", stream, (t, out, *pos, *neg, thr), (nb, chw, hw, K), c)
 
 
 def eps_direction_momentum(stream: int, *, t: int, out: int, pos, neg, c, mom_in: int, mom_out: int, s_m: float, beta: float, nb: int,
@@ -523,14 +517,9 @@ def eps_direction_momentum(stream: int, *, t: int, out: int, pos, neg, c, mom_in
     """slh_eps_direction_momentum (include/sliders_hip.h): slh_eps_direction with the momentum state nu (fp32 [nb][chw]) read from mom_in:
     out = rne_bf16(t + sum_k c[k] keep_k d_k + s_m nu), mom_out = beta nu + (1 - beta) (sum_k c[k] keep_k d_k + s_m nu).  mom_out may be
     mom_in.  1 - beta is formed here in double and rounded once to fp32, as the kernel reads it; s_m == 0 is refused (eps_direction)."""
-    pos, neg, K = _direction_rows("slh_eps_direction_momentum", pos, neg)
-    c = tuple(float(v) for v in c)
-    if len(c) != K:
-        raise SlidersHipError(f"slh_eps_direction_momentum: {len(c)} coefficients for {K} directions")
-    ptrs = (c_vp * 11)(t, out, *pos, *neg, thr, mom_in, mom_out)
-    dims = (c_i32 * 4)(nb, chw, hw, K)
-    coef = (c_f32 * 6)(*(c + (0.0,) * (MAX_DIRECTIONS - K)), s_m, beta, one_minus(beta))
-    check(load().slh_eps_direction_momentum(ptrs, dims, coef, c_vp(stream)), "slh_eps_direction_momentum")
+    pos, neg, c, K = _direction_rows("slh_eps_direction_momentum", pos, neg, c, "coefficients", float)
+    _three_arrays("slh_eps_direction_momentum", stream, (t, out, *pos, *neg, thr, mom_in, mom_out), (nb, chw, hw, K),
+                  (*c, s_m, beta, one_minus(beta)))
 
 
 def one_minus(beta: float) -> float:

@@ -6,6 +6,8 @@ import pytest
 import torch
 
 from sliders_amd import lib
+from sliders_amd.ddim import DDIMSchedule
+from sliders_amd.edit import ddpm_step_coefficients, fp32_coefficients
 from tests.latent_blend_ref import bound, expand_mask, oracle, worst_ratio
 from tests.test_latent_blend_host import S_NEXT, draw_inputs, draw_mask
 
@@ -144,3 +146,36 @@ def test_kernel_identities(dev, fp32, chw, hw, off):
     keep = keep if fp32 else keep.to(BF)
     f = Buffers(dev, n, nb * hw, fp32, off, keep, keep, draw_mask("fractional", nb * hw, g))
     assert torch.equal(_bits(f.get(run(f), "out")), _bits(keep))
+
+
+@pytest.mark.parametrize("hw", [35, 64])          # chw = 140: the scalar form of slh_latent_blend; chw = 256: its 16-byte form
+def test_agrees_with_ddpm_edit_blend(dev, hw):
+    """The blend is one piece of code (csrc/step_common.h): slh_ddpm_edit_step (mode 1) followed by slh_latent_blend writes the bits
+    slh_ddpm_edit_blend writes in one launch - out and both bf16 copies.  s_next = 1: the copy rne(out * 1) is rne(out)."""
+    nb, chw = 2, 4 * hw
+    n, s = nb * chw, torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(11)
+    eps = torch.randn(2 * n, generator=g).to(BF)
+    x, resid, keep = (torch.randn(n, generator=g) for _ in range(3))
+    mask = torch.rand(nb * hw, generator=g)
+    mask[0::3], mask[1::3] = 0.0, 1.0             # exact 0, exact 1 and fractions
+    p1 = (1 - hw) % 3                             # mask[hw + p1] == 1: a pixel of sample 1
+    assert mask[0] == 0 and mask[hw + p1] == 1 and 0 < mask[2] < 1
+    resid[hw] = float("nan")                      # e = mu + resid is NaN at (sample 0, channel 1, pixel 0), where m == 0
+    keep[chw + 2 * hw + p1] = float("nan")        # keep is NaN at (sample 1, channel 2, pixel p1), where m == 1
+    f = fp32_coefficients(ddpm_step_coefficients(DDIMSchedule(), 500, 50, 1.0))
+    eps_d, x_d, resid_d, keep_d, mask_d = (t.to(dev) for t in (eps, x, resid, keep, mask))
+    new32 = lambda: torch.full((n,), float("nan"), device=dev)
+    new16 = lambda: torch.full((n,), float("nan"), device=dev, dtype=BF)
+    common = dict(eps=eps_d.data_ptr(), x=x_d.data_ptr(), resid=resid_d.data_ptr(), nb=nb, chw=chw, guidance=7.5, v_prediction=0, **f)
+    e, two, one = new32(), (new32(), new16(), new16()), (new32(), new16(), new16())
+    lib.call(lib.OP_DDPM_EDIT, lib.DdpmEditDesc(out=e.data_ptr(), mode=1, **common), s)
+    lib.latent_blend(s, e=e.data_ptr(), keep=keep_d.data_ptr(), mask=mask_d.data_ptr(), out=two[0].data_ptr(), nb=nb, chw=chw, hw=hw, fp32=True,
+                     s_next=1.0, in_bf16=two[1].data_ptr(), in2_bf16=two[2].data_ptr())
+    lib.call(lib.OP_DDPM_EDIT_BLEND, lib.DdpmEditBlendDesc(keep=keep_d.data_ptr(), mask=mask_d.data_ptr(), hw=hw, out=one[0].data_ptr(),
+                                                           out_bf16=one[1].data_ptr(), out2_bf16=one[2].data_ptr(), **common), s)
+    torch.cuda.synchronize()
+    assert torch.isnan(e[hw]), "the NaN in e is where it was put"
+    for name, a, b in zip(("out", "first bf16 copy", "second bf16 copy"), two, one):
+        assert not torch.isnan(a).any() and not torch.isnan(b).any(), f"{name}: a NaN from the unselected side reached it"
+        assert torch.equal(_bits(a), _bits(b)), f"{name}: slh_latent_blend and slh_ddpm_edit_blend differ"
