@@ -1,7 +1,7 @@
 // Operand addressing shared by the bf16 GEMM kernels (gemm*.hip) and the skinny LoRA products (lora.hip): which source pixel
 // feeds a filter tap of the implicit-GEMM 3x3 convolution, which concat source holds a channel, where a weight / adapter row
 // starts.  The helpers are templates over the argument struct: GemmArgs and lora.hip's AddrArgs name the geometry fields alike
-// (a0, a1, lda0, lda1, ca0, ca1, hs, ws, src_xform, stride).  gfx950 only.
+// (a0, a1, lda0, lda1, ca0, ca1, hs, ws, src_xform, stride).  The fp32 kernels of vae.hip take pixel_of_row from here.  gfx950 only.
 #pragma once
 #include "common.h"
 
@@ -18,8 +18,8 @@ __device__ __forceinline__ RowPixel pixel_of_row(const int m, const int ho, cons
 // Source pixel of filter tap (ky, kx) of a 3x3, pad-1 convolution at output pixel (b, oy, ox).  src_xform 0: the source is the
 // input; 1: its nearest-neighbour 2x upsampling; 2: its zero-dilated 2x grid (only even (iy, ix) hold data: the backward-data
 // form of a stride-2 convolution).  !ok: the tap reads padding or a hole (the callers substitute zeros); pix indexes the source's
-// [b][hs][ws] pixels.  (vae.hip - fp32, its own descriptor - and lora_conv_dgrad_kernel - the transposed walk, from an input
-// pixel to the outputs it feeds - state their own addressing.)
+// [b][hs][ws] pixels.  (vae.hip shares pixel_of_row and keeps its own tap - conv_tap_src: fp32, pad 0 or 1, its own descriptor;
+// lora_conv_dgrad_kernel - the transposed walk, from an input pixel to the outputs it feeds - states its own addressing.)
 struct ConvTap { bool ok; long pix; };
 template <class G>
 __device__ __forceinline__ ConvTap conv_tap(const G& g, const int b, const int oy, const int ox, const int ky, const int kx) {

@@ -353,6 +353,12 @@ void slh_set_error(const char* fmt, ...);
             return -1;                  \
         }                               \
     } while (0)
+// grid: the 256-thread workgroups that hold `threads` threads of a launch over n elements; refused where they do not fit one launch
+inline int launch_grid(const char* name, long threads, long n, dim3& grid) {
+    SLH_CHECK((threads + 255) / 256 < (1L << 31), "%s: n = %ld is too large for one launch", name, n);
+    grid = dim3((unsigned)((threads + 255) / 256));
+    return 0;
+}
 // query mode (error.cpp; slh_gemm_kernel_name, slh_gemm_launch_query): the dispatch code runs as for a launch, slh_launch records the
 // chosen instantiation, its grid, its block size and a hash of its argument bytes instead of launching it, and the launch checks are
 // skipped (no device is needed)

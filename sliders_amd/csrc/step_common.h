@@ -1,6 +1,6 @@
 // The pieces the element-wise step kernels share (edit.hip, sigma_step.hip, latent_blend.hip, eps_direction.hip): the CFG combine, the
 // select-then-lerp blend, the text half of an epsilon pair, vector-or-scalar operand access and the bf16 copies of a result; on the
-// host the alignment, overlap and shape checks and the launch sizing.  Each is stated here once.  These kernels are held bit for bit
+// host the alignment, overlap and shape checks (the launch sizing is common.h's launch_grid).  Each is stated here once.  These kernels are held bit for bit
 // to plain-torch restatements in the same operation order (tests/*_ref.py, edit.ddpm_mu_reference, edit.blend_reference): fp32, one
 // rounding per operation, nothing contracted.
 // EVERY DEVICE FUNCTION HERE THAT DOES ARITHMETIC CARRIES ITS OWN `#pragma clang fp contract(off)`.  The setting belongs to the
@@ -97,11 +97,6 @@ inline int shape_check(const char* name, int nb, int chw, int hw) {
     return 0;
 }
 
-// grid: the 256-thread workgroups that hold `threads` threads of a launch over n = nb * chw elements; refused where they do not fit
-inline int launch_grid(const char* name, long threads, long n, dim3& grid) {
-    SLH_CHECK((threads + 255) / 256 < (1L << 31), "%s: nb * chw = %ld is too large for one launch", name, n);
-    grid = dim3((unsigned)((threads + 255) / 256));
-    return 0;
-}
+using ::launch_grid;      // common.h: the grid of a launch over n = nb * chw elements, refused where it does not fit
 
 }  // namespace slh_step_detail

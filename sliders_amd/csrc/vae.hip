@@ -15,7 +15,7 @@
 //   slh_vae_sample    mean + exp(0.5 clamp(logvar)) * n1, * scaling_factor, add_noise with n2 -> NCHW bf16 (+fp32)
 // The encoder runs twice per image-slider iteration (~1.1 TFLOP per 512x512 image): far from the hot loop's cost,
 // so these kernels are written for exact fp32 arithmetic first and MFMA-bound simplicity second.
-#include "common.h"
+#include "addressing.h"
 #include <string.h>
 #include <type_traits>
 #include "../../include/sliders_hip.h"
@@ -34,15 +34,85 @@ typedef __attribute__((ext_vector_type(4))) float f4;
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int SBM = 128, SBN = 128, SBK = 16;
 
+// ---- what the three sgemm kernels share ---------------------------------------------------------------------------------------
+// workgroup -> first row and column of its TM x SBN tile; tiles run [tile_m][tile_n]
+struct TileOrigin { int m0, n0; };
+__device__ __forceinline__ TileOrigin tile_origin(const int N, const int TM) {
+    const int tiles_n = (N + SBN - 1) / SBN;
+    const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
+    return {tile_m * TM, tile_n * SBN};
+}
+
+template <int MI>      // 32-row blocks per wave along M
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[MI][2]) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// Four floats from p, from the zero page for a row or tap that does not exist.  Every operand load is UNCONDITIONAL, from a selected
+// address: a load behind a condition makes hipcc branch around it and wait vmcnt(0) at the join - inside the split kernel's K loop
+// that drained the three-step prefetch on every step (the loop then ran at the memory latency: 7100 cycles per step pair against
+// ~1500 of MFMA).
+__device__ __forceinline__ f4 load4_or_zero(const bool ok, const float* p) { return *(const f4*)(ok ? p : (const float*)slh_zero_page); }
+
+// Conv mode (rows -> pixels: pixel_of_row, addressing.h).  K runs [ky][kx][cin]: K offset k0 -> filter tap and first channel in it
+struct KTap { int ky, kx, c0; };
+__device__ __forceinline__ KTap tap_of_k(const int k0, const int cin) {
+    const int tap = k0 / cin, ky = tap / 3;
+    return {ky, tap - ky * 3, k0 - tap * cin};
+}
+// the source of tap t at output pixel p: its first float, and whether the tap lies inside the (upsampled) image - outside is zero
+struct TapSrc { bool ok; const float* p; };
+__device__ __forceinline__ TapSrc conv_tap_src(const slh_sgemm_desc d, const RowPixel p, const KTap t) {
+    const int iy = p.oy * d.stride + t.ky - d.pad, ix = p.ox * d.stride + t.kx - d.pad;
+    const int sh = d.upsample ? 1 : 0;         // nearest-2x upsampled source (Upsample2D): read pixel (iy>>1, ix>>1)
+    const bool ok = iy >= 0 && iy < (d.hs << sh) && ix >= 0 && ix < (d.ws << sh);
+    return {ok, (const float*)d.x + (((long)p.b * d.hs + (iy >> sh)) * d.ws + (ix >> sh)) * d.ldx + t.c0};
+}
+
+// acc[i][j][e] = C[m = mw + i*32 + lrow][n = nw + j*32 + (e&3) + 8*(e>>2) + 4*lhi], (mw, nw) the wave's first row and column:
+// C = alpha * acc + bias (per row or per column) + residual, one 16-byte store per accumulator quad.  The descriptor comes BY VALUE:
+// through a reference hipcc recomputes the row addresses for every store (~100 instructions more per epilogue).
+template <int MI>
+__device__ __forceinline__ void sgemm_epilogue(const slh_sgemm_desc d, const f32x16 (&acc)[MI][2], const int mw, const int nw,
+                                               const int lrow, const int lhi) {
+    const float* bias = (const float*)d.bias;
+    const float* res = (const float*)d.residual;
+    float* C = (float*)d.c;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+        const int m = mw + i * 32 + lrow;
+        if (m >= d.M) continue;
+        const float rowb = (bias && d.bias_per_row) ? bias[m] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int n = nw + j * 32 + q * 8 + lhi * 4;
+                if (n >= d.N) continue;
+                f4 v = {acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
+                v *= d.alpha;
+                if (bias) {
+                    if (d.bias_per_row) v += rowb;
+                    else v += *(const f4*)(bias + n);
+                }
+                if (res) v += *(const f4*)(res + (long)m * d.ldr + n);
+                *(f4*)(C + (long)m * d.ldc + n) = v;
+            }
+    }
+}
+
 __global__ __launch_bounds__(256) void sgemm_kernel(const slh_sgemm_desc d) {
     __shared__ float sX[SBK][SBM];
     __shared__ float sW[SBK][SBN];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_n = (d.N + SBN - 1) / SBN;
-    const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
-    const int m0 = tile_m * SBM, n0 = tile_n * SBN;
+    const auto [m0, n0] = tile_origin(d.N, SBM);
     // loader geometry: thread -> tile row r (0..127), k quads kq and kq+2
     const int r = tid & 127, kq = tid >> 7;
     int xm = m0 + r;
@@ -53,46 +123,20 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const slh_sgemm_desc d) {
     wnr = wvalid ? wnr : d.N - 1;
     const float* X = (const float*)d.x;
     const float* W = (const float*)d.w;
-    int xb = 0, xoy = 0, xox = 0;
-    if (d.mode == 1) {
-        const int hw = d.ho * d.wo;
-        xb = xm / hw;
-        const int rem = xm - xb * hw;
-        xoy = rem / d.wo;
-        xox = rem - xoy * d.wo;
-    }
-    const int cin = d.cin;
+    const RowPixel xp = d.mode == 1 ? pixel_of_row(xm, d.ho, d.wo) : RowPixel{0, 0, 0};
     auto load_x = [&](int k0, f4& a, f4& b) {
-        const float* src;
-        bool ok = xvalid;
-        if (d.mode == 0) {
-            src = X + (long)xm * d.ldx + k0;
-        } else {
-            const int tap = k0 / cin, c0 = k0 - tap * cin;
-            const int ky = tap / 3, kx = tap - ky * 3;
-            const int iy = xoy * d.stride + ky - d.pad, ix = xox * d.stride + kx - d.pad;
-            const int sh = d.upsample ? 1 : 0;         // nearest-2x upsampled source (Upsample2D): read pixel (iy>>1, ix>>1)
-            ok = ok && iy >= 0 && iy < (d.hs << sh) && ix >= 0 && ix < (d.ws << sh);
-            src = X + (((long)xb * d.hs + (iy >> sh)) * d.ws + (ix >> sh)) * d.ldx + c0;
-        }
-        // unconditional loads from a selected address (see sgemm_bf16x3_kernel: a load behind a condition costs a vmcnt(0))
-        const float* sa = ok ? src + 4 * kq : (const float*)slh_zero_page;
-        const float* sb = ok ? src + 4 * (kq + 2) : (const float*)slh_zero_page;
-        a = *(const f4*)sa;
-        b = *(const f4*)sb;
+        TapSrc s = {true, X + (long)xm * d.ldx + k0};
+        if (d.mode == 1) s = conv_tap_src(d, xp, tap_of_k(k0, d.cin));
+        a = load4_or_zero(xvalid && s.ok, s.p + 4 * kq);
+        b = load4_or_zero(xvalid && s.ok, s.p + 4 * (kq + 2));
     };
     auto load_w = [&](int k0, f4& a, f4& b) {
         const float* src = W + (long)wnr * d.ldw + k0;
-        a = *(const f4*)(wvalid ? src + 4 * kq : (const float*)slh_zero_page);
-        b = *(const f4*)(wvalid ? src + 4 * (kq + 2) : (const float*)slh_zero_page);
+        a = load4_or_zero(wvalid, src + 4 * kq);
+        b = load4_or_zero(wvalid, src + 4 * (kq + 2));
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    clear_acc(acc);
     f4 xa, xb4, wa, wb;
     load_x(0, xa, xb4);
     load_w(0, wa, wb);
@@ -124,31 +168,7 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const slh_sgemm_desc d) {
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[j], xf[i], acc[i][j], 0, 0, 0);
         }
     }
-    // acc[i][j][e] = C[m = m0 + wm*64 + i*32 + lrow][n = n0 + wn*64 + j*32 + (e&3) + 8*(e>>2) + 4*lhi]
-    const float* bias = (const float*)d.bias;
-    const float* res = (const float*)d.residual;
-    float* C = (float*)d.c;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = m0 + wm * 64 + i * 32 + lrow;
-        if (m >= d.M) continue;
-        const float rowb = (bias && d.bias_per_row) ? bias[m] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n0 + wn * 64 + j * 32 + q * 8 + lhi * 4;
-                if (n >= d.N) continue;
-                f4 v = {acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
-                v *= d.alpha;
-                if (bias) {
-                    if (d.bias_per_row) v += rowb;
-                    else v += *(const f4*)(bias + n);
-                }
-                if (res) v += *(const f4*)(res + (long)m * d.ldr + n);
-                *(f4*)(C + (long)m * d.ldc + n) = v;
-            }
-    }
+    sgemm_epilogue<2>(d, acc, m0 + wm * 64, n0 + wn * 64, lrow, lhi);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -177,9 +197,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_n = (d.N + SBN - 1) / SBN;
-    const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
-    const int m0 = tile_m * TM, n0 = tile_n * SBN;
+    const auto [m0, n0] = tile_origin(d.N, TM);
     // loader geometry: 8 consecutive lanes read the 128 contiguous bytes (32 floats) one tile row contributes to a K step,
     // so a load instruction touches 8 cache lines (a lane-per-row mapping touches 64 and is bound by the address pipe);
     // a thread handles k quad k4 of rows r8 + 32*e
@@ -187,24 +205,16 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
     const int r8 = tid >> 3, k4 = tid & 7;
     const float* X = (const float*)d.x;
     const float* W = (const float*)d.w;
-    const int cin = d.cin;
     bool xok[XE];
     long xoff[XE];                                               // dense: element offset of the row
-    int xb[XE], xoy[XE], xox[XE];                                // conv: sample / output pixel of the row
+    RowPixel xp[XE];                                             // conv: sample / output pixel of the row
 #pragma unroll
     for (int e = 0; e < XE; ++e) {
         int xm = m0 + r8 + 32 * e;
         xok[e] = xm < d.M;
         xm = xok[e] ? xm : d.M - 1;
         xoff[e] = (long)xm * d.ldx;
-        xb[e] = xoy[e] = xox[e] = 0;
-        if (d.mode == 1) {
-            const int hw = d.ho * d.wo;
-            xb[e] = xm / hw;
-            const int rem = xm - xb[e] * hw;
-            xoy[e] = rem / d.wo;
-            xox[e] = rem - xoy[e] * d.wo;
-        }
+        xp[e] = d.mode == 1 ? pixel_of_row(xm, d.ho, d.wo) : RowPixel{0, 0, 0};
     }
     bool wok[4];
     long woff[4];
@@ -214,29 +224,22 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
         wok[e] = wnr < d.N;
         woff[e] = (long)(wok[e] ? wnr : d.N - 1) * d.ldw;
     }
-    // Every load is UNCONDITIONAL, from a selected address (the zero page for rows / taps that do not exist): a load behind a
-    // condition makes hipcc branch around it and wait vmcnt(0) at the join - inside the K loop that drained the three-step
-    // prefetch on every step (the loop then ran at the memory latency: 7100 cycles per step pair against ~1500 of MFMA).
-    const float* zero4 = (const float*)slh_zero_page;
-    auto load_x = [&](int k0, f4* v) {
+    auto load_x = [&](int k0, f4* v) {       // unconditional loads: see load4_or_zero
         if (d.mode == 0) {
 #pragma unroll
-            for (int e = 0; e < XE; ++e) v[e] = *(const f4*)(xok[e] ? X + xoff[e] + k0 + 4 * k4 : zero4);
+            for (int e = 0; e < XE; ++e) v[e] = load4_or_zero(xok[e], X + xoff[e] + k0 + 4 * k4);
         } else {
-            const int tap = k0 / cin, c0 = k0 - tap * cin;
-            const int ky = tap / 3, kx = tap - ky * 3;
-            const int sh = d.upsample ? 1 : 0;
+            const KTap t = tap_of_k(k0, d.cin);
 #pragma unroll
             for (int e = 0; e < XE; ++e) {
-                const int iy = xoy[e] * d.stride + ky - d.pad, ix = xox[e] * d.stride + kx - d.pad;
-                const bool ok = xok[e] && iy >= 0 && iy < (d.hs << sh) && ix >= 0 && ix < (d.ws << sh);
-                v[e] = *(const f4*)(ok ? X + (((long)xb[e] * d.hs + (iy >> sh)) * d.ws + (ix >> sh)) * d.ldx + c0 + 4 * k4 : zero4);
+                const TapSrc s = conv_tap_src(d, xp[e], t);
+                v[e] = load4_or_zero(xok[e] && s.ok, s.p + 4 * k4);
             }
         }
     };
     auto load_w = [&](int k0, f4* v) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = *(const f4*)(wok[e] ? W + woff[e] + k0 + 4 * k4 : zero4);
+        for (int e = 0; e < 4; ++e) v[e] = load4_or_zero(wok[e], W + woff[e] + k0 + 4 * k4);
     };
     // 4 floats -> 8 bytes of bf16 high parts and 8 bytes of bf16 remainders (half k4 & 1 of 16-byte slot k4 >> 1)
     auto split_store4 = [&](const f4& a, char* hi_img, char* lo_img, int row) {
@@ -252,12 +255,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
         *(bf16x4*)(lo_img + off) = lo;
     };
     f32x16 acc[MI][2];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    clear_acc(acc);
     // Global loads run THREE K steps ahead of the MFMAs in three rotating register sets (a single step of MFMAs is ~0.3 us,
     // a first-touch load from HBM / the other XCDs' writes ~2 us; with one step of prefetch the loop ran at the memory
     // latency, 200 TF/s).  Invariant at the start of step k: set k % 3 is free (step k is in LDS), sets (k+1) % 3 and
@@ -330,31 +328,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(const slh_sgemm_de
     }
     if (k < nk) step(I0{}, I1{}, k);
     if (k + 1 < nk) step(I1{}, I2{}, k + 1);
-    // acc[i][j][e] = C[m = m0 + wm*32*MI + i*32 + lrow][n = n0 + wn*64 + j*32 + (e&3) + 8*(e>>2) + 4*lhi]
-    const float* bias = (const float*)d.bias;
-    const float* res = (const float*)d.residual;
-    float* C = (float*)d.c;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-        const int m = m0 + wm * (32 * MI) + i * 32 + lrow;
-        if (m >= d.M) continue;
-        const float rowb = (bias && d.bias_per_row) ? bias[m] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n0 + wn * 64 + j * 32 + q * 8 + lhi * 4;
-                if (n >= d.N) continue;
-                f4 v = {acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
-                v *= d.alpha;
-                if (bias) {
-                    if (d.bias_per_row) v += rowb;
-                    else v += *(const f4*)(bias + n);
-                }
-                if (res) v += *(const f4*)(res + (long)m * d.ldr + n);
-                *(f4*)(C + (long)m * d.ldc + n) = v;
-            }
-    }
+    sgemm_epilogue<MI>(d, acc, m0 + wm * (32 * MI), n0 + wn * 64, lrow, lhi);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -417,10 +391,10 @@ __global__ __launch_bounds__(256) void gn32_apply_kernel(const slh_gn32_desc d) 
 }
 
 // row softmax in place, fp32, one workgroup per row
-__global__ __launch_bounds__(256) void softmax32_kernel(float* x, int rows, int cols, long ld) {
+__global__ __launch_bounds__(256) void softmax32_kernel(const slh_softmax32_desc d) {
     __shared__ float red[8];
-    float* row = x + (long)blockIdx.x * ld;
-    const int tid = threadIdx.x;
+    float* row = d.x + (long)blockIdx.x * d.ld;
+    const int tid = threadIdx.x, cols = d.cols;
     float mx = -3.0e38f;
     for (int c = tid * 4; c < cols; c += 1024) {
         const f4 v = *(const f4*)(row + c);
@@ -451,17 +425,17 @@ __global__ __launch_bounds__(256) void softmax32_kernel(float* x, int rows, int 
 
 // conv_in: image [B][H*W][cin] fp32 (pixel-major; cin = 3: encoder input in [-1,1], cin = 4: decoder latents)
 // -> [B*H*W][cout] fp32, 3x3 pad 1.  w: [cout][3(ky)][3(kx)][cin] fp32.  One thread = one pixel x 4 output channels.
-__global__ __launch_bounds__(256) void vae_conv_in_kernel(const float* img, const float* w, const float* bias, float* y,
-                                                          int B, int H, int Wd, int cout, int cin) {
+__global__ __launch_bounds__(256) void vae_conv_in_kernel(const slh_vae_conv_desc d) {
+    const float *img = (const float*)d.x, *w = (const float*)d.w, *bias = (const float*)d.bias;
+    float* y = (float*)d.y;
+    const int H = d.h, Wd = d.wd, cout = d.cout, cin = d.cin;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int nq = cout / 4;
-    const long total = (long)B * H * Wd * nq;
+    const long total = (long)d.batch * H * Wd * nq;
     if (idx >= total) return;
-    const long pix = idx / nq;
+    const long pix = idx / nq;                                  // fits an int: checked on the host
     const int co = (int)(idx - pix * nq) * 4;
-    const int b = (int)(pix / ((long)H * Wd));
-    const int rem = (int)(pix - (long)b * H * Wd);
-    const int oy = rem / Wd, ox = rem - oy * Wd;
+    const auto [b, oy, ox] = pixel_of_row((int)pix, H, Wd);
     float acc[4] = {bias[co], bias[co + 1], bias[co + 2], bias[co + 3]};
     for (int ky = 0; ky < 3; ++ky) {
         const int iy = oy + ky - 1;
@@ -482,14 +456,14 @@ __global__ __launch_bounds__(256) void vae_conv_in_kernel(const float* img, cons
 }
 
 // conv_out (C -> 8, 3x3 pad 1) + quant_conv (8 -> 8, 1x1): one wave per latent pixel, lanes split the K = 9*C products
-__global__ __launch_bounds__(256) void vae_moments_kernel(const float* x, const float* w, const float* bias, const float* qw,
-                                                          const float* qb, float* out, int B, int H, int Wd, int C) {
+__global__ __launch_bounds__(256) void vae_moments_kernel(const slh_vae_conv_desc d) {
+    const float *x = (const float*)d.x, *w = (const float*)d.w, *bias = (const float*)d.bias, *qw = (const float*)d.qw, *qb = (const float*)d.qb;
+    float* out = (float*)d.y;
+    const int H = d.h, Wd = d.wd, C = d.cin;
     const int lane = threadIdx.x & 63;
     const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (pix >= (long)B * H * Wd) return;
-    const int b = (int)(pix / ((long)H * Wd));
-    const int rem = (int)(pix - (long)b * H * Wd);
-    const int oy = rem / Wd, ox = rem - oy * Wd;
+    if (pix >= (long)d.batch * H * Wd) return;                  // fits an int: checked on the host
+    const auto [b, oy, ox] = pixel_of_row((int)pix, H, Wd);
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int tap = 0; tap < 9; ++tap) {
         const int iy = oy + tap / 3 - 1, ix = ox + tap % 3 - 1;
@@ -534,16 +508,20 @@ __global__ __launch_bounds__(256) void vae_sample_kernel(const slh_vae_sample_de
 }
 
 // decoder input: z NCHW [B][4][hw] (fp32 or bf16) -> (z * inv_scaling) -> post_quant_conv 1x1 (4 -> 4) -> pixel-major [B*hw][4]
-__global__ __launch_bounds__(256) void vae_post_quant_kernel(const void* z, int z_bf16, const float* qw, const float* qb, float* y,
-                                                             int B, int hw, float inv_scaling) {
+__global__ __launch_bounds__(256) void vae_post_quant_kernel(const slh_vae_conv_desc d) {
+    const void* z = d.x;
+    const int z_bf16 = d.cin;                                   // 1: z is bf16 (the descriptor's cin has no other meaning here)
+    const float *qw = (const float*)d.qw, *qb = (const float*)d.qb;
+    float* y = (float*)d.y;
+    const int hw = d.h * d.wd;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)B * hw) return;
+    if (idx >= (long)d.batch * hw) return;
     const int b = (int)(idx / hw), pix = (int)(idx - (long)b * hw);
     float v[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const long o = ((long)b * 4 + c) * hw + pix;
-        v[c] = (z_bf16 ? (float)((const __bf16*)z)[o] : ((const float*)z)[o]) * inv_scaling;
+        v[c] = (z_bf16 ? (float)((const __bf16*)z)[o] : ((const float*)z)[o]) * d.inv_scaling;
     }
     f4 out;
 #pragma unroll
@@ -551,15 +529,13 @@ __global__ __launch_bounds__(256) void vae_post_quant_kernel(const void* z, int 
     *(f4*)(y + idx * 4) = out;
 }
 
-}  // namespace
-
-extern "C" int slh_vae_post_quant(const slh_vae_conv_desc* d, slh_stream_t stream) {
-    SLH_CHECK(d && d->x && d->qw && d->qb && d->y, "slh_vae_post_quant: bad descriptor");
-    const long n = (long)d->batch * d->h * d->wd;
-    hipLaunchKernelGGL(vae_post_quant_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d->x,
-                       d->cin /* 1: z is bf16 */, (const float*)d->qw, (const float*)d->qb, (float*)d->y, d->batch, d->h * d->wd,
-                       d->inv_scaling);
-    SLH_LAUNCH_CHECK("slh_vae_post_quant");
+// The launch of every element-wise kernel here: `threads` threads in workgroups of 256, the descriptor by value; a grid that does not
+// fit one launch is refused in the entry point's name (launch_grid, common.h)
+template <auto Kern, class D>
+int launch_flat(const char* name, const long threads, slh_stream_t stream, const D& d) {
+    dim3 grid;
+    if (const int rc = launch_grid(name, threads, threads, grid)) return rc;
+    hipLaunchKernelGGL(Kern, grid, dim3(256), 0, (hipStream_t)stream, d);
     return 0;
 }
 
@@ -567,12 +543,26 @@ extern "C" int slh_vae_post_quant(const slh_vae_conv_desc* d, slh_stream_t strea
 // through the same launch statements.  Split form: only where every K step of 32 lies inside one tap (K, Cin multiples of 32), else the
 // exact kernel; 128-row tiles from 256 of them on (a full round of the chip), 64-row tiles below (the 64 x 64-pixel layers).
 struct sgemm_choice { int form, grid; };
-static sgemm_choice sgemm_choose(const slh_sgemm_desc* d) {
-    const int tiles_n = (d->N + SBN - 1) / SBN;
-    const int tiles = ((d->M + SBM - 1) / SBM) * tiles_n;
-    if (!(d->split_bf16 == 1 && d->K % TBK == 0 && (d->mode == 0 || d->cin % TBK == 0))) return {SLH_SGEMM_EXACT, tiles};
-    if (tiles >= 256) return {SLH_SGEMM_SPLIT128, tiles};
-    return {SLH_SGEMM_SPLIT64, ((d->M + 63) / 64) * tiles_n};
+int sgemm_choose(const slh_sgemm_desc* d, sgemm_choice& f) {
+    const long M = d->M, tiles_n = ((long)d->N + SBN - 1) / SBN;
+    long tiles = (M + SBM - 1) / SBM * tiles_n;
+    f.form = !(d->split_bf16 == 1 && d->K % TBK == 0 && (d->mode == 0 || d->cin % TBK == 0)) ? SLH_SGEMM_EXACT
+             : tiles >= 256                                                                   ? SLH_SGEMM_SPLIT128
+                                                                                              : SLH_SGEMM_SPLIT64;
+    if (f.form == SLH_SGEMM_SPLIT64) tiles = (M + 63) / 64 * tiles_n;
+    dim3 grid;
+    if (const int rc = launch_grid("slh_sgemm", tiles * 256, M * d->N, grid)) return rc;
+    f.grid = (int)grid.x;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int slh_vae_post_quant(const slh_vae_conv_desc* d, slh_stream_t stream) {
+    SLH_CHECK(d && d->x && d->qw && d->qb && d->y, "slh_vae_post_quant: bad descriptor");
+    if (const int rc = launch_flat<vae_post_quant_kernel>("slh_vae_post_quant", (long)d->batch * d->h * d->wd, stream, *d)) return rc;
+    SLH_LAUNCH_CHECK("slh_vae_post_quant");
+    return 0;
 }
 
 extern "C" int slh_sgemm(const slh_sgemm_desc* d, slh_stream_t stream) {
@@ -597,7 +587,8 @@ extern "C" int slh_sgemm(const slh_sgemm_desc* d, slh_stream_t stream) {
         SLH_CHECK(d->mode == 0, "slh_sgemm: bad mode");
         SLH_CHECK(d->upsample == 0, "slh_sgemm: upsample is a conv-mode read");
     }
-    const sgemm_choice f = sgemm_choose(d);
+    sgemm_choice f;
+    if (const int rc = sgemm_choose(d, f)) return rc;
     hipStream_t s = (hipStream_t)stream;
     switch (f.form) {
         case SLH_SGEMM_SPLIT128: slh_launch<sgemm_bf16x3_kernel<128>>(f.grid, 256, s, *d, "split<%d>", 128); break;
@@ -648,25 +639,24 @@ extern "C" int slh_gn32_stats(const slh_gn32_desc* d, slh_stream_t stream) {
 extern "C" int slh_gn32_apply(const slh_gn32_desc* d, slh_stream_t stream) {
     if (gn32_check(d, "slh_gn32_apply")) return -1;
     SLH_CHECK(d->y && d->gamma && d->beta && d->ldy % 4 == 0, "slh_gn32_apply: null pointer / ldy");
-    const long total = (long)d->batch * d->hw * (d->C / 4);
-    hipLaunchKernelGGL(gn32_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d);
+    if (const int rc = launch_flat<gn32_apply_kernel>("slh_gn32_apply", (long)d->batch * d->hw * (d->C / 4), stream, *d)) return rc;
     SLH_LAUNCH_CHECK("slh_gn32_apply");
     return 0;
 }
 
 extern "C" int slh_softmax32(const slh_softmax32_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->x && d->rows > 0 && d->cols > 0 && d->cols % 4 == 0 && d->ld % 4 == 0, "slh_softmax32: bad arguments");
-    hipLaunchKernelGGL(softmax32_kernel, dim3(d->rows), dim3(256), 0, (hipStream_t)stream, d->x, d->rows, d->cols, (long)d->ld);
+    if (const int rc = launch_flat<softmax32_kernel>("slh_softmax32", (long)d->rows * 256, stream, *d)) return rc;      // a workgroup per row
     SLH_LAUNCH_CHECK("slh_softmax32");
     return 0;
 }
 
+// conv_in and moments decode their pixel through pixel_of_row, whose rows are ints (as slh_sgemm's M is)
 extern "C" int slh_vae_conv_in(const slh_vae_conv_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->x && d->w && d->bias && d->y && d->cout % 4 == 0 && (d->cin == 3 || d->cin == 4), "slh_vae_conv_in: bad descriptor");
-    const long total = (long)d->batch * d->h * d->wd * (d->cout / 4);
-    hipLaunchKernelGGL(vae_conv_in_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)d->x, (const float*)d->w, (const float*)d->bias, (float*)d->y, d->batch, d->h, d->wd, d->cout,
-                       d->cin);
+    const long pix = (long)d->batch * d->h * d->wd;
+    SLH_CHECK(pix < (1L << 31), "slh_vae_conv_in: %ld pixels: more than 2^31 - 1", pix);
+    if (const int rc = launch_flat<vae_conv_in_kernel>("slh_vae_conv_in", pix * (d->cout / 4), stream, *d)) return rc;
     SLH_LAUNCH_CHECK("slh_vae_conv_in");
     return 0;
 }
@@ -674,17 +664,15 @@ extern "C" int slh_vae_conv_in(const slh_vae_conv_desc* d, slh_stream_t stream) 
 extern "C" int slh_vae_moments(const slh_vae_conv_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->x && d->w && d->bias && d->qw && d->qb && d->y && d->cin % 4 == 0, "slh_vae_moments: bad descriptor");
     const long pix = (long)d->batch * d->h * d->wd;
-    hipLaunchKernelGGL(vae_moments_kernel, dim3((unsigned)((pix + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)d->x, (const float*)d->w, (const float*)d->bias, (const float*)d->qw, (const float*)d->qb,
-                       (float*)d->y, d->batch, d->h, d->wd, d->cin);
+    SLH_CHECK(pix < (1L << 31), "slh_vae_moments: %ld pixels: more than 2^31 - 1", pix);
+    if (const int rc = launch_flat<vae_moments_kernel>("slh_vae_moments", pix * 64, stream, *d)) return rc;              // a wave per pixel
     SLH_LAUNCH_CHECK("slh_vae_moments");
     return 0;
 }
 
 extern "C" int slh_vae_sample(const slh_vae_sample_desc* d, slh_stream_t stream) {
     SLH_CHECK(d && d->moments && d->post_noise && d->noise && (d->noisy_bf16 || d->noisy_f32 || d->latent_f32), "slh_vae_sample: null pointer");
-    const long n = (long)d->batch * 4 * d->hw;
-    hipLaunchKernelGGL(vae_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d);
+    if (const int rc = launch_flat<vae_sample_kernel>("slh_vae_sample", (long)d->batch * 4 * d->hw, stream, *d)) return rc;
     SLH_LAUNCH_CHECK("slh_vae_sample");
     return 0;
 }

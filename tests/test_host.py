@@ -1931,6 +1931,35 @@ def test_sgemm_form_comes_from_the_library_and_bad_descriptors_are_refused():
     assert lib.sgemm_form(conv(stride=2, pad=0, ho=4, wo=3, M=24)) == "split<64>"
 
 
+def test_vae_launches_too_large_for_one_grid_are_refused():
+    """A launch of csrc/vae.hip that would need 2^31 workgroups or more is refused on the host, in the entry point's name, instead of
+    wrapping its grid (launch_grid, csrc/common.h).  The pointers are made up and nothing is launched: every call below is refused.
+    The flat entry points have no query mode, so only their refusals are asserted; slh_sgemm has one (slh_sgemm_form), and there the
+    largest tile product below 2^31 with the same M is shown to pass.  slh_vae_moments (a workgroup per four pixels) and slh_vae_conv_in
+    index their pixels in int, so 2^31 pixels and more are refused before the grid is sized - 2^33 pixels would not fit it either."""
+    one, grid = 0x1000, "too large for one launch"
+    conv = dict(x=one, w=one, bias=one, qw=one, qb=one, y=one)
+    flat = [
+        ("slh_vae_sample", lib.OP_VAE_SAMPLE, lib.VaeSampleDesc(moments=one, post_noise=one, noise=one, noisy_f32=one, batch=1 << 20, hw=1 << 18), grid),
+        ("slh_vae_post_quant", lib.OP_VAE_POST_QUANT, lib.VaeConvDesc(**conv, batch=1 << 9, h=1 << 15, wd=1 << 15, cin=0), grid),       # 2^39 threads
+        ("slh_vae_conv_in", lib.OP_VAE_CONV_IN, lib.VaeConvDesc(**conv, batch=1 << 10, h=1 << 10, wd=1 << 10, cin=3, cout=1 << 11), grid),  # 2^30 px x 2^9
+        ("slh_vae_conv_in", lib.OP_VAE_CONV_IN, lib.VaeConvDesc(**conv, batch=2, h=1 << 15, wd=1 << 15, cin=3, cout=4), "pixels"),
+        ("slh_vae_moments", lib.OP_VAE_MOMENTS, lib.VaeConvDesc(**conv, batch=8, h=1 << 15, wd=1 << 15, cin=4), "pixels"),              # 2^33 pixels
+        ("slh_gn32_apply", lib.OP_GN32_APPLY, lib.Gn32Desc(x=one, gamma=one, beta=one, stats=one, y=one, ldx=1024, ldy=1024, C=1024, batch=1 << 10,
+                                                           hw=1 << 21, groups=32), grid),                                                # 2^39 threads
+    ]
+    for name, op, d, what in flat:
+        with pytest.raises(lib.SlidersHipError, match=f"{name}: .*{what}"):
+            lib.call(op, d, 0)
+    # slh_sgemm, exact form (split_bf16 = 0): 2^16 x 2^15 tiles of 128 x 128 are 2^31 workgroups; one tile column less fits
+    big = dict(x=one, w=one, c=one, ldx=16, ldw=16, ldc=1 << 22, M=1 << 23, K=16, mode=0, alpha=1.0, split_bf16=0)
+    with pytest.raises(lib.SlidersHipError, match=f"slh_sgemm: .*{grid}"):
+        lib.sgemm_form(lib.SgemmDesc(**big, N=1 << 22))
+    assert lib.sgemm_form(lib.SgemmDesc(**big, N=(1 << 22) - 128)) == "exact"
+    with pytest.raises(lib.SlidersHipError, match=f"slh_sgemm: .*{grid}"):          # and in int the product of 2^24 x 2^24 tiles was 0
+        lib.sgemm_form(lib.SgemmDesc(**dict(big, M=(1 << 31) - 1, N=(1 << 31) - 4, ldc=(1 << 31) - 4)))
+
+
 def test_vae_bounds_admit_the_standins():
     """Every case of the matrix: the stand-in - fp32 arithmetic, for the split form the explicit bf16 halves - meets every bound; the
     evaluated dropped-product term of every split case stays below 3 * 2^-18 |alpha| sum |x||w| (the figure for operands spread over
