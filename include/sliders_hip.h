@@ -586,6 +586,40 @@ typedef struct slh_ddpm_edit_blend_desc {
 } slh_ddpm_edit_blend_desc;
 int slh_ddpm_edit_blend(const slh_ddpm_edit_blend_desc* d, slh_stream_t stream);
 
+/* One step of the second-order residual noise space (csrc/edit_step2.hip, docs/EDIT.md, "Second-order noise space"): the mean of
+ * slh_ddpm_edit_step with the multistep correction of SDE-DPM-Solver++ 2M added, its mode branch, and with keep / mask the blend of
+ * slh_ddpm_edit_blend, in one launch.  Never recorded in a program: no opcode, no descriptor struct; three host arrays, as
+ * slh_sigma_step.  Per element, with u, t the bf16 epsilon halves and x the master latent, fp32 throughout, one rounding per
+ * operation, nothing contracted:
+ *   e    = u + g (t - u)
+ *   x0h, mu_1                            the predicted clean sample and the mean, by the device code slh_ddpm_edit_step forms them with
+ *   with x0_prev:  d = x0h - x0_prev;  p = c_corr * d;  mu = mu_1 + p        without: mu = mu_1 (the term is skipped, not multiplied)
+ *   mode 0 (invert): resid = target - mu is written;   mode 1 (edit): resid is read;   both: o = mu + resid
+ *   with keep / mask (k, m = mask[b*hw + i % hw]):  o = m == 0 ? k : m == 1 ? o : k + m * (o - k)
+ *   out = o;  x0_out = x0h;  out_bf16 = out2_bf16 = round-to-nearest-even(o)
+ * Without x0_prev, out, resid and the bf16 copies are those of slh_ddpm_edit_step (with keep / mask: slh_ddpm_edit_blend) bit for bit.
+ * ptrs[12]: 0 eps       bf16 [2*nb][chw], unconditional half first
+ *           1 eps_text  optional, as slh_cfg_ddim_desc
+ *           2 x         fp32 [nb][chw]
+ *           3 x0_prev   optional fp32 [nb][chw]: x0h of the same chain's step before; NULL: first order
+ *           4 target    fp32 [nb][chw], mode 0 only (mode 1: not read, may be NULL)
+ *           5 resid     fp32 [nb][chw]; mode 0: written, mode 1: read
+ *           6 keep      optional fp32 [nb][chw]: the inversion's latent after this step (with mask)
+ *           7 mask      optional fp32 [nb][hw] in [0, 1], one value per latent pixel (with keep; mode 1 only)
+ *           8 out       fp32 [nb][chw]; may be x itself
+ *           9 x0_out    optional fp32 [nb][chw]; may be x0_prev itself
+ *           10, 11 out_bf16, out2_bf16   optional bf16 [nb][chw]: the two halves of the CFG pair's sample input
+ * dims[5]:  0 nb, 1 chw, 2 hw (chw % hw == 0), 3 mode (0 invert, 1 edit), 4 v_prediction (0, 1)
+ * coef[7]:  0 guidance, 1 c_sqrt_beta_t, 2 c_inv_sqrt_alpha_t, 3 c_sqrt_alpha_t, 4 c_sqrt_alpha_prev, 5 c_dir (as slh_ddpm_edit_desc),
+ *           6 c_corr = B h / (2 h_old), B = c_sqrt_alpha_prev - c_dir c_sqrt_alpha_t / c_sqrt_beta_t (read only with x0_prev)
+ * Every thread reads all it needs before it writes, which is what makes the two aliases legal.  16-byte fp32 / 8-byte bf16 accesses
+ * (four elements per thread) where every pointer, chw and hw allow them, one element per thread otherwise; any chw >= 1 works.
+ * Refused before the launch (slh_last_error): a null ptrs / dims / coef, eps, x, resid or out; an fp32 pointer that is not 4-byte or a
+ * bf16 pointer that is not 2-byte aligned; nb < 1, chw < 1, hw < 1, chw % hw != 0; mode or v_prediction out of range; keep without
+ * mask or mask without keep; mode 0 without target, or with a mask; x0_prev with a c_corr that is zero or not finite; an output
+ * overlapping an input (keep and mask included) other than out == x and x0_out == x0_prev; two outputs overlapping. */
+int slh_edit_step2(const void* const* ptrs, const int32_t* dims, const float* coef, slh_stream_t stream);
+
 /* Where two epsilon predictions differ, per latent pixel: with e = u + guidance * (t - u) of each pair (fp32, no contraction),
  *   out[b][p] = sum over c = 0 .. chw/hw - 1, ascending, of |e_a - e_b| at (b, c, p).
  * One thread per pixel, a fixed order and no atomics: bit-reproducible. */

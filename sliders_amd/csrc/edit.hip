@@ -28,30 +28,10 @@ namespace {
 
 using namespace slh_step_detail;
 
-// the coefficients both step kernels read from their descriptors
-struct mu_coef {
-    float guidance, c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev, c_dir;
-    int v_prediction;
-};
+// the coefficients both step kernels read from their descriptors (mu_coef, ddpm_mu: step_common.h, shared with csrc/edit_step2.hip)
 template <typename D>
 __device__ __forceinline__ mu_coef coef_of(const D& d) {
     return mu_coef{d.guidance, d.c_sqrt_beta_t, d.c_inv_sqrt_alpha_t, d.c_sqrt_alpha_t, d.c_sqrt_alpha_prev, d.c_dir, d.v_prediction};
-}
-
-// CFG combine + the DDIM mean of x_{t-1} from the epsilon halves u, t and the master latent x
-__device__ __forceinline__ float ddpm_mu(const mu_coef& c, float u, float t, float x) {
-#pragma clang fp contract(off)
-    // 8 roundings on the longest path from the inputs to mu (epsilon prediction; 7 with v prediction): docs/EDIT.md counts them
-    const float e = cfg_combine(u, t, c.guidance);
-    float x0, pe;
-    if (c.v_prediction) {
-        x0 = c.c_sqrt_alpha_t * x - c.c_sqrt_beta_t * e;
-        pe = c.c_sqrt_alpha_t * e + c.c_sqrt_beta_t * x;
-    } else {
-        x0 = (x - c.c_sqrt_beta_t * e) * c.c_inv_sqrt_alpha_t;
-        pe = e;
-    }
-    return c.c_sqrt_alpha_prev * x0 + c.c_dir * pe;
 }
 
 __global__ __launch_bounds__(256) void ddpm_edit_kernel(const slh_ddpm_edit_desc d) {

@@ -1,5 +1,5 @@
-// The pieces the element-wise step kernels share (edit.hip, sigma_step.hip, latent_blend.hip, eps_direction.hip): the CFG combine, the
-// select-then-lerp blend, the text half of an epsilon pair, vector-or-scalar operand access and the bf16 copies of a result; on the
+// The pieces the element-wise step kernels share (edit.hip, edit_step2.hip, sigma_step.hip, latent_blend.hip, eps_direction.hip): the
+// CFG combine, the DDIM mean of the edit steps, the select-then-lerp blend, the text half of an epsilon pair, vector-or-scalar operand access and the bf16 copies of a result; on the
 // host the alignment, overlap and shape checks (the launch sizing is common.h's launch_grid).  Each is stated here once.  These kernels are held bit for bit
 // to plain-torch restatements in the same operation order (tests/*_ref.py, edit.ddpm_mu_reference, edit.blend_reference): fp32, one
 // rounding per operation, nothing contracted.
@@ -26,6 +26,33 @@ __device__ __forceinline__ float blend_one(float e, float k, float m) {
 #pragma clang fp contract(off)      // the product and the sum must stay two instructions
     const float o = k + m * (e - k);
     return m == 0.0f ? k : m == 1.0f ? e : o;
+}
+
+// the coefficients of the DDIM mean, as the edit step kernels read them from their descriptors or their coef array
+struct mu_coef {
+    float guidance, c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev, c_dir;
+    int v_prediction;
+};
+
+// CFG combine + the DDIM mean of x_{t-1} from the epsilon halves u, t and the master latent x; the predicted clean sample through x0.
+// The one piece of code slh_ddpm_edit_step, slh_ddpm_edit_blend and slh_edit_step2 form them with.
+__device__ __forceinline__ float ddpm_mu_x0(const mu_coef& c, float u, float t, float x, float& x0) {
+#pragma clang fp contract(off)
+    // 8 roundings on the longest path from the inputs to mu (epsilon prediction; 7 with v prediction): docs/EDIT.md counts them
+    const float e = cfg_combine(u, t, c.guidance);
+    float pe;
+    if (c.v_prediction) {
+        x0 = c.c_sqrt_alpha_t * x - c.c_sqrt_beta_t * e;
+        pe = c.c_sqrt_alpha_t * e + c.c_sqrt_beta_t * x;
+    } else {
+        x0 = (x - c.c_sqrt_beta_t * e) * c.c_inv_sqrt_alpha_t;
+        pe = e;
+    }
+    return c.c_sqrt_alpha_prev * x0 + c.c_dir * pe;
+}
+__device__ __forceinline__ float ddpm_mu(const mu_coef& c, float u, float t, float x) {
+    float x0;
+    return ddpm_mu_x0(c, u, t, x, x0);
 }
 
 // The text half of an epsilon pair of n elements each: its own buffer where one is given, else the rows behind the unconditional

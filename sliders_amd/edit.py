@@ -22,6 +22,10 @@ bf16 rounding.
 `NoiseSpace`                                           what an inversion leaves: x0, X_0, the residuals, the reconstruction, its latents
 `SliderEditor`                                         SliderSampler + invert / edit_latents / edit / footprint on the engine
 
+`ddpm_step2_coefficients` / `ddpm_mu2_reference`        the second-order space (invert(order=2), --order 2; docs/EDIT.md "Second-order noise
+                                                       space"): mu gains c_corr (x0h - x0h of the chain's step before), one launch of
+                                                       slh_edit_step2 per step; NoiseSpace.order says which, and every edit reads it
+
 Localised edits (mask=, --mask / --auto_mask): every step of an edit is blended against the latent the inversion itself had after
 that step (NoiseSpace.visited, slh_ddpm_edit_blend), so outside the mask the result is the reconstruction bit for bit.  The mask
 comes from a file (`load_mask`, `feather_mask`) or from where the slider changes the predicted noise on this image
@@ -84,14 +88,61 @@ def _f32(v: float) -> float:
 
 
 def fp32_coefficients(coef: dict) -> dict:
-    """The descriptor's five scalars rounded to fp32 (as Python floats): what the kernel multiplies with"""
-    return {k: _f32(coef[k]) for k in COEFFICIENTS}
+    """The descriptor's five scalars rounded to fp32 (as Python floats): what the kernel multiplies with; and c_corr where the step
+    has one (`ddpm_step2_coefficients`)"""
+    return {k: _f32(coef[k]) for k in COEFFICIENTS + (("c_corr",) if "c_corr" in coef else ())}
+
+
+def check_order(order: int) -> int:
+    if order not in (1, 2):
+        raise ValueError(f"order = {order!r}: expected 1 or 2")
+    return int(order)
+
+
+def ddpm_step2_coefficients(schedule: DDIMSchedule, t: int, steps: int, eta: float = 1.0, t_older: Optional[int] = None) -> dict:
+    """`ddpm_step_coefficients` of the step from t, and, where the step is second order, c_corr: the weight of x0h(t) - x0h(t_older)
+    in the mean (docs/EDIT.md, "Second-order noise space").  With lambda = ln(sqrt(a) / sqrt(1 - a)),
+
+        h = lambda(prev) - lambda(t)    h_old = lambda(t) - lambda(t_older)
+        B = c_sqrt_alpha_prev - c_dir c_sqrt_alpha_t / c_sqrt_beta_t          d mu_1 / d x0h at fixed x, epsilon and v prediction alike
+        c_corr = B h / (2 h_old)
+
+    in float64.  t_older: the grid point before t; None on the grid's first step.  There, and on the last step (prev < 0: lambda(prev)
+    is infinite with alpha_prev = 1, the `lower_order_final` of the multistep solvers), the step is first order and the dict has no c_corr."""
+    coef = ddpm_step_coefficients(schedule, t, steps, eta)
+    prev = t - schedule.num_train_timesteps // steps
+    if t_older is None or prev < 0:
+        return coef
+    if not t_older > t:
+        raise ValueError(f"t_older = {t_older}: expected the grid point before t = {t}")
+    lam = lambda a: 0.5 * (math.log(a) - math.log1p(-a))
+    a_t, a_p, a_o = (float(schedule.alphas_cumprod[k]) for k in (t, prev, t_older))
+    h, h_old = lam(a_p) - lam(a_t), lam(a_t) - lam(a_o)
+    B = coef["c_sqrt_alpha_prev"] - coef["c_dir"] * coef["c_sqrt_alpha_t"] / coef["c_sqrt_beta_t"]
+    return dict(coef, c_corr=0.5 * B * h / h_old)
+
+
+def chain_coefficients(schedule: DDIMSchedule, ts: List[int], i: int, steps: int, eta: float, order: int = 1) -> dict:
+    """the scalars of step i of the grid ts for a chain of this order"""
+    if order == 1:
+        return ddpm_step_coefficients(schedule, ts[i], steps, eta)
+    return ddpm_step2_coefficients(schedule, ts[i], steps, eta, ts[i - 1] if i > 0 else None)
 
 
 def ddpm_mu_reference(eps_uncond: torch.Tensor, eps_text: torch.Tensor, x: torch.Tensor, coef: dict, guidance: float,
                       v_prediction: bool = False, dtype=torch.float64) -> torch.Tensor:
     """mu of one step from the bf16 epsilon halves and the master latent, on the fp32 values of the scalars.  float64: the oracle.
     float32: one tensor operation per operation of ddpm_edit_kernel, in its order - each rounds once, nothing is contracted."""
+    return ddpm_mu2_reference(eps_uncond, eps_text, x, {k: coef[k] for k in COEFFICIENTS}, guidance, v_prediction, dtype)[0]
+
+
+def ddpm_mu2_reference(eps_uncond: torch.Tensor, eps_text: torch.Tensor, x: torch.Tensor, coef: dict, guidance: float,
+                       v_prediction: bool = False, dtype=torch.float64, x0_prev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mu, x0h) of one step of the second-order chain: mu_1 and x0h as `ddpm_mu_reference` forms them, and where coef has a c_corr
+    (`ddpm_step2_coefficients`) and x0_prev - the same chain's x0h one step earlier - is given, mu = mu_1 + c_corr (x0h - x0_prev).
+    float64: the oracle.  float32: one tensor operation per operation of edit_step2_kernel, in its order."""
+    if ("c_corr" in coef) != (x0_prev is not None):
+        raise ValueError("ddpm_mu2_reference: c_corr and x0_prev go together (neither on a first-order step)")
     c = {k: torch.tensor(v, dtype=dtype) for k, v in fp32_coefficients(coef).items()}
     g = torch.tensor(_f32(guidance), dtype=dtype)
     u, t, x = eps_uncond.to(dtype), eps_text.to(dtype), x.to(dtype)
@@ -102,7 +153,12 @@ def ddpm_mu_reference(eps_uncond: torch.Tensor, eps_text: torch.Tensor, x: torch
     else:
         x0 = (x - c["c_sqrt_beta_t"] * e) * c["c_inv_sqrt_alpha_t"]
         pe = e
-    return c["c_sqrt_alpha_prev"] * x0 + c["c_dir"] * pe
+    mu = c["c_sqrt_alpha_prev"] * x0 + c["c_dir"] * pe
+    if x0_prev is not None:
+        d = x0 - x0_prev.to(dtype)
+        p = c["c_corr"] * d
+        mu = mu + p
+    return mu, x0
 
 
 def build_path(schedule: DDIMSchedule, x0: torch.Tensor, ts: List[int], seed: int) -> torch.Tensor:
@@ -136,6 +192,7 @@ class NoiseSpace:
     time_ids: Optional[torch.Tensor] = None
     visited: Optional[torch.Tensor] = None      # [len(timesteps)][bs][4][h][w] the latent after each step of the inversion's own chain
                                                 # (visited[-1] == recon): what a masked edit keeps outside the mask
+    order: int = 1                              # 1: the DDIM mean; 2: with the multistep correction (every edit of the space reads it)
 
     def _map(self, fn) -> dict:
         return {f.name: fn(getattr(self, f.name)) if torch.is_tensor(getattr(self, f.name)) else getattr(self, f.name) for f in fields(self)}
@@ -147,11 +204,13 @@ class NoiseSpace:
     @classmethod
     def load(cls, path: str, device=None) -> "NoiseSpace":
         d = torch.load(path, map_location="cpu")
-        missing = [f.name for f in fields(cls) if f.name not in d and f.name != "visited"]       # files from before masked edits have none
+        # files from before masked edits have no visited, files from before the second-order space no order: they are first order
+        missing = [f.name for f in fields(cls) if f.name not in d and f.name not in ("visited", "order")]
         if missing:
             raise KeyError(f"{path}: not a saved NoiseSpace (no {missing})")
         d = {f.name: d.get(f.name) for f in fields(cls)}
         d["timesteps"] = [int(t) for t in d["timesteps"]]
+        d["order"] = check_order(1 if d["order"] is None else d["order"])
         sp = cls(**d)
         return sp.to(device) if device is not None else sp
 
@@ -163,24 +222,33 @@ Predict = Callable[[torch.Tensor, int, float], Tuple[torch.Tensor, torch.Tensor]
 
 
 def invert_reference(predict: Predict, x0: torch.Tensor, schedule: DDIMSchedule, steps: int = 50, skip: Optional[int] = None,
-                     eta: float = 1.0, guidance: float = 7.5, seed: int = 0, dtype=torch.float32) -> NoiseSpace:
-    """The inversion over predict(x_bf16, t, multiplier) -> (eps_uncond, eps_text), multiplier 0 throughout."""
+                     eta: float = 1.0, guidance: float = 7.5, seed: int = 0, dtype=torch.float32, order: int = 1) -> NoiseSpace:
+    """The inversion over predict(x_bf16, t, multiplier) -> (eps_uncond, eps_text), multiplier 0 throughout.  order 2: every step but
+    the first and the last adds the correction from the chain's own x0h of the step before (`ddpm_mu2_reference`)."""
+    check_order(order)
     ts = edit_timesteps(schedule, steps, skip)
     x0 = x0.to(dtype)
     path = build_path(schedule, x0, ts, seed)
     v = schedule.prediction_type == "v_prediction"
     x = path[0].clone()
     resid, visited = torch.empty_like(path), torch.empty_like(path)
+    hist = None
     for i, t in enumerate(ts):
         eu, et = predict(x.to(torch.bfloat16), t, 0.0)
-        mu = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, steps, eta), guidance, v, dtype)
+        mu, hist = _mu_step(eu, et, x, schedule, ts, i, steps, eta, guidance, v, dtype, order, hist)
         target = path[i + 1] if i + 1 < len(ts) else x0
         resid[i] = target - mu
         x = mu + resid[i]                     # NOT target: the edit can only recompute mu + d
         visited[i] = x
     return NoiseSpace(x0=x0, x_start=path[0].clone(), resid=resid, recon=x, timesteps=list(ts), steps=int(steps),
                       skip=steps - len(ts), eta=float(eta), guidance=float(guidance), prediction_type=schedule.prediction_type,
-                      seed=int(seed), visited=visited)
+                      seed=int(seed), visited=visited, order=order)
+
+
+def _mu_step(eu, et, x, schedule, ts, i, steps, eta, guidance, v, dtype, order, hist):
+    """(mu, x0h) of step i of a reference chain of this order; hist: the chain's x0h of step i - 1 (read only where the step has a c_corr)"""
+    coef = chain_coefficients(schedule, ts, i, steps, eta, order)
+    return ddpm_mu2_reference(eu, et, x, coef, guidance, v, dtype, hist if "c_corr" in coef else None)
 
 
 def as_mask(mask: torch.Tensor, bs: int, h: int, w: int) -> torch.Tensor:
@@ -209,34 +277,44 @@ def blend_reference(e: torch.Tensor, keep: torch.Tensor, mask: torch.Tensor, dty
 
 
 def edit_reference(predict: Predict, space: NoiseSpace, schedule: DDIMSchedule, scale: float = 0.0, start_noise: int = 750,
-                   guidance: Optional[float] = None, dtype=torch.float32, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   guidance: Optional[float] = None, dtype=torch.float32, mask: Optional[torch.Tensor] = None,
+                   order: Optional[int] = None) -> torch.Tensor:
     """The edit at slider scale `scale` (multiplier 0 while t > start_noise, as SliderSampler.sample_latents).  mask: every step is
-    blended against the inversion's latent after that step (space.visited), so the result is space.recon outside the mask."""
+    blended against the inversion's latent after that step (space.visited), so the result is space.recon outside the mask.
+    order None: the space's own (another order is another image; no reconstruction claim applies).  At order 2 the history is the
+    edit chain's own x0h, formed on the blended and guided latent of the step before."""
+    order = check_order(space.order if order is None else order)
     g = space.guidance if guidance is None else guidance
     v = schedule.prediction_type == "v_prediction"
     x = space.x_start.to(dtype).clone()
     if mask is not None:
-        space = trajectory_reference(predict, space, schedule, dtype)
+        space = trajectory_reference(predict, space, schedule, dtype, order)
         mask = as_mask(mask, x.shape[0], x.shape[2], x.shape[3])
+    hist = None
     for i, t in enumerate(space.timesteps):
         eu, et = predict(x.to(torch.bfloat16), t, 0.0 if t > start_noise else float(scale))
-        mu = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, space.steps, space.eta), g, v, dtype)
+        mu, hist = _mu_step(eu, et, x, schedule, space.timesteps, i, space.steps, space.eta, g, v, dtype, order, hist)
         x = mu + space.resid[i].to(dtype)
         if mask is not None:
             x = blend_reference(x, space.visited[i], mask, dtype)
     return x
 
 
-def trajectory_reference(predict: Predict, space: NoiseSpace, schedule: DDIMSchedule, dtype=torch.float32) -> NoiseSpace:
-    """Fills a missing space.visited by the scale-0 replay (SliderEditor.trajectory over predict); raises if it does not end on recon"""
+def trajectory_reference(predict: Predict, space: NoiseSpace, schedule: DDIMSchedule, dtype=torch.float32,
+                         order: Optional[int] = None) -> NoiseSpace:
+    """Fills a missing space.visited by the scale-0 replay (SliderEditor.trajectory over predict); raises if it does not end on recon.
+    order None: the space's own."""
     if space.visited is not None:
         return space
+    order = check_order(space.order if order is None else order)
     v = schedule.prediction_type == "v_prediction"
     x = space.x_start.to(dtype).clone()
     visited = torch.empty_like(space.resid, dtype=dtype)
+    hist = None
     for i, t in enumerate(space.timesteps):
         eu, et = predict(x.to(torch.bfloat16), t, 0.0)
-        x = ddpm_mu_reference(eu, et, x, ddpm_step_coefficients(schedule, t, space.steps, space.eta), space.guidance, v, dtype) + space.resid[i].to(dtype)
+        mu, hist = _mu_step(eu, et, x, schedule, space.timesteps, i, space.steps, space.eta, space.guidance, v, dtype, order, hist)
+        x = mu + space.resid[i].to(dtype)
         visited[i] = x
     if not torch.equal(x, space.recon.to(dtype)):
         raise RuntimeError("trajectory_reference: the scale-0 replay does not end on space.recon bit for bit")
@@ -451,18 +529,27 @@ class SliderEditor(SliderSampler):
         drv.load_cond(ctx, pooled, time_ids)
         return drv
 
-    def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None, eps_text=0):
+    def _launch_step(self, p, t, steps, eta, guidance, src, dst, resid_i, target=None, keep=None, mask=None, eps_text=0, hist=None,
+                     t_older=None):
         """The step's one element-wise launch after the UNet pass, src -> dst (fp32, may be one tensor) and the bf16 halves of `sample`:
         slh_ddpm_edit_step - mode 0 with a target (resid_i written), else mode 1 (resid_i read) - or, with a mask, slh_ddpm_edit_blend
         against keep.  eps_text: the address of a text row to read in place of the one behind the unconditional half (a direction
-        step's guided row; p is then the wide plan, whose first two row blocks are the pair's)"""
+        step's guided row; p is then the wide plan, whose first two row blocks are the pair's).
+        hist (fp32, src's shape: a second-order chain): the launch is slh_edit_step2 in all these forms; it reads the chain's x0h of
+        the step from t_older out of hist where the step is second order (`ddpm_step2_coefficients`) and leaves its own x0h there."""
         io, bs, chw = p.io, src.shape[0], src[0].numel()
         smp = io["sample"]
         common = dict(eps=io["eps"].ptr, eps_text=eps_text, x=src.data_ptr(), resid=resid_i.data_ptr(), out=dst.data_ptr(), out_bf16=smp.ptr,
                       out2_bf16=smp.ptr + bs * chw * 2, nb=bs, chw=chw, guidance=float(guidance),
-                      v_prediction=1 if self.sched.prediction_type == "v_prediction" else 0,
-                      **fp32_coefficients(ddpm_step_coefficients(self.sched, t, steps, eta)))
+                      v_prediction=1 if self.sched.prediction_type == "v_prediction" else 0)
         s = torch.cuda.current_stream().cuda_stream
+        if hist is not None:
+            coef = fp32_coefficients(ddpm_step2_coefficients(self.sched, t, steps, eta, t_older))
+            lib.edit_step2(s, x0_prev=hist.data_ptr() if "c_corr" in coef else 0, x0_out=hist.data_ptr(), hw=chw // src.shape[1],
+                           target=0 if target is None else target.data_ptr(), mode=0 if target is not None else 1,
+                           keep=0 if mask is None else keep.data_ptr(), mask=0 if mask is None else mask.data_ptr(), **common, **coef)
+            return
+        common.update(fp32_coefficients(ddpm_step_coefficients(self.sched, t, steps, eta)))
         if mask is None:
             d = lib.DdpmEditDesc(target=0 if target is None else target.data_ptr(), mode=0 if target is not None else 1, **common)
             lib.call(lib.OP_DDPM_EDIT, d, s)
@@ -471,7 +558,7 @@ class SliderEditor(SliderSampler):
             lib.call(lib.OP_DDPM_EDIT_BLEND, d, s)
 
     def _chain(self, drv: Pass, x, ts, steps, eta, guidance, scale, start_noise, resid, path=None, x0=None, record=None, keep=None,
-               mask=None, guide=None):
+               mask=None, guide=None, order=1):
         """x (fp32) through the grid; returns the final latent.  path given = invert (resid written), else edit (resid read).
         record None: x is updated in place.  record [len(ts)][bs][4][h][w]: the same launches, but step i reads record[i - 1] (x for
         i = 0) and writes record[i], so the chain's latents are kept (the inversion, `trajectory`).
@@ -482,8 +569,11 @@ class SliderEditor(SliderSampler):
         moves to the wide plan - the bf16 rounding of the fp32 master, which is what the step before wrote as the plain plan's input,
         into every row block, and the full program, since the direction rows' cross-attention K/V were never projected - and from
         there on every step is wide replay -> guide.guide -> the same step launch reading the guided text row and writing the wide
-        plan's first two row blocks -> guide.spread."""
+        plan's first two row blocks -> guide.spread.
+        order 2: the launches are slh_edit_step2 over one fp32 history buffer of this chain's own (x0h of the step before, updated in
+        place; it belongs to no plan, so the move to the wide plan leaves it as it is)."""
         drv.load_latents(x)
+        hist = torch.empty_like(x) if check_order(order) == 2 else None
         s = torch.cuda.current_stream().cuda_stream
         with self.slider_session(scale, start_noise, zero_merges=False) as gate:
             for i, t in enumerate(ts):
@@ -495,7 +585,7 @@ class SliderEditor(SliderSampler):
                 drv.run(t, gate(t, first), s)
                 target = None if path is None else (path[i + 1] if i + 1 < len(ts) else x0)
                 self._launch_step(drv.p, t, steps, eta, guidance, src, dst, resid[i], target, None if mask is None else keep[i], mask,
-                                  eps_text=guide.guide(s) if wide else 0)
+                                  eps_text=guide.guide(s) if wide else 0, hist=hist, t_older=ts[i - 1] if i > 0 else None)
                 if wide:
                     guide.spread()
         return x if record is None else record[-1].clone()
@@ -503,9 +593,12 @@ class SliderEditor(SliderSampler):
     @torch.no_grad()
     def invert(self, ctx: torch.Tensor, x0_latents: torch.Tensor, steps: int = 50, skip: Optional[int] = None, eta: float = 1.0,
                guidance_scale: float = 7.5, seed: int = 0, pooled: Optional[torch.Tensor] = None,
-               time_ids: Optional[torch.Tensor] = None) -> NoiseSpace:
+               time_ids: Optional[torch.Tensor] = None, order: int = 1) -> NoiseSpace:
         """ctx: (2*bs, 77, D) = cat([unconditional, text]); x0_latents: (bs, 4, h, w) = scaling_factor * posterior mean of the image
-        (VaeEncoder.get_noisy_image's third output with zero noises).  2 * len(grid) launches besides the UNet replays."""
+        (VaeEncoder.get_noisy_image's third output with zero noises).  2 * len(grid) launches besides the UNet replays.
+        order 2: the second-order noise space (docs/EDIT.md; slh_edit_step2 in place of slh_ddpm_edit_step); every edit of the
+        returned space reads its order."""
+        check_order(order)
         ts = edit_timesteps(self.sched, steps, skip)
         ddpm_step_coefficients(self.sched, ts[0], steps, eta)          # validates eta before anything runs
         dev = self.eng.device
@@ -514,12 +607,12 @@ class SliderEditor(SliderSampler):
         drv = self._pass(bs, h, w, ctx, pooled, time_ids)
         path = build_path(self.sched, x0, ts, seed)
         resid, visited = torch.empty_like(path), torch.empty_like(path)
-        x = self._chain(drv, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0, record=visited)
+        x = self._chain(drv, path[0].clone(), ts, steps, eta, guidance_scale, 0.0, -1, resid, path, x0, record=visited, order=order)
         return NoiseSpace(x0=x0, x_start=path[0].clone(), resid=resid, recon=x, timesteps=list(ts), steps=int(steps),
                           skip=steps - len(ts), eta=float(eta), guidance=float(guidance_scale),
                           prediction_type=self.sched.prediction_type, seed=int(seed), ctx=ctx.detach().clone(),
                           pooled=None if pooled is None else pooled.detach().clone(),
-                          time_ids=None if time_ids is None else time_ids.detach().clone(), visited=visited)
+                          time_ids=None if time_ids is None else time_ids.detach().clone(), visited=visited, order=int(order))
 
     def _check_prediction(self, space: NoiseSpace):
         if space.prediction_type != self.sched.prediction_type:
@@ -545,7 +638,7 @@ class SliderEditor(SliderSampler):
         bs, _, h, w = x.shape
         drv = self._pass(bs, h, w, space.ctx, space.pooled, space.time_ids)
         visited = torch.empty_like(resid)
-        end = self._chain(drv, x, space.timesteps, space.steps, space.eta, space.guidance, 0.0, -1, resid, record=visited)
+        end = self._chain(drv, x, space.timesteps, space.steps, space.eta, space.guidance, 0.0, -1, resid, record=visited, order=space.order)
         if not torch.equal(end, space.recon.to(dev)):
             raise RuntimeError("trajectory: the scale-0 replay does not end on space.recon bit for bit: this NoiseSpace was not inverted "
                                "with these weights and this conditioning")
@@ -591,7 +684,8 @@ class SliderEditor(SliderSampler):
         elif direction_momentum is not None:
             raise ValueError("edit_latents: direction_momentum without directions")
         drv = self._pass(bs, h, w, ctx, pooled, time_ids)
-        return self._chain(drv, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask, guide=guide)
+        return self._chain(drv, x, space.timesteps, space.steps, space.eta, g, scale, start_noise, resid, keep=visited, mask=mask, guide=guide,
+                           order=space.order)
 
     @torch.no_grad()
     def footprint(self, space: NoiseSpace, scale: float, start_noise: int = 750, draws: int = 8, t_min: int = 200,
@@ -657,7 +751,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--guidance_scale", type=float, default=7.5)
     p.add_argument("--edit_guidance_scale", type=float, default=None, help="guidance of the edits (default: the inversion's)")
     p.add_argument("--save_inversion", default=None, help="write the NoiseSpace here")
-    p.add_argument("--inversion", default=None, help="edit a saved NoiseSpace instead of inverting --image")
+    p.add_argument("--inversion", "--load_inversion", default=None, help="edit a saved NoiseSpace instead of inverting --image")
+    p.add_argument("--order", type=int, choices=[1, 2], default=None,
+                   help="order of the inversion's solver (default 1; 2: the second-order noise space, for coarser grids); stored by "
+                        "--save_inversion, and not given with --inversion: the file decides")
     p.add_argument("--res", type=int, default=None)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
@@ -695,6 +792,8 @@ def check_args(a):
     """every argument error, before any model is built"""
     if a.inversion and a.save_inversion:
         raise SystemExit("--inversion reads a saved inversion, --save_inversion writes one: give one of them")
+    if a.inversion and a.order is not None:
+        raise SystemExit("--order belongs to the inversion: a saved one (--inversion) carries its own")
     if not a.inversion and not a.image:
         raise SystemExit("--image (or --inversion) is required")
     if not 1 <= a.steps <= 1000:
@@ -883,7 +982,8 @@ def main(argv=None):
         zero = torch.zeros(1, 4, res // 8, res // 8, device=dev)
         x0 = encoder.get_noisy_image(image, zero, zero, 1.0, 0.0)[2].clone()          # scaling_factor * posterior mean, fp32
         del encoder
-        space = ed.invert(ctx, x0, steps=a.steps, skip=a.skip, eta=a.eta, guidance_scale=a.guidance_scale, seed=a.seed, pooled=pooled)
+        space = ed.invert(ctx, x0, steps=a.steps, skip=a.skip, eta=a.eta, guidance_scale=a.guidance_scale, seed=a.seed, pooled=pooled,
+                          order=a.order or 1)
         if a.save_inversion:
             space.save(a.save_inversion)
             print(f"inversion saved to {a.save_inversion}")

@@ -185,7 +185,7 @@ _HOST_FNS = {
 }
 # the step entry points that take (ptrs, dims, coef, stream): three flat arrays instead of a descriptor (_three_arrays calls them)
 _HOST_FNS.update((name, (c_i32, [_P(c_vp), _P(c_i32), _P(c_f32), c_vp])) for name in (
-    "slh_sigma_step", "slh_latent_blend", "slh_direction_threshold", "slh_eps_direction", "slh_eps_direction_momentum"))
+    "slh_sigma_step", "slh_latent_blend", "slh_direction_threshold", "slh_eps_direction", "slh_eps_direction_momentum", "slh_edit_step2"))
 
 EXPORTS = list(_HOST_FNS) + [name for name, _ in _ENTRY.values()]
 
@@ -479,6 +479,18 @@ def latent_blend(stream: int, *, e: int, keep: int, mask: int, out: int, nb: int
     it is 1, keep + m (e - keep) between.  Pointers are device addresses (0: absent); fp32: e / keep / out are fp32 and the bf16 copies
     are rne(out * s_next) (s_next rounded to fp32 here, as the kernel reads it), else they are bf16 and the copies are out's bits."""
     _three_arrays("slh_latent_blend", stream, (e, keep, mask, out, in_bf16, in2_bf16), (nb, chw, hw, 1 if fp32 else 0), (s_next,))
+
+
+def edit_step2(stream: int, *, eps: int, x: int, resid: int, out: int, nb: int, chw: int, hw: int, mode: int, guidance: float,
+               c_sqrt_beta_t: float, c_inv_sqrt_alpha_t: float, c_sqrt_alpha_t: float, c_sqrt_alpha_prev: float, c_dir: float,
+               c_corr: float = 0.0, v_prediction: int = 0, eps_text: int = 0, x0_prev: int = 0, target: int = 0, keep: int = 0, mask: int = 0,
+               x0_out: int = 0, out_bf16: int = 0, out2_bf16: int = 0):
+    """slh_edit_step2 (include/sliders_hip.h): one launch of the second-order edit step.  Pointers are device addresses (0: absent);
+    x0_prev = 0 is a first-order step and c_corr is not read; mode 0 writes resid from target, mode 1 reads it; keep and mask (mode 1)
+    blend the result.  The scalars are rounded to fp32 here, as the kernel reads them."""
+    _three_arrays("slh_edit_step2", stream, (eps, eps_text, x, x0_prev, target, resid, keep, mask, out, x0_out, out_bf16, out2_bf16),
+                  (nb, chw, hw, mode, v_prediction),
+                  (guidance, c_sqrt_beta_t, c_inv_sqrt_alpha_t, c_sqrt_alpha_t, c_sqrt_alpha_prev, c_dir, c_corr))
 
 
 MAX_DIRECTIONS = 3          # prompt pairs per slh_direction_threshold / slh_eps_direction[_momentum] call
